@@ -9,8 +9,18 @@ exchange; no host sync inside the step).  Consecutive steps alternate over --dep
 decoders, each with its own context and stream, so one step's front end overlaps the previous
 step's k_bp tail; every step decodes the whole batch (`depth.one_chain`: the same steps as one chain).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--slots S] [--no-cpu] [--gather]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--slots S] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--slots S] [--no-cpu] [--gather] ...
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline needs and no more: it synthesises the batch, settles the clock,
+runs the W warmup and the K timed steps, writes the last timed step's outputs when --dump-outputs
+DIR is given (DIR/<name>.npy, float64: per-slot counts and the fields of the decoder's result
+records; the batch is seeded, so two builds can be compared array for array) and prints the line:
+metric, value, unit, ms_per_step (the wall-clock milliseconds of one timed step), dtype, config,
+decodes_per_step, ldpc_candidates_per_s, settle, build_id.  Everything else below -- the CPU
+baselines and parity, per-kernel times and rooflines, the one-chain rate, the clock probe, the side
+legs -- is measured only with --full.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks
 itself (a torch.distributed.run child, before this process touches the GPU) and exits with its
@@ -19,10 +29,11 @@ Rank r decodes global slots [256 r, 256 (r + 1)) (per-slot seeds 100000 + slot),
 is the first shard of every larger run.
 
 Prints ONE JSON line on rank 0.  Besides the contract fields it carries:
-  depth         contexts / streams the timed steps alternate over; one_chain: the same K steps on one
-                context and one stream, timed after the loop (N=1)
   settle        untimed steps run before the W warmup steps until consecutive blocks' GPU times agree
                 within 1.5 % (k_bp's clock ramp), their block times; --settle_max 0 turns it off
+  depth         contexts / streams the timed steps alternate over
+and, with --full:
+  depth.one_chain  the same K steps on one context and one stream, timed after the loop (N=1)
   roofline      the dominant kernel (k_bp: LLR + float64 BP + CRC), FLOP-rate vs the FP64 vector peak
   roofline_hbm  the HBM-bound STFT kernel, GB/s vs the 8 TB/s HBM peak
   stages_ms     per-kernel device time per step (HIP events on the decode stream)
@@ -109,6 +120,18 @@ def cpu_synth_worker(args):
     seed, signals = args
     x, _ = synth.make_slots(1, signals, fs=12000, snr_db=(-24.0, -10.0), seeds=[seed], device="cpu")
     return x[0].numpy()
+
+
+def cpu_synth(n_slots, procs, seed0, signals):
+    """The first n_slots slots of rank 0's batch synthesised on the CPU (per-slot seeds seed0 + b),
+    `procs` worker processes, before this process touches the GPU: the bytes the CPU leg of a --full
+    run decodes, so a plain run and a --full run time the same batch.  -> [n_slots, N] float32."""
+    import multiprocessing as mp
+    import numpy as np
+    ctx = mp.get_context("fork")
+    with ctx.Pool(min(procs, n_slots), initializer=_worker_init) as pool:
+        xs = pool.map(cpu_synth_worker, [(seed0 + b, signals) for b in range(n_slots)], chunksize=1)
+    return np.stack(xs)
 
 
 def cpu_worker(args):
@@ -1073,11 +1096,13 @@ class StepLoop:
     def __init__(self, decs, stream_ctxs, x, gatherer=None):
         self.decs, self.ctxs, self.x, self.gatherer = decs, stream_ctxs, x, gatherer
         self.handles = []
+        self.last = None   # the latest step's (records, counts), as its decoder returned them
 
     def step(self, k, keep=False, ev=None):
         D = len(self.decs)
         with self.ctxs[k % D]():
             out, counts = self.decs[k % D].run(self.x)
+            self.last = (out, counts)
             if self.gatherer is not None:
                 h = self.gatherer.start(out, counts)
                 if keep:
@@ -1093,6 +1118,40 @@ class StepLoop:
             out.append((*h.resolve(), h.capacity))
         self.handles.clear()
         return out
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, out, counts, cap, seed=20240):
+    """--dump-outputs: what one step's decoder returned (SlotDecoder.run: ft8_result records
+    [slots, cap] and per-slot counts) -> dirname/<name>.npy, float64.  counts.npy holds every slot's
+    count; each field of the records becomes <field>.npy of shape [kept slots, cap] (payload:
+    [kept slots, cap, 10]) with the rows past a slot's count zeroed (the decoder leaves them
+    unwritten).  All slots are kept while the files stay under DUMP_MAX_BYTES; a larger output keeps a
+    fixed, seeded sample of the slots, listed in kept_slots.npy.  -> {name: shape}."""
+    import numpy as np
+    from ft8_demodulator_amd import _lib
+    dt = _lib.RESULT_DTYPE
+    c = counts.cpu().numpy().astype(np.int64)
+    S = len(c)
+    recs = out[: S * cap * dt.itemsize].cpu().numpy().view(dt).reshape(S, cap)
+    cols = sum(int(np.prod(dt[n_].shape, dtype=np.int64)) for n_ in dt.names)
+    per_slot = cap * cols * 8 + 8           # a kept slot's record columns + its kept_slots.npy entry
+    budget = DUMP_MAX_BYTES - S * 8 - 4096  # counts.npy and the .npy headers
+    keep = np.arange(S)
+    if S * per_slot > budget:
+        keep = np.sort(np.random.default_rng(seed).choice(S, max(1, budget // per_slot), replace=False))
+    valid = np.arange(cap)[None, :] < np.minimum(c[keep], cap)[:, None]
+    arrays = {"counts": c.astype(np.float64), "kept_slots": keep.astype(np.float64)}
+    for n_ in dt.names:
+        a = recs[n_][keep].astype(np.float64)
+        a[~valid] = 0.0
+        arrays[n_] = a
+    os.makedirs(dirname, exist_ok=True)
+    for n_, a in arrays.items():
+        np.save(os.path.join(dirname, n_ + ".npy"), a)
+    return {n_: list(a.shape) for n_, a in arrays.items()}
 
 
 LINE_MAX = 4096   # bytes of the stdout line; the driver's parser gave up on the 23.8 KB r05 line
@@ -1149,7 +1208,7 @@ def compact_line(full, legs_path):
     one = (full.get("depth") or {}).get("one_chain")
     line = {k: full.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup")}
     line["settle_steps"] = full.get("settle_steps", (full.get("settle") or {}).get("steps", 0))
-    for k in ("ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"):
+    for k in ("ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "full", "data"):
         line[k] = full.get(k)
     if "rehearsal" in full:
         line["rehearsal"] = full["rehearsal"]
@@ -1232,6 +1291,13 @@ def main():
                          "step's STFT / sync can start while the previous step's k_bp retires its last waves "
                          "(1: one chain on one stream)")
     ap.add_argument("--signals", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline (set-up, warm-up, the timed steps, the result line): the CPU baselines "
+                         "and parity, the per-kernel times and rooflines, the one-chain rate, the clock probe and "
+                         "every side leg; the --no-* options below switch single legs of a --full run off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step's decoder returned (per-slot "
+                         "counts and the fields of its result records) as DIR/<name>.npy, float64 (rank 0)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-slots", type=int, default=256)
     ap.add_argument("--shard-parity-slots", type=int, default=32,
@@ -1289,15 +1355,23 @@ def main():
     cpu = drift_cpu_port = None
     cpu_x = cpu_dec = None
     shard_sample_wall = None
+    full = args.full
+    if args.sensitivity and not full:
+        ap.error("--sensitivity is a leg of a --full run")
     if rank == 0 and world == 1 and not args.no_cpu and args.cpu_slots > 0:
         procs, basis = host_cores()
-        cpu, cpu_x, cpu_dec = cpu_baseline(kw, min(args.cpu_slots, S), procs, basis, seed0, args.signals)
-        if not args.no_drift:
-            drift_cpu_port = drift_cpu_baseline(procs)
+        if full:
+            cpu, cpu_x, cpu_dec = cpu_baseline(kw, min(args.cpu_slots, S), procs, basis, seed0, args.signals)
+            if not args.no_drift:
+                drift_cpu_port = drift_cpu_baseline(procs)
+        else:
+            # a plain run times the batch a --full run times: the same slots synthesised on the CPU
+            cpu_x = cpu_synth(min(args.cpu_slots, S), procs, seed0, args.signals)
     sub_oracle = None
-    if rank == 0 and world == 1 and not args.no_cpu and not args.no_subtract and args.subtract_oracle_slots > 0:
+    if (full and rank == 0 and world == 1 and not args.no_cpu and not args.no_subtract
+            and args.subtract_oracle_slots > 0):
         sub_oracle = subtract_oracle(args.subtract_oracle_slots, host_cores()[0])
-    if world > 1 and args.shard_parity_slots > 0:
+    if full and world > 1 and args.shard_parity_slots > 0:
         # every rank: the oracle decodes the first slots of this rank's own shard (global seeds
         # 100000 + g) on its share of the host cores, before the GPU is touched; those bytes are
         # the first rows of the rank's batch, so the gathered records of the last timed step are
@@ -1404,10 +1478,14 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     step_ms = [step_ev[i_].elapsed_time(step_ev[i_ + 1]) for i_ in range(args.steps)]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's records and counts, before anything below reuses its decoder's buffers
+        dumped = dump_outputs(args.dump_outputs, loop.last[0], loop.last[1], dec.cap)
     # the same K steps as one chain (D = 1) right after, on the first decoder and the default
     # stream: what the overlap of consecutive steps is worth on this box
     depth1 = None
-    if D > 1 and world == 1:
+    if full and D > 1 and world == 1:
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -1434,38 +1512,6 @@ def main():
                   "capacity_grown": gatherer.grown, "capacity_after": gatherer.capacity,
                   "host_sync_per_step": False}
 
-    # per-kernel durations inside the real step sequence: one pass of `stage_steps` steps per stage,
-    # with HIP events bracketing only that stage's kernel (the rest of the step runs undisturbed);
-    # the BP work counters of the k_bp pass give its algorithmic FLOPs per launch
-    R = max(1, args.stage_steps)
-    stage_ms = {}
-    for st in STAGE_ORDER:
-        ctx.timing(reset=True)
-        if st == "bp":
-            ctx.counters(reset=True)
-            ctx.bp_clock(reset=True)
-        ctx.set_timing(True, stages=[st])
-        for _ in range(R):
-            step(0)   # the first decoder (this context), one chain
-        torch.cuda.synchronize()
-        ctx.set_timing(False)
-        tm = ctx.timing(reset=True)[st]
-        stage_ms[st] = tm[0] / max(tm[1], 1)
-        if st == "bp":
-            cn = ctx.counters(reset=True)
-            bclk = ctx.bp_clock(reset=True)
-    ctx.set_timing(False, stages=None)
-    # the STFT is the first kernel of a step, so an event placed before it also times the host's
-    # launch gap; its launch duration comes from back-to-back re-launches of the step's STFT instead
-    # (ft8_replay_stage), events only around the whole run
-    stft_reps = 20
-    ctx.replay("stft", 2)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    ctx.replay("stft", stft_reps)
-    e1.record()
-    torch.cuda.synchronize()
-    stft_replay_ms = e0.elapsed_time(e1) / stft_reps
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1499,6 +1545,100 @@ def main():
     total_slots = S * world * args.steps
     value = total_slots / elapsed
     K = args.steps
+    q1 = max(1, K // 4)
+    step_times = {"ms": [round(v_, 4) for v_ in step_ms],
+                  "first_quarter_mean_ms": sum(step_ms[:q1]) / q1, "last_quarter_mean_ms": sum(step_ms[-q1:]) / q1,
+                  "from": "HIP events between consecutive timed steps (GPU periods; the line's ms_per_step is the "
+                          "host wall clock around all of them)"}
+    build_id = _lib.lib().ft8_build_id().decode()
+    # the headline: all a plain run reports; a --full run adds the rooflines, baselines and legs below
+    line = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "slots/s",
+        "n_gpus": world,
+        **({"rehearsal": "--share-gpu: every rank on cuda:0 over gloo; not a measurement"} if args.share_gpu else {}),
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / K * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32 (STFT, sync score) / f64 (LLR, BP)",
+        "data": "synthetic (ft8_demodulator_amd.synth: 50 GFSK signals/slot, SNR U(-24,-10) dB, unit noise; "
+                "per-slot seeds 100000 + global slot)",
+        "config": {"workload": "BASELINE config 3: batch of 256 independent 15-s slots per GPU, 12 kHz, "
+                               "K=300 candidates, min_score=2, 20 BP iterations (config 5 shape at N>1)",
+                   "slots_per_gpu": S, "sample_rate": 12000, "samples_per_slot": int(x.shape[1]),
+                   "max_candidates": 300, "min_score": 2, "max_iterations": 20,
+                   "pipeline_depth": D,
+                   "parallelism": f"slot-sharded x{world}" + (
+                       (", one all-gather per step of the device-packed decodes over "
+                        + ("gloo (--share-gpu rehearsal, every rank on cuda:0)" if args.share_gpu else "RCCL")
+                        + (" (world size 1, --gather)" if world == 1 else ""))
+                       if exchange else "")},
+        "decodes_per_step": decoded,  # successful decodes in one step's batch (every step decodes the same batch)
+        "full": full,
+        "step_times": step_times,
+        "depth": {"contexts": D, "streams": D if D > 1 else 1, "one_chain": depth1},
+        "settle": settle,
+        "settle_steps": settle["steps"],
+        "build_id": build_id,
+    }
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if gather is not None:
+        line["gather"] = gather
+
+    def emit():
+        if rank == 0:
+            # the whole record goes to the side file; stdout gets ONE compact line (<= LINE_MAX bytes, strict JSON)
+            legs_path = write_legs(line, args.legs_out)
+            print(compact_line(line, legs_path), flush=True)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+
+    if not full:
+        # the candidates of one step's k_bp launch (the metric's LDPC rate): one more step, its work counters
+        ctx.counters(reset=True)
+        dec.run(x)
+        torch.cuda.synchronize()
+        line["ldpc_candidates_per_s"] = ctx.counters(reset=True)["candidates"] * world / (elapsed / K)
+        emit()
+        return
+
+    # per-kernel durations inside the real step sequence: one pass of `stage_steps` steps per stage,
+    # with HIP events bracketing only that stage's kernel (the rest of the step runs undisturbed);
+    # the BP work counters of the k_bp pass give its algorithmic FLOPs per launch
+    R = max(1, args.stage_steps)
+    stage_ms = {}
+    for st in STAGE_ORDER:
+        ctx.timing(reset=True)
+        if st == "bp":
+            ctx.counters(reset=True)
+            ctx.bp_clock(reset=True)
+        ctx.set_timing(True, stages=[st])
+        for _ in range(R):
+            step(0)   # the first decoder (this context), one chain
+        torch.cuda.synchronize()
+        ctx.set_timing(False)
+        tm = ctx.timing(reset=True)[st]
+        stage_ms[st] = tm[0] / max(tm[1], 1)
+        if st == "bp":
+            cn = ctx.counters(reset=True)
+            bclk = ctx.bp_clock(reset=True)
+    ctx.set_timing(False, stages=None)
+    # the STFT is the first kernel of a step, so an event placed before it also times the host's
+    # launch gap; its launch duration comes from back-to-back re-launches of the step's STFT instead
+    # (ft8_replay_stage), events only around the whole run
+    stft_reps = 20
+    ctx.replay("stft", 2)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    ctx.replay("stft", stft_reps)
+    e1.record()
+    torch.cuda.synchronize()
+    stft_replay_ms = e0.elapsed_time(e1) / stft_reps
     bp_ms = stage_ms["bp"]
     stft_ms = stft_replay_ms
     # dominant kernel: k_bp.  Algorithmic FLOPs per launch from the device counters.
@@ -1534,11 +1674,6 @@ def main():
                     "note": "mean_wave_cycles ~ k_bp's cycles per launch (persistent waves live for the launch); "
                             "effective_ghz = summed wave cycles / summed wave wall time; wave_busy_vs_event = mean "
                             "wave lifetime / event-timed launch"}
-    q1 = max(1, K // 4)
-    step_times = {"ms": [round(v_, 4) for v_ in step_ms],
-                  "first_quarter_mean_ms": sum(step_ms[:q1]) / q1, "last_quarter_mean_ms": sum(step_ms[-q1:]) / q1,
-                  "from": "HIP events between consecutive timed steps (GPU periods; the line's ms_per_step is the "
-                          "host wall clock around all of them)"}
 
     stress = None
     if world == 1 and not args.no_bp_stress:
@@ -1568,7 +1703,6 @@ def main():
     gather_n1 = None
     if world == 1 and not args.gather and not args.no_gather_leg:
         gather_n1 = gather_leg(dec, x, dev, S, args.steps)
-    build_id = _lib.lib().ft8_build_id().decode()
     traffic, tsrc = counters_for_build("r*_pmc_traffic.json", build_id)
     qdata, qsrc = counters_for_build("r*_v*_pmc.json", build_id)
     issue = None
@@ -1590,33 +1724,8 @@ def main():
                 return v.get("hbm_bytes")
         return None
 
-    line = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "slots/s",
-        "n_gpus": world,
-        **({"rehearsal": "--share-gpu: every rank on cuda:0 over gloo; not a measurement"} if args.share_gpu else {}),
-        "steps": K,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / K * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32 (STFT, sync score) / f64 (LLR, BP)",
-        "data": "synthetic (ft8_demodulator_amd.synth: 50 GFSK signals/slot, SNR U(-24,-10) dB, unit noise; "
-                "per-slot seeds 100000 + global slot)",
-        "config": {"workload": "BASELINE config 3: batch of 256 independent 15-s slots per GPU, 12 kHz, "
-                               "K=300 candidates, min_score=2, 20 BP iterations (config 5 shape at N>1)",
-                   "slots_per_gpu": S, "sample_rate": 12000, "samples_per_slot": int(x.shape[1]),
-                   "max_candidates": 300, "min_score": 2, "max_iterations": 20,
-                   "pipeline_depth": D,
-                   "parallelism": f"slot-sharded x{world}" + (
-                       (", one all-gather per step of the device-packed decodes over "
-                        + ("gloo (--share-gpu rehearsal, every rank on cuda:0)" if args.share_gpu else "RCCL")
-                        + (" (world size 1, --gather)" if world == 1 else ""))
-                       if exchange else "")},
+    line.update({
         "ldpc_candidates_per_s": cand_per_s,
-        "decodes_per_step": decoded,  # successful decodes in one step's batch (every step decodes the same batch)
         "roofline": {"kernel": "k_bp (float64 BP + CRC)", "bound": "fp64-valu",
                      "achieved": ach_tf, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
                      "frac": ach_tf / FP64_VECTOR_PEAK_TFLOPS, "traffic": hbm("ft8::k_bp"), "traffic_source": tsrc,
@@ -1624,9 +1733,6 @@ def main():
                      "launch_ms_from": f"HIP events around k_bp alone in {R} full steps after the timed loop",
                      "bp_passes_per_launch": cn["passes"] / R, "candidates_per_launch": cn["candidates"] / R,
                      "clock": bp_clock, "issue": issue},
-        "step_times": step_times,
-        "depth": {"contexts": D, "streams": D if D > 1 else 1, "one_chain": depth1},
-        "settle": settle,
         "step_hbm": {"what": "BASELINE.md whole-step accounting: slots/s per GPU x B_slot algorithmic bytes "
                              "(the step is FP64-VALU bound in k_bp, so this fraction is low by construction)",
                      "bytes_per_slot": b_slot, "achieved": step_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1649,21 +1755,12 @@ def main():
         "cpu_baseline": cpu,
         "parity": parity,
         "reference_measured": REFERENCE_MEASURED,
-        "build_id": build_id,
         # the shader clock of this box, measured after the timed work (boxes differ by up to ~15 %)
         "gpu_clock_ghz": gpu_clock_ghz(local),
-    }
-    if gather is not None:
-        line["gather"] = gather
+    })
     if gather_n1 is not None:
         line["gather_n1"] = gather_n1
-    line["settle_steps"] = settle["steps"]
-    if rank == 0:
-        # every leg goes to the side file; stdout gets ONE compact line (<= LINE_MAX bytes, strict JSON)
-        legs_path = write_legs(line, args.legs_out)
-        print(compact_line(line, legs_path), flush=True)
-    if dist.is_initialized():
-        dist.destroy_process_group()
+    emit()
 
 
 if __name__ == "__main__":

@@ -179,6 +179,81 @@ def test_compact_line_n8(bench):
     assert d["gather"]["world"] == 8 and d["settle_steps"] == 96
 
 
+def test_compact_line_of_a_plain_run(bench):
+    """A plain run's record (no --full: no roofline, CPU baseline, parity or legs) still gives the
+    strict line with the contract fields; what was not measured is null."""
+    full = _fixture("bench_full_n1_r5.json")
+    for k in ("roofline", "roofline_hbm", "cpu_baseline", "parity", "bp_stress", "subtract_redecode", "h2d_stream",
+              "drift_correct", "gather_n1", "gpu_clock_ghz", "stages_ms"):
+        full.pop(k, None)
+    full["depth"]["one_chain"] = None
+    full["full"] = False
+    s = bench.compact_line(full, "legs.json")
+    assert len(s.encode()) <= 4096 and "\n" not in s
+    d = json.loads(s, parse_constant=lambda c: (_ for _ in ()).throw(ValueError(c)))
+    assert d["full"] is False and d["cpu_baseline"] is None and d["parity"] is None
+    assert d["roofline"].get("launch_ms") is None and d["depth"]["one_chain_value"] is None
+    assert d["n_gpus"] == 1 and d["steps"] == full["steps"] and d["legs"] == "legs.json"
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert d[k] == full[k]
+    assert d["value"] == pytest.approx(full["value"], rel=1e-5)
+    assert d["ms_per_step"] == pytest.approx(full["ms_per_step"], rel=1e-5)
+
+
+def _fake_step_output(S, cap, counts, seed=0):
+    import torch
+    from ft8_demodulator_amd._lib import RESULT_DTYPE
+    rng = np.random.default_rng(seed)
+    recs = np.zeros((S, cap), RESULT_DTYPE)
+    recs["score"] = rng.standard_normal((S, cap)) + 5.0       # rows past a slot's count hold garbage too
+    recs["abs_time"] = rng.integers(1, 1000, (S, cap))
+    recs["payload"] = rng.integers(1, 255, (S, cap, 10))
+    recs["ok"] = 1
+    out = torch.from_numpy(recs.view(np.uint8).reshape(-1).copy())
+    return recs, out, torch.tensor(counts, dtype=torch.int32)
+
+
+def test_dump_outputs_writes_the_step_records(bench, tmp_path):
+    """--dump-outputs: counts and every ft8_result field as float64 .npy, rows past a slot's count
+    (capped at the record capacity) zeroed, the same bytes when written twice."""
+    from ft8_demodulator_amd._lib import RESULT_DTYPE
+    S, cap = 5, 7
+    counts = [0, 3, 7, 9, 1]
+    recs, out, cnt = _fake_step_output(S, cap, counts)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), out, cnt, cap)
+    assert set(shapes) == set(RESULT_DTYPE.names) | {"counts", "kept_slots"}
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in shapes}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["counts"].tolist() == counts and got["kept_slots"].tolist() == list(range(S))
+    assert got["payload"].shape == (S, cap, 10) and got["score"].shape == (S, cap)
+    kept = np.minimum(counts, cap)
+    for s in range(S):
+        assert np.array_equal(got["score"][s, :kept[s]], recs["score"][s, :kept[s]])
+        assert np.array_equal(got["payload"][s, :kept[s]], recs["payload"][s, :kept[s]])
+        assert not got["score"][s, kept[s]:].any() and not got["payload"][s, kept[s]:].any()
+        assert not got["ok"][s, kept[s]:].any() and got["ok"][s, :kept[s]].all()
+    bench.dump_outputs(str(tmp_path / "b"), out, cnt, cap)
+    for n in shapes:
+        assert (tmp_path / "a" / (n + ".npy")).read_bytes() == (tmp_path / "b" / (n + ".npy")).read_bytes()
+
+
+def test_dump_outputs_samples_a_large_output(bench, tmp_path, monkeypatch):
+    """Over the size budget the dump keeps a fixed, seeded sample of the slots (every slot's count
+    still written) and stays under the budget."""
+    S, cap = 40, 16
+    recs, out, cnt = _fake_step_output(S, cap, [cap] * S, seed=1)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 40000)
+    a = bench.dump_outputs(str(tmp_path / "a"), out, cnt, cap)
+    b = bench.dump_outputs(str(tmp_path / "b"), out, cnt, cap)
+    assert a == b
+    keep = np.load(tmp_path / "a" / "kept_slots.npy").astype(int)
+    assert 0 < len(keep) < S and np.array_equal(keep, np.load(tmp_path / "b" / "kept_slots.npy"))
+    assert np.all(np.diff(keep) > 0)
+    assert np.load(tmp_path / "a" / "counts.npy").shape == (S,)
+    assert np.array_equal(np.load(tmp_path / "a" / "score.npy"), recs["score"][keep])
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 40000
+
+
 def test_write_legs_strict(bench, tmp_path):
     full = {"a": float("inf"), "b": [1.0, float("nan")], "c": np.float32(2.5), "d": np.int64(3)}
     p = bench.write_legs(full, str(tmp_path / "legs" / "x.json"))

@@ -4,7 +4,7 @@
 set -o pipefail
 T=${1:-r2}
 shift
-EXTRA="$*"   # extra bench.py flags (e.g. --depth 1 --no-single-call)
+EXTRA="--full $*"   # --full: the stage times, k_bp replays and one-chain loop trace_steps.py reconciles; then extra bench.py flags (e.g. --depth 1 --no-single-call)
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp &&
