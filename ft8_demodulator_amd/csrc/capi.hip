@@ -2,10 +2,13 @@
 //
 // See include/ft8hip.h for the contract.  Everything below runs on the host; all numerical work is
 // in the kernels of stft.hip / sync.hip / bp.hip.  No path here computes a decode on the CPU.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstring>
+#include <map>
+#include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "ft8_internal.h"
@@ -21,9 +24,29 @@ using namespace ft8;
 
 namespace {
 
+// a device allocation and its owner: move-only, freed with its holder (a context's are freed under
+// the context's DeviceGuard, ft8_destroy)
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) {
+    o.p = nullptr;
+    o.cap = 0;
+  }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  template <typename T>
+  T* as() const { return static_cast<T*>(p); }
 };
 
 struct PlanEntry {
@@ -31,19 +54,23 @@ struct PlanEntry {
   bool cplx;   // complex-input path (P = nfft) vs real-input half-length path (P = nfft/2)
   bool f64;
   int L = 0;   // nperseg (chirp-z plans are built for one)
-  FftPlan plan;
-  void* tw = nullptr;
-  void* post = nullptr;
-  void* chirp = nullptr;
-  void* hspec = nullptr;
+  FftPlan plan;  // its table pointers are views into the buffers below
+  DevBuf tw, post, chirp, hspec;
 };
 
 struct WinEntry {
   int L;
   bool f64;
-  void* w = nullptr;
+  DevBuf w;
   double scale;
 };
+
+// per-stage timing slots (ft8_get_timing, ft8_replay_stage), in the order of the binding's STAGE_NAMES
+enum Stage {
+  kStft, kScore, kSelect, kBp, kCompact, kDecodeBatch, kLlr, kSubEst, kDriftStftArgmax, kDriftFit, kDriftDerotate,
+  kSubApply, kNStages
+};
+static_assert(kNStages == FT8_N_STAGES, "the stage ids are the public timing slots");
 
 struct TimedLaunch {
   int stage;
@@ -51,6 +78,36 @@ struct TimedLaunch {
 };
 
 }  // namespace
+
+// ---- LDS opt-in (ft8_internal.h) -----------------------------------------------------------------
+namespace ft8 {
+hipError_t lds_opt_in(const void* kernel, size_t dyn_bytes) {
+  constexpr size_t kDefaultLds = 64 * 1024;
+  struct KernelLds {
+    size_t static_lds = 0;          // a property of the code object (one architecture): queried once
+    std::map<int, size_t> granted;  // device -> dynamic bytes granted there
+  };
+  static std::mutex mu;
+  static std::map<const void*, KernelLds> kernels;
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = kernels.find(kernel);
+  if (it == kernels.end()) {
+    hipFuncAttributes fa{};
+    const bool ok = hipFuncGetAttributes(&fa, kernel) == hipSuccess;
+    if (!ok) (void)hipGetLastError();
+    it = kernels.emplace(kernel, KernelLds{ok ? fa.sharedSizeBytes : 0, {}}).first;
+  }
+  if (it->second.static_lds + dyn_bytes <= kDefaultLds) return hipSuccess;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  size_t& granted = it->second.granted[dev];
+  if (dyn_bytes <= granted) return hipSuccess;
+  e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_bytes);
+  if (e == hipSuccess) granted = dyn_bytes;
+  return e;
+}
+}  // namespace ft8
 
 struct ft8_ctx {
   int device = 0;
@@ -123,7 +180,21 @@ struct DeviceGuard {
   }
 };
 
-int ensure(ft8_ctx* c, DevBuf& b, size_t bytes);
+// grow-only scratch: at least `bytes` (a quarter more when it has to grow), old contents dropped
+int ensure(ft8_ctx* c, DevBuf& b, size_t bytes) {
+  if (bytes == 0) bytes = 16;
+  if (b.cap >= bytes) return FT8_OK;
+  b.release();
+  size_t want = bytes + bytes / 4;
+  hipError_t e = hipMalloc(&b.p, want);
+  if (e != hipSuccess) {
+    b.p = nullptr;
+    (void)hipGetLastError();
+    return fail(c, FT8_E_NOMEM, std::string("hipMalloc failed for ") + std::to_string(want) + " bytes");
+  }
+  b.cap = want;
+  return FT8_OK;
+}
 
 // ensure() for a buffer that must read as zeros when (re)allocated: the k_bp work counters, which
 // every k_bp launch leaves at 0 again (bp.hip), so they are cleared only here
@@ -150,24 +221,6 @@ int ensure_work(ft8_ctx* c, int n_counters, hipStream_t s) {
   return FT8_OK;
 }
 
-int ensure(ft8_ctx* c, DevBuf& b, size_t bytes) {
-  if (bytes == 0) bytes = 16;
-  if (b.cap >= bytes) return FT8_OK;
-  if (b.p) {
-    (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-  }
-  size_t want = bytes + bytes / 4;
-  hipError_t e = hipMalloc(&b.p, want);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(c, FT8_E_NOMEM, std::string("hipMalloc failed for ") + std::to_string(want) + " bytes");
-  }
-  b.cap = want;
-  return FT8_OK;
-}
-
 hipEvent_t get_event(ft8_ctx* c) {
   if (!c->pool.empty()) {
     hipEvent_t e = c->pool.back();
@@ -181,10 +234,10 @@ hipEvent_t get_event(ft8_ctx* c) {
 
 struct StageTimer {
   ft8_ctx* c;
-  int stage;
+  Stage stage;
   hipStream_t s;
   hipEvent_t a = nullptr;
-  StageTimer(ft8_ctx* c_, int st, hipStream_t s_) : c(c_), stage(st), s(s_) {
+  StageTimer(ft8_ctx* c_, Stage st, hipStream_t s_) : c(c_), stage(st), s(s_) {
     if (c->timing && ((c->stage_mask >> st) & 1u)) {
       a = get_event(c);
       (void)hipEventRecord(a, s);
@@ -199,6 +252,16 @@ struct StageTimer {
     }
   }
 };
+
+// one timed launch: `launch()` enqueues on s and returns its hipError_t; a failure is the context's
+// error "<what>: <hip error>"
+template <typename F>
+int timed_launch(ft8_ctx* c, Stage stage, hipStream_t s, const char* what, F&& launch) {
+  StageTimer t(c, stage, s);
+  const hipError_t e = launch();
+  t.done();
+  return e == hipSuccess ? FT8_OK : hipfail(c, e, what);
+}
 
 // Stream order of a context's work.  The scratch buffers, the k_bp claim counters and their
 // host-side ticket bases assume that a context's launches run one after another; an entry point
@@ -287,6 +350,37 @@ std::vector<double> hann(int L) {
   return w;
 }
 
+// n host values of T in a fresh device buffer of exactly that size
+template <typename T>
+hipError_t upload(DevBuf& b, const std::vector<T>& host) {
+  b.release();
+  const size_t bytes = sizeof(T) * host.size();
+  hipError_t e = hipMalloc(&b.p, bytes);
+  if (e != hipSuccess) {
+    b.p = nullptr;
+    return e;
+  }
+  b.cap = bytes;
+  return hipMemcpy(b.p, host.data(), bytes, hipMemcpyHostToDevice);
+}
+
+// a complex table of n entries, gen(i, &re, &im) in long double, rounded to the plan's type
+// (cplx<double> or cplx<float>)
+template <typename Gen>
+hipError_t upload_table(DevBuf& b, bool f64, size_t n, Gen&& gen) {
+  auto build = [&](auto zero) {
+    using CT = decltype(zero);
+    std::vector<cplx<CT>> host(n);
+    for (size_t i = 0; i < n; ++i) {
+      long double re, im;
+      gen(i, &re, &im);
+      host[i] = {(CT)re, (CT)im};
+    }
+    return upload(b, host);
+  };
+  return f64 ? build(0.0) : build(0.0f);
+}
+
 int get_window(ft8_ctx* c, int L, bool f64, WinEntry** out) {
   for (auto& w : c->wins)
     if (w.L == L && w.f64 == f64) { *out = &w; return FT8_OK; }
@@ -298,19 +392,17 @@ int get_window(ft8_ctx* c, int L, bool f64, WinEntry** out) {
   if (f64) {
     double s = 0.0 + double_pairwise(w.data(), L);
     e.scale = 1.0 / (s * s);
-    he = hipMalloc(&e.w, sizeof(double) * L);
-    if (he == hipSuccess) he = hipMemcpy(e.w, w.data(), sizeof(double) * L, hipMemcpyHostToDevice);
+    he = upload(e.w, w);
   } else {
     std::vector<float> w32(L);
     for (int i = 0; i < L; ++i) w32[i] = (float)w[i];
     float s = 0.0f + cfloat_pairwise_re(w32.data(), 2L * L);
     float sq = s * s;
     e.scale = (double)(1.0f / sq);
-    he = hipMalloc(&e.w, sizeof(float) * L);
-    if (he == hipSuccess) he = hipMemcpy(e.w, w32.data(), sizeof(float) * L, hipMemcpyHostToDevice);
+    he = upload(e.w, w32);
   }
   if (he != hipSuccess) return hipfail(c, he, "window upload");
-  c->wins.push_back(e);
+  c->wins.push_back(std::move(e));
   *out = &c->wins.back();
   return FT8_OK;
 }
@@ -377,18 +469,7 @@ void chirp_of(int64_t j, int N, long double* cr, long double* ci) {
 int blue_tables(ft8_ctx* c, PlanEntry& e, int nfft, int L, int P, bool f64) {
   const int B = P - L + 1;
   const int nblk = (nfft + B - 1) / B;
-  const size_t esz = f64 ? 16 : 8;
-  std::vector<unsigned char> ch(esz * nfft), hs(esz * (size_t)nblk * P);
-  auto put = [&](std::vector<unsigned char>& v, size_t i, long double xr, long double xi) {
-    if (f64) { double t[2] = {(double)xr, (double)xi}; memcpy(&v[esz * i], t, 16); }
-    else { float t[2] = {(float)xr, (float)xi}; memcpy(&v[esz * i], t, 8); }
-  };
-  for (int k = 0; k < nfft; ++k) {
-    long double cr, ci;
-    chirp_of(k, nfft, &cr, &ci);
-    put(ch, k, cr, ci);
-  }
-  std::vector<long double> re(P), im(P);
+  std::vector<long double> hre((size_t)nblk * P), him((size_t)nblk * P), re(P), im(P);
   for (int b = 0; b < nblk; ++b) {
     for (int m = 0; m < P; ++m) {
       long double cr, ci;
@@ -397,18 +478,24 @@ int blue_tables(ft8_ctx* c, PlanEntry& e, int nfft, int L, int P, bool f64) {
       im[m] = -ci;
     }
     host_fft_pow2(re, im);
-    for (int m = 0; m < P; ++m) put(hs, (size_t)b * P + m, re[m], im[m]);
+    std::copy(re.begin(), re.end(), hre.begin() + (size_t)b * P);
+    std::copy(im.begin(), im.end(), him.begin() + (size_t)b * P);
   }
-  hipError_t he = hipMalloc(&e.chirp, ch.size());
-  if (he == hipSuccess) he = hipMalloc(&e.hspec, hs.size());
-  if (he == hipSuccess) he = hipMemcpy(e.chirp, ch.data(), ch.size(), hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(e.hspec, hs.data(), hs.size(), hipMemcpyHostToDevice);
+  // both straight from long double to the plan's type
+  hipError_t he = upload_table(e.chirp, f64, nfft, [&](size_t k, long double* cr, long double* ci) {
+    chirp_of((int64_t)k, nfft, cr, ci);
+  });
+  if (he == hipSuccess)
+    he = upload_table(e.hspec, f64, hre.size(), [&](size_t i, long double* xr, long double* xi) {
+      *xr = hre[i];
+      *xi = him[i];
+    });
   if (he != hipSuccess) return hipfail(c, he, "chirp-z plan upload");
   e.plan.L = L;
   e.plan.B = B;
   e.plan.nblk = nblk;
-  e.plan.chirp = e.chirp;
-  e.plan.hspec = e.hspec;
+  e.plan.chirp = e.chirp.p;
+  e.plan.hspec = e.hspec.p;
   return FT8_OK;
 }
 
@@ -457,30 +544,25 @@ int get_plan(ft8_ctx* c, int nfft, bool cplx, bool f64, int nperseg, FftPlan* ou
     }
   }
   e.plan.P = P;
-  // twiddles W_P^m and post-processing W_N^k (N = 2P), from long double angles
-  const size_t esz = f64 ? 16 : 8;
-  std::vector<unsigned char> tw(esz * P), post(esz * (P + 1));
-  for (int m = 0; m < P; ++m) {
-    const long double ang = -2.0L * M_PIl * (long double)m / (long double)P;
-    const double cr = (double)cosl(ang), ci = (double)sinl(ang);
-    if (f64) { double v[2] = {cr, ci}; memcpy(&tw[esz * m], v, 16); }
-    else { float v[2] = {(float)cr, (float)ci}; memcpy(&tw[esz * m], v, 8); }
-  }
-  for (int k = 0; k <= P; ++k) {
-    const long double ang = -2.0L * M_PIl * (long double)k / (long double)(2 * P);
-    const double cr = (double)cosl(ang), ci = (double)sinl(ang);
-    if (f64) { double v[2] = {cr, ci}; memcpy(&post[esz * k], v, 16); }
-    else { float v[2] = {(float)cr, (float)ci}; memcpy(&post[esz * k], v, 8); }
-  }
-  hipError_t he = hipMalloc(&e.tw, tw.size());
-  if (he == hipSuccess) he = hipMalloc(&e.post, post.size());
-  if (he == hipSuccess) he = hipMemcpy(e.tw, tw.data(), tw.size(), hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(e.post, post.data(), post.size(), hipMemcpyHostToDevice);
+  // twiddles W_P^m and post-processing W_N^k (N = 2P), from long double angles, rounded to double
+  // and from there to the plan's type
+  auto root_of_unity = [](size_t k, int n, long double* cr, long double* ci) {
+    const long double ang = -2.0L * M_PIl * (long double)k / (long double)n;
+    *cr = (double)cosl(ang);
+    *ci = (double)sinl(ang);
+  };
+  hipError_t he = upload_table(e.tw, f64, P, [&](size_t m, long double* cr, long double* ci) {
+    root_of_unity(m, P, cr, ci);
+  });
+  if (he == hipSuccess)
+    he = upload_table(e.post, f64, (size_t)P + 1, [&](size_t k, long double* cr, long double* ci) {
+      root_of_unity(k, 2 * P, cr, ci);
+    });
   if (he != hipSuccess) return hipfail(c, he, "fft plan upload");
-  e.plan.tw = e.tw;
-  e.plan.post = e.post;
-  c->plans.push_back(e);
+  e.plan.tw = e.tw.p;
+  e.plan.post = e.post.p;
   *out = e.plan;
+  c->plans.push_back(std::move(e));
   return FT8_OK;
 }
 
@@ -509,48 +591,67 @@ int geometry(double fs, int bpt, int sps, int64_t n, Geo* g, std::string* why) {
 bool is_f64_dtype(int dt) { return dt == FT8_F64 || dt == FT8_C128; }
 bool is_cplx_dtype(int dt) { return dt == FT8_C64 || dt == FT8_C128; }
 
-int do_stft(ft8_ctx* c, const void* samples, int dtype, int64_t n_samples, int n_slots, int64_t slot_stride,
-            const ft8_params* p, void* d_wf, hipStream_t s) {
+// what an StftLaunch is built for: dB rows (an empty bin range is an empty result), the per-frame
+// argmax (an empty bin range has none: an error), or only the choice of kernel (ft8_stft_method: no
+// ranges, no window)
+enum class StftUse { Rows, Argmax, Method };
+
+// The one place that validates an STFT request and fills its launch block: geometry, dtype, frame
+// and bin ranges, plan, the direct DFT's LDS limit, window.  *launch = false: valid, nothing to
+// compute.  samples / out / argmax / screen_* stay with the caller.
+int make_stft_launch(ft8_ctx* c, const ft8_params* p, int dtype, int64_t n_samples, int n_slots, int64_t stride,
+                     StftUse use, StftLaunch* L, bool* launch) {
   Geo g;
   std::string why;
   int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
   if (rc) return fail(c, rc, why);
   if (dtype < FT8_F32 || dtype > FT8_I16) return fail(c, FT8_E_ARG, "unknown sample dtype");
-  if (p->t_lo < 0 || p->t_hi > g.frames || p->t_lo > p->t_hi)
-    return fail(c, FT8_E_ARG, "frame range [t_lo, t_hi) outside [0, " + std::to_string(g.frames) + ")");
-  if (p->f_lo < 0 || p->f_hi > g.nfft || p->f_lo > p->f_hi)
-    return fail(c, FT8_E_ARG, "bin range [f_lo, f_hi) outside [0, nfft)");
-  if (p->t_hi == p->t_lo || p->f_hi == p->f_lo || n_slots == 0) return FT8_OK;
-  const bool f64 = is_f64_dtype(dtype), cplx = is_cplx_dtype(dtype);
-  StftLaunch L{};
-  rc = get_plan(c, g.nfft, cplx, f64, g.nperseg, &L.plan);
-  if (rc) return rc;
-  if (L.plan.dft && (size_t)g.nperseg * (f64 ? 16 : 8) > (size_t)kMaxDftLds)
+  *launch = false;
+  if (use != StftUse::Method) {
+    if (p->t_lo < 0 || p->t_hi > g.frames || p->t_lo > p->t_hi)
+      return fail(c, FT8_E_ARG, "frame range [t_lo, t_hi) outside [0, " + std::to_string(g.frames) + ")");
+    if (use == StftUse::Argmax) {
+      if (p->f_lo < 0 || p->f_hi > g.nfft || p->f_lo >= p->f_hi) return fail(c, FT8_E_ARG, "bin range [f_lo, f_hi) empty or outside [0, nfft)");
+    } else if (p->f_lo < 0 || p->f_hi > g.nfft || p->f_lo > p->f_hi) {
+      return fail(c, FT8_E_ARG, "bin range [f_lo, f_hi) outside [0, nfft)");
+    }
+    if (p->t_hi == p->t_lo || p->f_hi == p->f_lo || n_slots == 0) return FT8_OK;
+  }
+  const bool f64 = is_f64_dtype(dtype);
+  *L = StftLaunch{};
+  L->dtype = dtype;
+  L->n_samples = n_samples;
+  L->slot_stride = stride;
+  L->n_slots = n_slots;
+  L->nperseg = g.nperseg;
+  L->hop = g.hop;
+  L->nfft = g.nfft;
+  L->t_lo = p->t_lo;
+  L->t_hi = p->t_hi;
+  L->f_lo = p->f_lo;
+  L->f_hi = p->f_hi;
+  if ((rc = get_plan(c, g.nfft, is_cplx_dtype(dtype), f64, g.nperseg, &L->plan))) return rc;
+  *launch = true;
+  if (use == StftUse::Method) return FT8_OK;
+  if (L->plan.dft && (size_t)g.nperseg * (f64 ? 16 : 8) > (size_t)kMaxDftLds)
     return fail(c, FT8_E_RANGE, "nperseg " + std::to_string(g.nperseg) + " exceeds the direct-DFT limit");
   WinEntry* w = nullptr;
-  rc = get_window(c, g.nperseg, f64, &w);
-  if (rc) return rc;
+  if ((rc = get_window(c, g.nperseg, f64, &w))) return rc;
+  L->window = w->w.p;
+  L->scale = w->scale;
+  return FT8_OK;
+}
+
+int do_stft(ft8_ctx* c, const void* samples, int dtype, int64_t n_samples, int n_slots, int64_t slot_stride,
+            const ft8_params* p, void* d_wf, hipStream_t s) {
+  StftLaunch L;
+  bool launch;
+  int rc = make_stft_launch(c, p, dtype, n_samples, n_slots, slot_stride, StftUse::Rows, &L, &launch);
+  if (rc || !launch) return rc;
   L.samples = samples;
-  L.dtype = dtype;
-  L.n_samples = n_samples;
-  L.slot_stride = slot_stride;
-  L.n_slots = n_slots;
-  L.nperseg = g.nperseg;
-  L.hop = g.hop;
-  L.nfft = g.nfft;
-  L.t_lo = p->t_lo;
-  L.t_hi = p->t_hi;
-  L.f_lo = p->f_lo;
-  L.f_hi = p->f_hi;
-  L.window = w->w;
-  L.scale = w->scale;
   L.out = d_wf;
   c->last_stft = L;
-  StageTimer tm(c, 0, s);
-  hipError_t e = launch_stft(L, s);
-  tm.done();
-  if (e != hipSuccess) return hipfail(c, e, "stft launch");
-  return FT8_OK;
+  return timed_launch(c, kStft, s, "stft launch", [&] { return launch_stft(L, s); });
 }
 
 struct Grid {
@@ -571,6 +672,49 @@ Grid grid_of(int T, int F, int sps, int bpt) {
 size_t score_elems(const Grid& g) { return (size_t)g.NT * n_segments(g.NF) * kSegCols; }
 size_t smask_words(const Grid& g) { return (size_t)g.NT * n_segments(g.NF) * 2; }
 
+// the score/select scratch of a run of slots: scores [n][score_elems] in the waterfall's type, smask
+// [n][smask_words], warn [n], rowsum [n][NT][nseg], tie [n][tie_stride(N)] (float32 scores only)
+struct SelScratch {
+  void* scores;
+  uint64_t* smask;
+  int32_t* warn;
+  RowSummary* rowsum;
+  int32_t* tie;
+};
+
+// sizes the context's score/select scratch for n_slots slots (own_scores = false: the caller brings
+// the score grid)
+int ensure_sel_scratch(ft8_ctx* c, int n_slots, const Grid& g, int N, bool f64, bool own_scores = true) {
+  const size_t n = (size_t)n_slots;
+  int rc;
+  if (own_scores && (rc = ensure(c, c->scores, (f64 ? 8 : 4) * n * score_elems(g)))) return rc;
+  if ((rc = ensure(c, c->smask, sizeof(uint64_t) * n * smask_words(g)))) return rc;
+  if ((rc = ensure(c, c->warn, sizeof(int32_t) * n))) return rc;
+  if ((rc = ensure(c, c->rowsum, sizeof(RowSummary) * n * g.NT * n_segments(g.NF)))) return rc;
+  if (!f64 && (rc = ensure(c, c->tie, sizeof(int32_t) * n * tie_stride(N)))) return rc;
+  return FT8_OK;
+}
+
+// the part of that scratch that starts at slot `slot0`
+SelScratch sel_scratch_at(const ft8_ctx* c, int slot0, const Grid& g, int N, bool f64) {
+  const size_t k = (size_t)slot0;
+  return {c->scores.as<char>() + (f64 ? 8 : 4) * k * score_elems(g), c->smask.as<uint64_t>() + k * smask_words(g),
+          c->warn.as<int32_t>() + k, c->rowsum.as<RowSummary>() + k * g.NT * n_segments(g.NF),
+          f64 ? nullptr : c->tie.as<int32_t>() + k * tie_stride(N)};
+}
+
+// the search parameters ft8_sync_select and ft8_decode_batch share.  The two entry points have
+// always reported a call that breaks two rules differently: ft8_decode_batch names the candidate
+// limit first, ft8_sync_select the flags (limit_first).
+int check_search_params(ft8_ctx* c, const ft8_params* p, bool limit_first) {
+  if (p->steps_per_symbol <= 0 || p->bins_per_tone <= 0) return fail(c, FT8_E_ARG, "bad oversampling factors");
+  const bool over = p->max_candidates > kMaxCandidates;
+  if ((p->flags & ~(FT8_FLAG_TOPK | FT8_FLAG_SUBTRACT)) && !(limit_first && over))
+    return fail(c, FT8_E_ARG, "unknown bits in ft8_params.flags");
+  if (over) return fail(c, FT8_E_RANGE, "max_candidates > " + std::to_string(kMaxCandidates) + " is not supported");
+  return FT8_OK;
+}
+
 int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
                 int64_t slot_stride, const ft8_params* p, ft8_result* d_out, int32_t* d_counts, int32_t cap,
                 hipStream_t s);
@@ -578,59 +722,18 @@ int subtract_core(ft8_ctx* c, const void* x, int dtype, float* resid, int64_t n_
                   int64_t x_stride, int64_t r_stride, const ft8_params* p, const ft8_result* res,
                   const int32_t* counts, int cap, hipStream_t s);
 int gfsk_tables(ft8_ctx* c, int nsps);
-int sync_select_core(ft8_ctx* c, const void* d_wf, int wf_f64, int n_slots, int T, int F, const ft8_params* p,
-                     int32_t* cand, double* cand_score, int32_t* cand_count, void* scores, uint64_t* smask,
-                     int compact, int32_t* warn, RowSummary* rowsum, hipStream_t s, int32_t* tie = nullptr);
 
-int do_sync_select(ft8_ctx* c, const void* d_wf, int wf_f64, int n_slots, int T, int F, const ft8_params* p,
-                   int32_t* cand, double* cand_score, int32_t* cand_count, void* d_scores, hipStream_t s) {
-  if (p->steps_per_symbol <= 0 || p->bins_per_tone <= 0) return fail(c, FT8_E_ARG, "bad oversampling factors");
-  if (p->flags & ~(FT8_FLAG_TOPK | FT8_FLAG_SUBTRACT)) return fail(c, FT8_E_ARG, "unknown bits in ft8_params.flags");
-  const int N = p->max_candidates;
-  if (N > kMaxCandidates)
-    return fail(c, FT8_E_RANGE, "max_candidates > " + std::to_string(kMaxCandidates) + " is not supported");
-  Grid g = grid_of(T, F, p->steps_per_symbol, p->bins_per_tone);
-  if (N <= 0 || g.NT == 0 || g.NF == 0 || n_slots == 0) {
-    hipError_t e = hipMemsetAsync(cand_count, 0, sizeof(int32_t) * (size_t)(n_slots > 0 ? n_slots : 0), s);
-    return e == hipSuccess ? FT8_OK : hipfail(c, e, "memset");
-  }
-  const size_t esz = wf_f64 ? 8 : 4;
-  int rc;
-  // without a caller grid the scores stay in the compact layout (only passing scores written)
-  void* scores = d_scores;
-  if (!scores) {
-    if ((rc = ensure(c, c->scores, esz * (size_t)n_slots * score_elems(g)))) return rc;
-    scores = c->scores.p;
-  }
-  if ((rc = ensure(c, c->smask, sizeof(uint64_t) * (size_t)n_slots * smask_words(g)))) return rc;
-  if ((rc = ensure(c, c->warn, sizeof(int32_t) * (size_t)n_slots))) return rc;
-  if ((rc = ensure(c, c->rowsum, sizeof(RowSummary) * (size_t)n_slots * g.NT * n_segments(g.NF)))) return rc;
-  // float32 scores: k_select leaves equal scores in scan order and k_tie_apply replays the
-  // reference heap for the slots that have them (the same code k_llr runs inside decode_batch)
-  int32_t* tie = nullptr;
-  if (!wf_f64) {
-    if ((rc = ensure(c, c->tie, sizeof(int32_t) * (size_t)n_slots * tie_stride(N)))) return rc;
-    tie = (int32_t*)c->tie.p;
-  }
-  int32_t* warn = (int32_t*)c->warn.p;
-  if ((rc = sync_select_core(c, d_wf, wf_f64, n_slots, T, F, p, cand, cand_score, cand_count, scores,
-                             (uint64_t*)c->smask.p, d_scores == nullptr, warn, (RowSummary*)c->rowsum.p, s, tie)))
-    return rc;
-  if (tie) {
-    const TieArgs ta{n_slots, N, cand_count, warn, tie, cand_score};
-    hipError_t e = launch_tie_apply(ta, cand, cand_score, s);
-    if (e != hipSuccess) return hipfail(c, e, "tie launch");
-  }
-  return FT8_OK;
+// k_bp's work counters, and its clock counters while timing is on (ft8_set_timing allocates them)
+void wire_bp_stats(const ft8_ctx* c, BpLaunch& B) {
+  B.stats = c->stats.as<unsigned long long>();
+  B.clock = c->timing && c->stats.p ? B.stats + 4 : nullptr;
 }
 
-// score + select on caller-provided scratch (scores [n_slots][score_elems], smask
-// [n_slots][smask_words], warn [n_slots], rowsum [n_slots][NT][nseg]); compact: the score kernel may
-// write only the passing scores (k_score2 path, reference selection), else the full grid
+// score + select on the scratch `sc`; compact: the score kernel may write only the passing scores
+// (k_score2 path, reference selection), else the full grid
 int sync_select_core(ft8_ctx* c, const void* d_wf, int wf_f64, int n_slots, int T, int F, const ft8_params* p,
-                     int32_t* cand, double* cand_score, int32_t* cand_count, void* scores, uint64_t* smask,
-                     int compact, int32_t* warn, RowSummary* rowsum, hipStream_t s, int32_t* tie) {
-  const int N = p->max_candidates;
+                     int32_t* cand, double* cand_score, int32_t* cand_count, const SelScratch& sc, int compact,
+                     hipStream_t s) {
   Grid g = grid_of(T, F, p->steps_per_symbol, p->bins_per_tone);
   SyncLaunch L{};
   L.wf = d_wf;
@@ -643,28 +746,49 @@ int sync_select_core(ft8_ctx* c, const void* d_wf, int wf_f64, int n_slots, int 
   L.t0 = g.t0;
   L.NT = g.NT;
   L.NF = g.NF;
-  L.scores = scores;
-  L.smask = smask;
+  L.scores = sc.scores;
+  L.smask = sc.smask;
   L.compact = compact;
-  L.N = N;
+  L.N = p->max_candidates;
   L.min_score = p->min_score;
   L.min_score_f64 = p->min_score_f64;
   L.cand = cand;
   L.cand_score = cand_score;
   L.cand_count = cand_count;
-  L.warn = warn;
-  L.rowsum = rowsum;
-  L.tie = tie;
+  L.warn = sc.warn;
+  L.rowsum = sc.rowsum;
+  L.tie = sc.tie;
   L.topk = (p->flags & FT8_FLAG_TOPK) ? 1 : 0;
   c->last_sync = L;
-  StageTimer t1(c, 1, s);
-  hipError_t e = launch_score(L, s);
-  t1.done();
-  if (e != hipSuccess) return hipfail(c, e, "score launch");
-  StageTimer t2(c, 2, s);
-  e = launch_select(L, s);
-  t2.done();
-  if (e != hipSuccess) return hipfail(c, e, "select launch");
+  int rc = timed_launch(c, kScore, s, "score launch", [&] { return launch_score(L, s); });
+  if (rc) return rc;
+  return timed_launch(c, kSelect, s, "select launch", [&] { return launch_select(L, s); });
+}
+
+int do_sync_select(ft8_ctx* c, const void* d_wf, int wf_f64, int n_slots, int T, int F, const ft8_params* p,
+                   int32_t* cand, double* cand_score, int32_t* cand_count, void* d_scores, hipStream_t s) {
+  int rc = check_search_params(c, p, false);
+  if (rc) return rc;
+  const int N = p->max_candidates;
+  Grid g = grid_of(T, F, p->steps_per_symbol, p->bins_per_tone);
+  if (N <= 0 || g.NT == 0 || g.NF == 0 || n_slots == 0) {
+    hipError_t e = hipMemsetAsync(cand_count, 0, sizeof(int32_t) * (size_t)(n_slots > 0 ? n_slots : 0), s);
+    return e == hipSuccess ? FT8_OK : hipfail(c, e, "memset");
+  }
+  // without a caller grid the scores stay in the compact layout (only passing scores written)
+  if ((rc = ensure_sel_scratch(c, n_slots, g, N, wf_f64, d_scores == nullptr))) return rc;
+  SelScratch sc = sel_scratch_at(c, 0, g, N, wf_f64);
+  if (d_scores) sc.scores = d_scores;
+  if ((rc = sync_select_core(c, d_wf, wf_f64, n_slots, T, F, p, cand, cand_score, cand_count, sc,
+                             d_scores == nullptr, s)))
+    return rc;
+  // float32 scores: k_select leaves equal scores in scan order and k_tie_apply replays the
+  // reference heap for the slots that have them (the same code k_llr runs inside decode_batch)
+  if (sc.tie) {
+    const TieArgs ta{n_slots, N, cand_count, sc.warn, sc.tie, cand_score};
+    hipError_t e = launch_tie_apply(ta, cand, cand_score, s);
+    if (e != hipSuccess) return hipfail(c, e, "tie launch");
+  }
   return FT8_OK;
 }
 
@@ -706,21 +830,16 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
   for (int k = 0; k < n_chunks; ++k) {
     const int c0 = k * csz, ns = std::min(csz, n_slots - c0);
     hipStream_t cs = n_str > 0 ? c->streams[k % n_str] : s;
-    char* wf = (char*)c->wf.p + esz * (size_t)c0 * T * F;
+    char* wf = c->wf.as<char>() + esz * (size_t)c0 * T * F;
     const char* xs = (const char*)d_samples + in_esz * (size_t)c0 * slot_stride;
     if ((rc = do_stft(c, xs, dtype, n_samples, ns, slot_stride, p, wf, cs))) return rc;
-    int32_t* cand = (int32_t*)c->cand.p + 2 * (size_t)c0 * N;
-    double* cand_score = (double*)c->cand_score.p + (size_t)c0 * N;
-    int32_t* cand_count = (int32_t*)c->cand_count.p + c0;
-    // float32 scores: equal scores keep the select order through LLR/BP and are reordered by
-    // k_compact after k_llr's first workgroups replayed the reference heap
-    int32_t* tie = f64 ? nullptr : (int32_t*)c->tie.p + (size_t)c0 * tie_stride(N);
-    int32_t* warn = (int32_t*)c->warn.p + c0;
-    if ((rc = sync_select_core(c, wf, f64, ns, T, F, p, cand, cand_score, cand_count,
-                               (char*)c->scores.p + esz * (size_t)c0 * score_elems(gr),
-                               (uint64_t*)c->smask.p + (size_t)c0 * smask_words(gr), 1, (int32_t*)c->warn.p + c0,
-                               (RowSummary*)c->rowsum.p + (size_t)c0 * gr.NT * n_segments(gr.NF), cs, tie)))
-      return rc;
+    int32_t* cand = c->cand.as<int32_t>() + 2 * (size_t)c0 * N;
+    double* cand_score = c->cand_score.as<double>() + (size_t)c0 * N;
+    int32_t* cand_count = c->cand_count.as<int32_t>() + c0;
+    // float32 scores (sc.tie): equal scores keep the select order through LLR/BP and are reordered
+    // by k_compact after k_llr's first workgroups replayed the reference heap
+    const SelScratch sc = sel_scratch_at(c, c0, gr, N, f64);
+    if ((rc = sync_select_core(c, wf, f64, ns, T, F, p, cand, cand_score, cand_count, sc, 1, cs))) return rc;
     BpLaunch B{};
     B.wf = wf;
     B.wf_f64 = f64;
@@ -738,24 +857,17 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     B.mode = 0;
     B.normalize = 1;
     B.max_iterations = p->max_iterations;
-    B.llr_out = (double*)c->llr.p + (size_t)FT8_LDPC_N * c0 * N;
+    B.llr_out = c->llr.as<double>() + (size_t)FT8_LDPC_N * c0 * N;
     B.llr_in = B.llr_out;
-    B.res = (ft8_result*)c->res_all.p + (size_t)c0 * N;
-    B.work = (unsigned long long*)c->work.p + 1 + k;
+    B.res = c->res_all.as<ft8_result>() + (size_t)c0 * N;
+    B.work = c->work.as<unsigned long long>() + 1 + k;
     B.work_base = &c->work_base[1 + k];
-    B.stats = (unsigned long long*)c->stats.p;
-    B.clock = c->timing && c->stats.p ? (unsigned long long*)c->stats.p + 4 : nullptr;
+    wire_bp_stats(c, B);
     B.grid_waves = c->bp_waves;  // resident waves per SIMD of the persistent grid (kernel maximum 4)
-    B.tie = tie;
-    B.warn = warn;
-    StageTimer t6(c, 6, cs);
-    e = launch_llr(B, cs);
-    t6.done();
-    if (e != hipSuccess) return hipfail(c, e, "llr launch");
-    StageTimer t3(c, 3, cs);
-    e = launch_bp(B, cs);
-    t3.done();
-    if (e != hipSuccess) return hipfail(c, e, "bp launch");
+    B.tie = sc.tie;
+    B.warn = sc.warn;
+    if ((rc = timed_launch(c, kLlr, cs, "llr launch", [&] { return launch_llr(B, cs); }))) return rc;
+    if ((rc = timed_launch(c, kBp, cs, "bp launch", [&] { return launch_bp(B, cs); }))) return rc;
     CompactLaunch C{};
     C.res = B.res;
     C.cand_count = cand_count;
@@ -764,14 +876,11 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     C.out = d_out ? d_out + (size_t)c0 * cap : nullptr;
     C.counts = d_counts + c0;
     C.cap = cap;
-    C.warn = warn;
-    C.tie = tie;
+    C.warn = sc.warn;
+    C.tie = sc.tie;
     c->last_bp = B;
     c->last_compact = C;
-    StageTimer t4(c, 4, cs);
-    e = launch_compact(C, cs);
-    t4.done();
-    if (e != hipSuccess) return hipfail(c, e, "compact launch");
+    if ((rc = timed_launch(c, kCompact, cs, "compact launch", [&] { return launch_compact(C, cs); }))) return rc;
   }
   for (int i = 0; i < n_str; ++i) {
     if ((e = hipEventRecord(c->joins[i], c->streams[i])) != hipSuccess) return hipfail(c, e, "join");
@@ -847,19 +956,13 @@ int subtract_core(ft8_ctx* c, const void* x, int dtype, float* resid, int64_t n_
   L.res = res;
   L.counts = counts;
   L.cap = cap;
-  L.P = (const double*)c->gfsk_P.p;
-  L.Pf = (const float*)c->gfsk_Pf.p;
+  L.P = c->gfsk_P.as<const double>();
+  L.Pf = c->gfsk_Pf.as<const float>();
   L.est = c->sub_est.p;
-  L.list = (int32_t*)c->sub_list.p;
+  L.list = c->sub_list.as<int32_t>();
   L.Q = Q;
-  StageTimer tm(c, 7, s);
-  hipError_t e = launch_sub_est(L, s);
-  tm.done();
-  if (e != hipSuccess) return hipfail(c, e, "subtract launch");
-  StageTimer tm2(c, 11, s);
-  e = launch_sub_apply(L, s);
-  tm2.done();
-  if (e != hipSuccess) return hipfail(c, e, "subtract launch");
+  if ((rc = timed_launch(c, kSubEst, s, "subtract launch", [&] { return launch_sub_est(L, s); }))) return rc;
+  if ((rc = timed_launch(c, kSubApply, s, "subtract launch", [&] { return launch_sub_apply(L, s); }))) return rc;
   c->sub_slots = n_slots;
   c->sub_cap = cap;
   return FT8_OK;
@@ -871,67 +974,36 @@ int drift_bins(int nfft) { return (nfft + 1) / 2; }
 
 int stft_argmax_core(ft8_ctx* c, const void* x, int dtype, int64_t n_samples, int n_slots, int64_t stride,
                      const ft8_params* p, int32_t* idx, hipStream_t s) {
-  Geo g;
-  std::string why;
-  int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
-  if (rc) return fail(c, rc, why);
-  if (dtype < FT8_F32 || dtype > FT8_I16) return fail(c, FT8_E_ARG, "unknown sample dtype");
-  if (p->t_lo < 0 || p->t_hi > g.frames || p->t_lo > p->t_hi)
-    return fail(c, FT8_E_ARG, "frame range [t_lo, t_hi) outside [0, " + std::to_string(g.frames) + ")");
-  if (p->f_lo < 0 || p->f_hi > g.nfft || p->f_lo >= p->f_hi) return fail(c, FT8_E_ARG, "bin range [f_lo, f_hi) empty or outside [0, nfft)");
-  if (p->t_hi == p->t_lo || n_slots == 0) return FT8_OK;
-  const bool f64 = is_f64_dtype(dtype), cplx = is_cplx_dtype(dtype);
-  StftLaunch L{};
-  if ((rc = get_plan(c, g.nfft, cplx, f64, g.nperseg, &L.plan))) return rc;
+  StftLaunch L;
+  bool launch;
+  int rc = make_stft_launch(c, p, dtype, n_samples, n_slots, stride, StftUse::Argmax, &L, &launch);
+  if (rc || !launch) return rc;
+  L.samples = x;
+  L.argmax = idx;
+  const size_t frames = (size_t)n_slots * (size_t)(p->t_hi - p->t_lo);
   if (L.plan.dft || L.plan.blue) {
     // the direct DFT and the chirp-z path write the dB rows, then reduce each to its argmax: stage
     // them in wf
-    if (L.plan.dft && (size_t)g.nperseg * (f64 ? 16 : 8) > (size_t)kMaxDftLds)
-      return fail(c, FT8_E_RANGE, "nperseg " + std::to_string(g.nperseg) + " exceeds the direct-DFT limit");
-    const size_t bytes = (size_t)n_slots * (p->t_hi - p->t_lo) * (p->f_hi - p->f_lo) * (f64 ? 8 : 4);
-    if ((rc = ensure(c, c->wf, bytes))) return rc;
+    if ((rc = ensure(c, c->wf, frames * (p->f_hi - p->f_lo) * (is_f64_dtype(dtype) ? 8 : 4)))) return rc;
     L.out = c->wf.p;
   }
-  WinEntry* w = nullptr;
-  if ((rc = get_window(c, g.nperseg, f64, &w))) return rc;
-  L.samples = x;
-  L.dtype = dtype;
-  L.n_samples = n_samples;
-  L.slot_stride = stride;
-  L.n_slots = n_slots;
-  L.nperseg = g.nperseg;
-  L.hop = g.hop;
-  L.nfft = g.nfft;
-  L.t_lo = p->t_lo;
-  L.t_hi = p->t_hi;
-  L.f_lo = p->f_lo;
-  L.f_hi = p->f_hi;
-  L.window = w->w;
-  L.scale = w->scale;
-  L.argmax = idx;
-  // the geometries launch_stft sends to k_stftc3840 (stft.hip)
-  if (dtype == FT8_C128 && !L.plan.dft && !L.plan.blue && g.nfft == 3840 && g.nperseg == 1920 &&
-      (g.hop == 240 || g.hop == 480 || g.hop == 960 || g.hop == 1920)) {
-    const size_t frames = (size_t)n_slots * (size_t)(p->t_hi - p->t_lo);
+  if (dtype != FT8_C128 || !stftc3840_eligible(L)) {
+    c->screen_frames = 0;
+  } else {
     if ((rc = ensure(c, c->screen, sizeof(int32_t) * (frames + 1)))) return rc;
-    L.screen_count = (int32_t*)c->screen.p;
+    L.screen_count = c->screen.as<int32_t>();
     L.screen_list = L.screen_count + 1;
     // the screening pass transforms in float32: its own twiddles and window
     FftPlan fp;
-    if ((rc = get_plan(c, g.nfft, true, false, g.nperseg, &fp))) return rc;
+    if ((rc = get_plan(c, L.nfft, true, false, L.nperseg, &fp))) return rc;
     WinEntry* wf32 = nullptr;
-    if ((rc = get_window(c, g.nperseg, false, &wf32))) return rc;
+    if ((rc = get_window(c, L.nperseg, false, &wf32))) return rc;
     if (fp.P != 3840 || fp.dft || fp.blue) return fail(c, FT8_E_UNSUPPORTED, "float32 screening plan");
     L.screen_tw = fp.tw;
-    L.screen_window = wf32->w;
+    L.screen_window = wf32->w.p;
     c->screen_frames = (int64_t)frames;
-  } else {
-    c->screen_frames = 0;
   }
-  StageTimer tm(c, 8, s);
-  hipError_t e = launch_stft(L, s);
-  tm.done();
-  return e == hipSuccess ? FT8_OK : hipfail(c, e, "stft argmax launch");
+  return timed_launch(c, kDriftStftArgmax, s, "stft argmax launch", [&] { return launch_stft(L, s); });
 }
 
 int check_drift_params(ft8_ctx* c, const ft8_drift_params* p) {
@@ -1006,13 +1078,10 @@ int drift_fit_core(ft8_ctx* c, int stage, const int32_t* idx, int n_slots, int T
   L.max_segments = segments ? max_segments : 0;
   if (stage == 2) {
     if ((rc = drift_template(c, p))) return rc;
-    L.tmpl = (const double*)c->drift_tmpl.p;
+    L.tmpl = c->drift_tmpl.as<const double>();
     L.n_tmpl = c->tmpl_len;
   }
-  StageTimer tm(c, 9, s);
-  hipError_t e = launch_drift_fit(stage, L, s);
-  tm.done();
-  return e == hipSuccess ? FT8_OK : hipfail(c, e, "drift fit launch");
+  return timed_launch(c, kDriftFit, s, "drift fit launch", [&] { return launch_drift_fit(stage, L, s); });
 }
 
 }  // namespace
@@ -1047,18 +1116,6 @@ int ft8_destroy(ft8_ctx* c) {
   if (!c) return FT8_OK;
   {
     DeviceGuard dg(c->device);
-    for (auto* b : {&c->wf, &c->scores, &c->smask, &c->cand, &c->cand_score, &c->cand_count, &c->warn, &c->rowsum,
-                    &c->res_all, &c->work, &c->stats, &c->llr, &c->tie, &c->residual, &c->sub_est, &c->sub_list, &c->screen, &c->out1,
-                    &c->counts1, &c->out2, &c->counts2, &c->gfsk_P, &c->gfsk_Pf, &c->drift_idx, &c->drift_tmpl})
-      if (b->p) (void)hipFree(b->p);
-    for (auto& p : c->plans) {
-      if (p.tw) (void)hipFree(p.tw);
-      if (p.post) (void)hipFree(p.post);
-      if (p.chirp) (void)hipFree(p.chirp);
-      if (p.hspec) (void)hipFree(p.hspec);
-    }
-    for (auto& w : c->wins)
-      if (w.w) (void)hipFree(w.w);
     for (auto& t : c->pending) {
       (void)hipEventDestroy(t.a);
       (void)hipEventDestroy(t.b);
@@ -1068,8 +1125,8 @@ int ft8_destroy(ft8_ctx* c) {
     for (auto ev : c->joins) (void)hipEventDestroy(ev);
     if (c->fork) (void)hipEventDestroy(c->fork);
     if (c->last_done) (void)hipEventDestroy(c->last_done);
+    delete c;  // every DevBuf of the context (scratch, plans, windows) is freed here, on its device
   }
-  delete c;
   return FT8_OK;
 }
 
@@ -1119,20 +1176,18 @@ int ft8_stft_screen_stats(ft8_ctx* c, int64_t* frames_redone, int64_t* frames) {
 int ft8_stft_method(ft8_ctx* c, int32_t fs, int32_t bpt, int32_t sps, int64_t n, int dtype) {
   if (!c) return FT8_E_ARG;
   if (dtype < FT8_F32 || dtype > FT8_I16) return fail(c, FT8_E_ARG, "unknown sample dtype");
-  Geo g;
-  std::string why;
-  int rc = geometry(fs, bpt, sps, n, &g, &why);
-  if (rc) return fail(c, rc, why);
+  ft8_params p{};
+  p.sample_rate = fs;
+  p.bins_per_tone = bpt;
+  p.steps_per_symbol = sps;
   DeviceGuard dg(c->device);
-  StftLaunch L{};
-  if ((rc = get_plan(c, g.nfft, is_cplx_dtype(dtype), is_f64_dtype(dtype), g.nperseg, &L.plan))) return rc;
+  StftLaunch L;
+  bool launch;
+  // stride 2: the packed kernel's only stride condition (even) is the caller's
+  int rc = make_stft_launch(c, &p, dtype, n, 1, 2, StftUse::Method, &L, &launch);
+  if (rc) return rc;
   if (L.plan.blue) return FT8_STFT_CHIRPZ;
   if (L.plan.dft) return FT8_STFT_DFT;
-  L.dtype = dtype;
-  L.nfft = g.nfft;
-  L.nperseg = g.nperseg;
-  L.hop = g.hop;
-  L.slot_stride = 2;  // the packed kernel's only stride condition (even) is the caller's
   return stft3840_eligible(L) ? FT8_STFT_PACKED3840 : FT8_STFT_STOCKHAM;
 }
 
@@ -1176,10 +1231,8 @@ int ft8_llr(ft8_ctx* c, const void* d_wf, int wf_f64, int32_t T, int32_t F, int3
   L.mode = 1;
   L.normalize = normalize;
   L.llr_out = d_llr;
-  StageTimer tm(c, 6, (hipStream_t)stream);
-  hipError_t e = launch_llr(L, (hipStream_t)stream);
-  tm.done();
-  return e == hipSuccess ? FT8_OK : hipfail(c, e, "llr launch");
+  hipStream_t s = (hipStream_t)stream;
+  return timed_launch(c, kLlr, s, "llr launch", [&] { return launch_llr(L, s); });
 }
 
 int ft8_normalize(ft8_ctx* c, const double* d_in, int32_t n, double* d_out, void* stream) {
@@ -1193,10 +1246,8 @@ int ft8_normalize(ft8_ctx* c, const double* d_in, int32_t n, double* d_out, void
   L.n_items = n;
   L.normalize = 1;
   L.llr_out = d_out;
-  StageTimer tm(c, 6, (hipStream_t)stream);
-  hipError_t e = launch_llr(L, (hipStream_t)stream);
-  tm.done();
-  return e == hipSuccess ? FT8_OK : hipfail(c, e, "normalize launch");
+  hipStream_t s = (hipStream_t)stream;
+  return timed_launch(c, kLlr, s, "normalize launch", [&] { return launch_llr(L, s); });
 }
 
 int ft8_bp(ft8_ctx* c, const double* d_llr, int32_t n, int32_t max_iterations, uint8_t* d_plain, ft8_result* d_res,
@@ -1216,14 +1267,11 @@ int ft8_bp(ft8_ctx* c, const double* d_llr, int32_t n, int32_t max_iterations, u
   L.max_iterations = max_iterations;
   L.plain_out = d_plain;
   L.res = d_res;
-  L.work = (unsigned long long*)c->work.p;
+  L.work = c->work.as<unsigned long long>();
   L.work_base = &c->work_base[0];
-  L.stats = (unsigned long long*)c->stats.p;
-  L.clock = c->timing && c->stats.p ? (unsigned long long*)c->stats.p + 4 : nullptr;
-  StageTimer tm(c, 3, (hipStream_t)stream);
-  hipError_t e = launch_bp(L, (hipStream_t)stream);
-  tm.done();
-  return e == hipSuccess ? FT8_OK : hipfail(c, e, "bp launch");
+  wire_bp_stats(c, L);
+  hipStream_t s = (hipStream_t)stream;
+  return timed_launch(c, kBp, s, "bp launch", [&] { return launch_bp(L, s); });
 }
 
 int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
@@ -1237,14 +1285,13 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   DeviceGuard dg(c->device);
   hipStream_t s = (hipStream_t)stream;
   if (n_slots == 0) return FT8_OK;
-  StageTimer whole(c, 5, s);
+  StageTimer whole(c, kDecodeBatch, s);
   Geo g;
   std::string why;
   int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
   if (rc) return fail(c, rc, why);
   const int T = p->t_hi - p->t_lo, F = p->f_hi - p->f_lo;
   const bool f64 = is_f64_dtype(dtype);
-  const size_t esz = f64 ? 8 : 4;
   const int N = p->max_candidates;
   Grid gr = grid_of(T > 0 ? T : 0, F > 0 ? F : 0, p->steps_per_symbol, p->bins_per_tone);
   if (T <= 0 || F <= 0 || N <= 0 || gr.NT == 0 || gr.NF == 0) {
@@ -1255,21 +1302,14 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
     whole.done();
     return e == hipSuccess ? FT8_OK : hipfail(c, e, "memset");
   }
-  if (N > kMaxCandidates)
-    return fail(c, FT8_E_RANGE, "max_candidates > " + std::to_string(kMaxCandidates) + " is not supported");
-  if ((rc = ensure(c, c->wf, esz * (size_t)n_slots * T * F))) return rc;
+  if ((rc = check_search_params(c, p, true))) return rc;
+  if ((rc = ensure(c, c->wf, (f64 ? 8 : 4) * (size_t)n_slots * T * F))) return rc;
   if ((rc = ensure(c, c->cand, sizeof(int32_t) * 2 * (size_t)n_slots * N))) return rc;
   if ((rc = ensure(c, c->cand_score, sizeof(double) * (size_t)n_slots * N))) return rc;
   if ((rc = ensure(c, c->cand_count, sizeof(int32_t) * (size_t)n_slots))) return rc;
   if ((rc = ensure(c, c->res_all, sizeof(ft8_result) * (size_t)n_slots * N))) return rc;
   if ((rc = ensure(c, c->llr, sizeof(double) * FT8_LDPC_N * (size_t)n_slots * N))) return rc;
-  if ((rc = ensure(c, c->scores, esz * (size_t)n_slots * score_elems(gr)))) return rc;
-  if ((rc = ensure(c, c->smask, sizeof(uint64_t) * (size_t)n_slots * smask_words(gr)))) return rc;
-  if ((rc = ensure(c, c->warn, sizeof(int32_t) * (size_t)n_slots))) return rc;
-  if ((rc = ensure(c, c->rowsum, sizeof(RowSummary) * (size_t)n_slots * gr.NT * n_segments(gr.NF)))) return rc;
-  if (!f64 && (rc = ensure(c, c->tie, sizeof(int32_t) * (size_t)n_slots * tie_stride(N)))) return rc;
-  if (p->steps_per_symbol <= 0 || p->bins_per_tone <= 0) return fail(c, FT8_E_ARG, "bad oversampling factors");
-  if (p->flags & ~(FT8_FLAG_TOPK | FT8_FLAG_SUBTRACT)) return fail(c, FT8_E_ARG, "unknown bits in ft8_params.flags");
+  if ((rc = ensure_sel_scratch(c, n_slots, gr, N, f64))) return rc;
   if (!(p->flags & FT8_FLAG_SUBTRACT)) {
     if ((rc = decode_pass(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, d_out, d_counts, cap, s))) return rc;
     whole.done();
@@ -1283,11 +1323,11 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   if ((rc = ensure(c, c->counts1, sizeof(int32_t) * (size_t)n_slots))) return rc;
   if ((rc = ensure(c, c->counts2, sizeof(int32_t) * (size_t)n_slots))) return rc;
   if ((rc = ensure(c, c->residual, sizeof(float) * (size_t)n_slots * n_samples))) return rc;
-  ft8_result* out1 = (ft8_result*)c->out1.p;
-  ft8_result* out2 = (ft8_result*)c->out2.p;
-  int32_t* counts1 = (int32_t*)c->counts1.p;
-  int32_t* counts2 = (int32_t*)c->counts2.p;
-  float* resid = (float*)c->residual.p;
+  ft8_result* out1 = c->out1.as<ft8_result>();
+  ft8_result* out2 = c->out2.as<ft8_result>();
+  int32_t* counts1 = c->counts1.as<int32_t>();
+  int32_t* counts2 = c->counts2.as<int32_t>();
+  float* resid = c->residual.as<float>();
   if ((rc = decode_pass(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, out1, counts1, N, s))) return rc;
   if ((rc = subtract_core(c, d_samples, dtype, resid, n_samples, n_slots, slot_stride, n_samples, p, out1, counts1,
                           N, s)))
@@ -1335,7 +1375,7 @@ int ft8_synthesize(ft8_ctx* c, const uint8_t* d_tones, const ft8_tx_signal* d_si
   L.nsps = nsps;
   L.style = style;
   L.fs = (double)sample_rate;
-  L.P = (const double*)c->gfsk_P.p;
+  L.P = c->gfsk_P.as<const double>();
   L.out = d_out;
   L.dtype = out_dtype;
   L.n_samples = n_samples;
@@ -1428,7 +1468,7 @@ int ft8_drift_correct(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sa
   if (g.frames > kDriftMaxT) return fail(c, FT8_E_RANGE, "more than " + std::to_string(kDriftMaxT) + " frames per signal");
   const int T = g.frames, F = drift_bins(g.nfft);
   if ((rc = ensure(c, c->drift_idx, sizeof(int32_t) * (size_t)n_slots * T))) return rc;
-  int32_t* idx = (int32_t*)c->drift_idx.p;
+  int32_t* idx = c->drift_idx.as<int32_t>();
   ft8_params sp{};
   sp.sample_rate = fs;
   sp.bins_per_tone = p->bins_per_tone;
@@ -1450,19 +1490,11 @@ int ft8_drift_correct(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sa
   D.fs = p->sample_rate;
   D.inv_fs = 1.0 / p->sample_rate;
   D.inv_2fs2 = 1.0 / (2.0 * p->sample_rate * p->sample_rate);
-  {
-    StageTimer tm(c, 10, s);
-    hipError_t e = launch_derotate1(D, s);
-    tm.done();
-    if (e != hipSuccess) return hipfail(c, e, "derotate launch");
-  }
+  if ((rc = timed_launch(c, kDriftDerotate, s, "derotate launch", [&] { return launch_derotate1(D, s); }))) return rc;
   if (!p->precise_sync) return FT8_OK;
   if ((rc = stft_argmax_core(c, d_out, FT8_C128, n_samples, n_slots, n_samples, &sp, idx, s))) return rc;
   if ((rc = drift_fit_core(c, 2, idx, n_slots, T, F, p, d_res, nullptr, nullptr, 0, s))) return rc;
-  StageTimer tm(c, 10, s);
-  hipError_t e = launch_derotate2(D, p->poly_degree, s);
-  tm.done();
-  return e == hipSuccess ? FT8_OK : hipfail(c, e, "derotate launch");
+  return timed_launch(c, kDriftDerotate, s, "derotate launch", [&] { return launch_derotate2(D, p->poly_degree, s); });
 }
 
 const char* ft8_build_id(void) { return FT8_BUILD_ID; }
@@ -1477,12 +1509,12 @@ int ft8_replay_stage(ft8_ctx* c, int32_t stage, int32_t reps, void* stream) {
   for (int r = 0; r < reps; ++r) {
     hipError_t e;
     switch (stage) {
-      case 0: e = launch_stft(c->last_stft, s); break;
-      case 1: e = launch_score(c->last_sync, s); break;
-      case 2: e = launch_select(c->last_sync, s); break;
-      case 3: e = launch_bp(c->last_bp, s); break;
-      case 4: e = launch_compact(c->last_compact, s); break;
-      case 6: e = launch_llr(c->last_bp, s); break;
+      case kStft: e = launch_stft(c->last_stft, s); break;
+      case kScore: e = launch_score(c->last_sync, s); break;
+      case kSelect: e = launch_select(c->last_sync, s); break;
+      case kBp: e = launch_bp(c->last_bp, s); break;
+      case kCompact: e = launch_compact(c->last_compact, s); break;
+      case kLlr: e = launch_llr(c->last_bp, s); break;
       default: return fail(c, FT8_E_ARG, "stage " + std::to_string(stage) + " cannot be replayed");
     }
     if (e != hipSuccess) return hipfail(c, e, "replay launch");

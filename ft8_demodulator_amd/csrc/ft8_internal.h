@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <stdint.h>
+#include <utility>
 
 #include "../../include/ft8hip.h"
 #include "ft8_ldpc_tables.h"
@@ -74,6 +75,23 @@ struct cplx {
   T x, y;
 };
 
+// ---- LDS opt-in (defined in capi.hip) --------------------------------------------------------
+// A launch whose static + dynamic LDS exceeds the default 64 KB needs the kernel's
+// MaxDynamicSharedMemorySize attribute raised first.  lds_opt_in returns at once, with no runtime
+// call, when `kernel`'s static LDS (queried once) plus dyn_bytes fits the default or when that
+// kernel already holds a grant of at least dyn_bytes on the current device; else it raises the
+// attribute and records the grant.  The state is keyed by (kernel address, device): kernels of one
+// pointer type (the six subtraction kernels are all void(*)(SubLaunch)) never share a grant.
+hipError_t lds_opt_in(const void* kernel, size_t dyn_bytes);
+// opt in, launch, report
+template <typename... P, typename... A>
+hipError_t lds_launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A&&... args) {
+  const hipError_t e = lds_opt_in(reinterpret_cast<const void*>(kern), lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, grid, block, lds, s, std::forward<A>(args)...);
+  return hipGetLastError();
+}
+
 // ---- STFT plan (host-built tables, device-resident) ----------------------------------------
 struct FftPlan {
   int P;              // transform length (nfft/2 for real input, nfft for complex input; nfft if dft;
@@ -114,12 +132,31 @@ struct StftLaunch {
   FftPlan plan;
 };
 hipError_t launch_stft(const StftLaunch& a, hipStream_t s);
+// complex input in the beacon receiver's geometry (nfft 3840, nperseg 1920, hop 240 M): k_stftc3840
+// (stft.hip); a complex128 argmax request in it is screened in float32 first
+bool stftc3840_eligible(const StftLaunch& a);
 // the production geometry (real float32 / int16 input, nfft 3840, nperseg 1920, hop 960) with packed
 // float32 complex arithmetic (stft3840.hip)
 bool stft3840_eligible(const StftLaunch& a);
 hipError_t launch_stft3840(const StftLaunch& a, hipStream_t s);
 bool stftpk_eligible(const StftLaunch& a);        // stft3840.hip: the packed generic real-input plans
 hipError_t launch_stftpk(const StftLaunch& a, hipStream_t s);
+// the static plans k_stft_sp (stft.hip) and k_stft_pk (stft3840.hip) are built for, {P, radices...}:
+// the reference's other real-input geometries (20 kHz, 12 kHz at bpt 10, 6 kHz)
+struct StaticPlan {
+  int P, n, r[4];
+};
+constexpr StaticPlan kStaticPlans[] = {{3200, 4, {16, 8, 5, 5}}, {9600, 4, {16, 8, 15, 5}}, {960, 3, {16, 4, 15}}};
+// index of the static plan with this factorisation, or -1
+inline int static_plan_of(int P, int nstages, const int* radix) {
+  for (int q = 0; q < 3; ++q) {
+    const StaticPlan& p = kStaticPlans[q];
+    bool ok = P == p.P && nstages == p.n;
+    for (int i = 0; ok && i < p.n; ++i) ok = radix[i] == p.r[i];
+    if (ok) return q;
+  }
+  return -1;
+}
 
 // ---- sync score + selection ----------------------------------------------------------------
 // Per (slot, time row) summary written by k_score for k_select: how many grid points of the row

@@ -498,12 +498,6 @@ __global__ __launch_bounds__(kThreads) void k_stft_sp(StftArgs a) {
   }
 }
 
-// the static plans k_stft_sp is built for: {P, radices...}
-struct SpPlan {
-  int P, n, r[5];
-};
-constexpr SpPlan kSpPlans[] = {{3200, 4, {16, 8, 5, 5}}, {9600, 4, {16, 8, 15, 5}}, {960, 3, {16, 4, 15}}};
-
 // ---- k_stftc3840: complex input, nfft = 3840, nperseg = 1920, hop = 240 M (M in 1, 2, 4, 8) -----
 // The beacon receiver's geometry (12 kHz complex baseband, frequency_correction.py; the reference
 // test runs steps_per_symbol = 8, hop 240).  P = 3840 = 16 x 16 x 15: 256 threads, one butterfly per
@@ -789,32 +783,32 @@ __global__ __launch_bounds__(kC38Threads, 2) void k_stftc3840(StftArgs a) {
   }
 }
 
+// f(integral_constant<int, M>) for the hop's M = hop / 240 (stftc3840_eligible admits 1, 2, 4, 8)
+template <typename F>
+hipError_t c3840_by_hop(int hop, F&& f) {
+  switch (hop) {
+    case 240: return f(std::integral_constant<int, 1>{});
+    case 480: return f(std::integral_constant<int, 2>{});
+    case 960: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
+
+template <typename CT>
+constexpr size_t c3840_lds() {
+  return (size_t)(kC38P + kC38P / 16 + 1) * sizeof(cplx<CT>) + 16 * sizeof(CT) + 1920 * sizeof(CT);
+}
+
 template <typename InT, typename CT>
 hipError_t launch_c3840(const StftLaunch& L, StftArgs a, hipStream_t s) {
   const int chunks = (a.nt_out + kC38Chunk - 1) / kC38Chunk;
   a.per_xcd = (int)(((int64_t)chunks * L.n_slots + 7) / 8);
   const dim3 grid((unsigned)(8 * a.per_xcd));
-  const size_t lds = (size_t)(kC38P + kC38P / 16 + 1) * sizeof(cplx<CT>) + 16 * sizeof(CT) + 1920 * sizeof(CT);
-  auto go = [&](auto kern) {
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(kC38Threads), lds, s, a);
-    return hipGetLastError();
-  };
-  auto go_m = [&](auto am) {
-    constexpr int AM = decltype(am)::value;
-    switch (L.hop) {
-      case 240: return go(k_stftc3840<InT, CT, 1, AM>);
-      case 480: return go(k_stftc3840<InT, CT, 2, AM>);
-      case 960: return go(k_stftc3840<InT, CT, 4, AM>);
-      default: return go(k_stftc3840<InT, CT, 8, AM>);
-    }
-  };
-  if (a.argmax == nullptr) return go_m(std::integral_constant<int, 0>{});
-  return go_m(std::integral_constant<int, 1>{});
+  return c3840_by_hop(L.hop, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    if (a.argmax == nullptr) return lds_launch(k_stftc3840<InT, CT, M, 0>, grid, dim3(kC38Threads), c3840_lds<CT>(), s, a);
+    return lds_launch(k_stftc3840<InT, CT, M, 1>, grid, dim3(kC38Threads), c3840_lds<CT>(), s, a);
+  });
 }
 
 // complex128 argmax in two steps: the float32 transform decides every frame whose argmax the
@@ -827,17 +821,6 @@ hipError_t launch_c3840_screened(const StftLaunch& L, StftArgs a, hipStream_t s)
   if (e != hipSuccess) return e;
   const int chunks = (a.nt_out + kC38Chunk - 1) / kC38Chunk;
   a.per_xcd = (int)(((int64_t)chunks * L.n_slots + 7) / 8);
-  const size_t lds32 = (size_t)(kC38P + kC38P / 16 + 1) * sizeof(cplx<float>) + 16 * sizeof(float) + 1920 * sizeof(float);
-  const size_t lds64 = (size_t)(kC38P + kC38P / 16 + 1) * sizeof(cplx<double>) + 16 * sizeof(double) + 1920 * sizeof(double);
-  auto go = [&](auto kern, dim3 grid, size_t lds, const StftArgs& args) {
-    if (lds > 64 * 1024) {
-      hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)lds);
-      if (e2 != hipSuccess) return e2;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(kC38Threads), lds, s, args);
-    return hipGetLastError();
-  };
   const dim3 g1((unsigned)(8 * a.per_xcd));
   const int64_t frames = (int64_t)a.nt_out * L.n_slots;
   // the screen transforms in float32 (the plan's tables are float64 for complex128 input)
@@ -845,20 +828,12 @@ hipError_t launch_c3840_screened(const StftLaunch& L, StftArgs a, hipStream_t s)
   a32.tw = L.screen_tw;
   a32.window = L.screen_window;
   const dim3 g2((unsigned)std::min<int64_t>(frames, 512));  // two float64 workgroups per CU
-  switch (L.hop) {
-    case 240:
-      if ((e = go(k_stftc3840<double, float, 1, 2>, g1, lds32, a32)) != hipSuccess) return e;
-      return go(k_stftc3840<double, double, 1, 3>, g2, lds64, a);
-    case 480:
-      if ((e = go(k_stftc3840<double, float, 2, 2>, g1, lds32, a32)) != hipSuccess) return e;
-      return go(k_stftc3840<double, double, 2, 3>, g2, lds64, a);
-    case 960:
-      if ((e = go(k_stftc3840<double, float, 4, 2>, g1, lds32, a32)) != hipSuccess) return e;
-      return go(k_stftc3840<double, double, 4, 3>, g2, lds64, a);
-    default:
-      if ((e = go(k_stftc3840<double, float, 8, 2>, g1, lds32, a32)) != hipSuccess) return e;
-      return go(k_stftc3840<double, double, 8, 3>, g2, lds64, a);
-  }
+  return c3840_by_hop(L.hop, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    const hipError_t e1 = lds_launch(k_stftc3840<double, float, M, 2>, g1, dim3(kC38Threads), c3840_lds<float>(), s, a32);
+    if (e1 != hipSuccess) return e1;
+    return lds_launch(k_stftc3840<double, double, M, 3>, g2, dim3(kC38Threads), c3840_lds<double>(), s, a);
+  });
 }
 
 // ---- k_stft_dft: direct DFT for lengths the FFT plans cannot take ---------------------------
@@ -1034,24 +1009,24 @@ __global__ __launch_bounds__(kWave) void k_row_argmax(const CT* rows, int nf, in
   if (threadIdx.x == 0) idx[r] = bi;
 }
 
-template <typename InT, bool CPLX, typename CT>
-hipError_t launch_dft(const StftLaunch& L, const StftArgs& a, hipStream_t s) {
-  const size_t lds = (size_t)L.nperseg * sizeof(cplx<CT>);
-  if (lds > (size_t)kMaxDftLds) return hipErrorInvalidValue;
-  auto kern = k_stft_dft<InT, CPLX, CT>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  const int nbb = (a.nf_out + kDftThreads - 1) / kDftThreads;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(nbb * a.nt_out), (unsigned)L.n_slots), dim3(kDftThreads), lds, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || !L.argmax) return e;
+// the argmax of a launch whose kernel wrote the dB rows to a.out (direct DFT, chirp-z)
+template <typename CT>
+hipError_t launch_row_argmax(const StftLaunch& L, const StftArgs& a, hipStream_t s) {
   const int64_t rows = (int64_t)a.nt_out * L.n_slots;
   hipLaunchKernelGGL(k_row_argmax<CT>, dim3((unsigned)rows), dim3(kWave), 0, s, reinterpret_cast<const CT*>(a.out),
                      a.nf_out, rows, L.argmax);
   return hipGetLastError();
+}
+
+template <typename InT, bool CPLX, typename CT>
+hipError_t launch_dft(const StftLaunch& L, StftArgs a, hipStream_t s) {
+  a.argmax = nullptr;  // the DFT kernel writes dB rows; an argmax request reduces them below
+  const size_t lds = (size_t)L.nperseg * sizeof(cplx<CT>);
+  if (lds > (size_t)kMaxDftLds) return hipErrorInvalidValue;
+  const int nbb = (a.nf_out + kDftThreads - 1) / kDftThreads;
+  const hipError_t e = lds_launch(k_stft_dft<InT, CPLX, CT>, dim3((unsigned)(nbb * a.nt_out), (unsigned)L.n_slots),
+                                  dim3(kDftThreads), lds, s, a);
+  return e != hipSuccess || !L.argmax ? e : launch_row_argmax<CT>(L, a, s);
 }
 
 template <typename InT, bool CPLX, typename CT>
@@ -1071,18 +1046,8 @@ hipError_t launch_blue(const StftLaunch& L, const StftArgs& a, hipStream_t s) {
   if (a.P > 512 * 16 || L.plan.L > a.P) return hipErrorInvalidValue;
   const bool wide = a.P > kThreads * 16;
   auto kern = !wide ? k_stft_blue<InT, CPLX, CT, 16, kThreads> : k_stft_blue<InT, CPLX, CT, 16, 512>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(8 * b.s.per_xcd)), dim3(wide ? 512 : kThreads), lds, s, b);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || !L.argmax) return e;
-  const int64_t rows = (int64_t)a.nt_out * L.n_slots;
-  hipLaunchKernelGGL(k_row_argmax<CT>, dim3((unsigned)rows), dim3(kWave), 0, s, reinterpret_cast<const CT*>(a.out),
-                     a.nf_out, rows, L.argmax);
-  return hipGetLastError();
+  const hipError_t e = lds_launch(kern, dim3((unsigned)(8 * b.s.per_xcd)), dim3(wide ? 512 : kThreads), lds, s, b);
+  return e != hipSuccess || !L.argmax ? e : launch_row_argmax<CT>(L, a, s);
 }
 
 template <typename InT, bool CPLX, typename CT>
@@ -1090,26 +1055,18 @@ hipError_t launch_t(const StftLaunch& L, const StftArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)(8 * a.per_xcd));  // see k_stft: a.per_xcd (slot, frame) pairs per XCD
   // pidx padding + the argmax epilogue's cross-wave scratch
   const size_t lds = (size_t)(a.P + a.P / 16 + 1) * sizeof(cplx<CT>) + 64;
-  auto go = [&](auto kern) {
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(kThreads), lds, s, a);
-    return hipGetLastError();
-  };
+  auto go = [&](auto kern) { return lds_launch(kern, grid, dim3(kThreads), lds, s, a); };
   if constexpr (!CPLX && sizeof(CT) == 4) {
-    // a static plan for the reference's other real-input geometries (dB rows, nperseg <= P)
-    auto plan_is = [&](const SpPlan& q) {
-      if (a.P != q.P || a.nstages != q.n || a.argmax != nullptr || a.nperseg > a.P) return false;
-      for (int i = 0; i < q.n; ++i)
-        if (a.radix[i] != q.r[i]) return false;
-      return true;
-    };
-    if (plan_is(kSpPlans[0])) return go(k_stft_sp<InT, 3200, 13, 16, 8, 5, 5>);
-    if (plan_is(kSpPlans[1])) return go(k_stft_sp<InT, 9600, 38, 16, 8, 15, 5>);
-    if (plan_is(kSpPlans[2])) return go(k_stft_sp<InT, 960, 4, 16, 4, 15>);
+    // a static plan for the reference's other real-input geometries (dB rows, nperseg <= P): what
+    // k_stft_pk does not take of them (odd hop or stride)
+    if (a.argmax == nullptr && a.nperseg <= a.P) {
+      switch (static_plan_of(a.P, a.nstages, a.radix)) {
+        case 0: return go(k_stft_sp<InT, 3200, 13, 16, 8, 5, 5>);
+        case 1: return go(k_stft_sp<InT, 9600, 38, 16, 8, 15, 5>);
+        case 2: return go(k_stft_sp<InT, 960, 4, 16, 4, 15>);
+        default: break;
+      }
+    }
   }
   if (a.P <= kThreads * 8) return go(k_stft<InT, CPLX, CT, 8>);
   // P <= 3840 (3840 = 16 x 16 x 15: one butterfly per thread per stage) keeps half the registers
@@ -1124,7 +1081,33 @@ hipError_t launch_t(const StftLaunch& L, const StftArgs& a, hipStream_t s) {
   }
 }
 
+// tag of a sample dtype's kernel types: input element, complex input, compute type
+template <typename InT_, bool CPLX_, typename CT_>
+struct SampleTypes {
+  using InT = InT_;
+  using CT = CT_;
+  static constexpr bool CPLX = CPLX_;
+};
+
+// f(SampleTypes<InT, CPLX, CT>) for an ft8_dtype
+template <typename F>
+hipError_t by_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case FT8_F32: return f(SampleTypes<float, false, float>{});
+    case FT8_I16: return f(SampleTypes<int16_t, false, float>{});
+    case FT8_F64: return f(SampleTypes<double, false, double>{});
+    case FT8_C64: return f(SampleTypes<float, true, float>{});
+    case FT8_C128: return f(SampleTypes<double, true, double>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
 }  // namespace
+
+bool stftc3840_eligible(const StftLaunch& L) {
+  return !L.plan.dft && !L.plan.blue && (L.dtype == FT8_C64 || L.dtype == FT8_C128) && L.nfft == kC38P &&
+         L.nperseg == 1920 && L.plan.P == kC38P && (L.hop == 240 || L.hop == 480 || L.hop == 960 || L.hop == 1920);
+}
 
 hipError_t launch_stft(const StftLaunch& L, hipStream_t s) {
   StftArgs a{};
@@ -1149,47 +1132,24 @@ hipError_t launch_stft(const StftLaunch& L, hipStream_t s) {
   a.n_slots = L.n_slots;
   a.per_xcd = (int)(((int64_t)a.nt_out * L.n_slots + 7) / 8);
   if (a.nt_out <= 0 || a.nf_out <= 0 || L.n_slots <= 0) return hipSuccess;
-  if (L.plan.blue) {
-    switch (L.dtype) {
-      case FT8_F32: return launch_blue<float, false, float>(L, a, s);
-      case FT8_I16: return launch_blue<int16_t, false, float>(L, a, s);
-      case FT8_F64: return launch_blue<double, false, double>(L, a, s);
-      case FT8_C64: return launch_blue<float, true, float>(L, a, s);
-      case FT8_C128: return launch_blue<double, true, double>(L, a, s);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  if (L.plan.dft) {
-    a.argmax = nullptr;  // the DFT kernel writes dB rows; launch_dft reduces them to the argmax
-    switch (L.dtype) {
-      case FT8_F32: return launch_dft<float, false, float>(L, a, s);
-      case FT8_I16: return launch_dft<int16_t, false, float>(L, a, s);
-      case FT8_F64: return launch_dft<double, false, double>(L, a, s);
-      case FT8_C64: return launch_dft<float, true, float>(L, a, s);
-      case FT8_C128: return launch_dft<double, true, double>(L, a, s);
-      default: return hipErrorInvalidValue;
-    }
-  }
+  // (the three special geometries below take no chirp-z or direct-DFT plan)
   // production geometry (12 kHz, bins_per_tone = steps_per_symbol = 2): stft3840.hip's packed kernel
   if (stft3840_eligible(L)) return launch_stft3840(L, s);
   // the reference's other real-input geometries (20 kHz, 12 kHz at bpt 10, 6 kHz): packed plans
   if (stftpk_eligible(L)) return launch_stftpk(L, s);
   // complex input in the beacon receiver's geometry (12 kHz: nfft 3840, nperseg 1920, hop 240 M)
-  if ((L.dtype == FT8_C64 || L.dtype == FT8_C128) && L.nfft == kC38P && L.nperseg == 1920 && a.P == kC38P &&
-      (L.hop == 240 || L.hop == 480 || L.hop == 960 || L.hop == 1920)) {
+  if (stftc3840_eligible(L)) {
     if (L.dtype == FT8_C128 && L.argmax && L.screen_list && L.screen_tw && L.screen_window)
       return launch_c3840_screened(L, a, s);
     if (L.dtype == FT8_C128) return launch_c3840<double, double>(L, a, s);
     return launch_c3840<float, float>(L, a, s);
   }
-  switch (L.dtype) {
-    case FT8_F32: return launch_t<float, false, float>(L, a, s);
-    case FT8_I16: return launch_t<int16_t, false, float>(L, a, s);
-    case FT8_F64: return launch_t<double, false, double>(L, a, s);
-    case FT8_C64: return launch_t<float, true, float>(L, a, s);
-    case FT8_C128: return launch_t<double, true, double>(L, a, s);
-    default: return hipErrorInvalidValue;
-  }
+  return by_dtype(L.dtype, [&](auto t) {
+    using T = decltype(t);
+    if (L.plan.blue) return launch_blue<typename T::InT, T::CPLX, typename T::CT>(L, a, s);
+    if (L.plan.dft) return launch_dft<typename T::InT, T::CPLX, typename T::CT>(L, a, s);
+    return launch_t<typename T::InT, T::CPLX, typename T::CT>(L, a, s);
+  });
 }
 
 }  // namespace ft8

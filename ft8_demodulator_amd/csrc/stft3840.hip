@@ -705,23 +705,13 @@ hipError_t launch_stft3840(const StftLaunch& L, hipStream_t s) {
   return hipGetLastError();
 }
 
-// the plans k_stft_pk is built for
-struct PkPlan {
-  int P, n, r[4];
-};
 constexpr int kPk9600Threads = 640;
-constexpr PkPlan kPkPlans[] = {{3200, 4, {16, 8, 5, 5}}, {9600, 4, {16, 8, 15, 5}}, {960, 3, {16, 4, 15}}};
 
+// the static plan (kStaticPlans) k_stft_pk takes this launch with, or -1
 static int pk_plan_of(const StftLaunch& L) {
   if (L.argmax || L.plan.dft || L.plan.blue || !(L.dtype == FT8_F32 || L.dtype == FT8_I16)) return -1;
   if (L.nfft != 2 * L.plan.P || L.nperseg > L.plan.P || (L.hop % 2) || (L.slot_stride % 2)) return -1;
-  for (int q = 0; q < 3; ++q) {
-    const PkPlan& p = kPkPlans[q];
-    bool ok = L.plan.P == p.P && L.plan.nstages == p.n;
-    for (int i = 0; ok && i < p.n; ++i) ok = L.plan.radix[i] == p.r[i];
-    if (ok) return q;
-  }
-  return -1;
+  return static_plan_of(L.plan.P, L.plan.nstages, L.plan.radix);
 }
 
 bool stftpk_eligible(const StftLaunch& L) { return pk_plan_of(L) >= 0; }
@@ -749,15 +739,8 @@ hipError_t launch_stftpk(const StftLaunch& L, hipStream_t s) {
   const int fr = q == 1 ? 1 : kPkFrames;
   a.per_xcd = (int)(((int64_t)((a.nt_out + fr - 1) / fr) * L.n_slots + 7) / 8);
   const dim3 grid((unsigned)(8 * a.per_xcd));
-  const size_t lds = (size_t)(kPkPlans[q].P + kPkPlans[q].P / 16 + 1) * sizeof(f2);
-  auto go = [&](auto kern) {
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(q == 1 ? kPk9600Threads : kThreads38), lds, s, a);
-    return hipGetLastError();
-  };
+  const size_t lds = (size_t)(kStaticPlans[q].P + kStaticPlans[q].P / 16 + 1) * sizeof(f2);
+  auto go = [&](auto kern) { return lds_launch(kern, grid, dim3(q == 1 ? kPk9600Threads : kThreads38), lds, s, a); };
   const bool i16 = L.dtype == FT8_I16;
   switch (q) {
     case 0:

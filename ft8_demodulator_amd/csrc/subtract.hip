@@ -21,7 +21,6 @@
 //            summed in record order (deterministic).
 // k_merge    one wave per slot: pass-2 records with a payload not decoded in pass 1 are appended.
 #include <algorithm>
-#include <mutex>
 #include <type_traits>
 
 #include "tx_device.h"
@@ -607,31 +606,9 @@ __global__ __launch_bounds__(kWave) void k_merge(ft8_result* out, int32_t* count
 size_t sub_est_bytes() { return sizeof(SubEst); }
 
 // dynamic LDS above the default 64 KB needs the kernel's attribute raised first (the pulse table is
-// nsps float4s: 61.4 KB at 24 kHz, more above)
-// The attribute is set once per kernel instantiation and device, and again only when a launch needs
-// more than any before it (it was a host-side call per launch); static + dynamic LDS is
-// compared against the 64 KB default, the kernel's static size queried once.
-template <typename K>
-static hipError_t allow_lds(K kern, size_t dyn) {
-  constexpr int kMaxDev = 64;
-  static std::mutex mu;
-  static size_t static_lds[kMaxDev];
-  static size_t granted[kMaxDev];
-  static bool queried[kMaxDev];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
-  std::lock_guard<std::mutex> lk(mu);
-  if (!queried[dev]) {
-    hipFuncAttributes fa{};
-    static_lds[dev] = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern)) == hipSuccess ? fa.sharedSizeBytes : 0;
-    queried[dev] = true;
-  }
-  if (static_lds[dev] + dyn <= 64 * 1024 || dyn <= granted[dev]) return hipSuccess;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-  if (e == hipSuccess) granted[dev] = dyn;
-  return e;
-}
-
+// nsps float4s: 61.4 KB at 24 kHz, more above): every launch below goes through
+// lds_launch, which raises it once per kernel and device and again only when a launch needs more
+// (it was a host-side call per launch)
 hipError_t launch_sub_est(const SubLaunch& a, hipStream_t s) {
   if (a.n_slots <= 0 || a.n_samples <= 0) return hipSuccess;
   if (a.Q <= 0 || a.Q > kMaxQ || a.nsps % a.Q != 0 || a.hop <= 0 || a.nsps % a.hop != 0) return hipErrorInvalidValue;
@@ -646,23 +623,16 @@ hipError_t launch_sub_est(const SubLaunch& a, hipStream_t s) {
     const int D = a.nsps / a.Q;
     const size_t mz = (size_t)z_words(a.Q) + (size_t)((D + 1) & ~1) + (size_t)(2 * kMf + 1) * 8 * (a.Q + 1);
     const size_t lds = std::max(mz * sizeof(float2), (size_t)a.nsps * sizeof(float4));
-    hipError_t e = hipSuccess;
+    const bool rest = a.cap > kSubRecStride;
+    hipError_t e;
     if (a.dtype == FT8_I16) {
-      if ((e = allow_lds(k_sub_est<int16_t, false>, lds)) != hipSuccess) return e;
-      hipLaunchKernelGGL((k_sub_est<int16_t, false>), dim3(grid), dim3(kSubThreads), lds, s, a);
-      if (a.cap > kSubRecStride) {
-        if ((e = allow_lds(k_sub_est<int16_t, true>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((k_sub_est<int16_t, true>), dim3(grid_rest), dim3(kSubThreads), lds, s, a);
-      }
+      e = lds_launch(k_sub_est<int16_t, false>, dim3(grid), dim3(kSubThreads), lds, s, a);
+      if (e == hipSuccess && rest) e = lds_launch(k_sub_est<int16_t, true>, dim3(grid_rest), dim3(kSubThreads), lds, s, a);
     } else {
-      if ((e = allow_lds(k_sub_est<float, false>, lds)) != hipSuccess) return e;
-      hipLaunchKernelGGL((k_sub_est<float, false>), dim3(grid), dim3(kSubThreads), lds, s, a);
-      if (a.cap > kSubRecStride) {
-        if ((e = allow_lds(k_sub_est<float, true>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((k_sub_est<float, true>), dim3(grid_rest), dim3(kSubThreads), lds, s, a);
-      }
+      e = lds_launch(k_sub_est<float, false>, dim3(grid), dim3(kSubThreads), lds, s, a);
+      if (e == hipSuccess && rest) e = lds_launch(k_sub_est<float, true>, dim3(grid_rest), dim3(kSubThreads), lds, s, a);
     }
-    return hipGetLastError();
+    return e;
   }
   return hipSuccess;
 }
@@ -671,15 +641,8 @@ hipError_t launch_sub_apply(const SubLaunch& a, hipStream_t s) {
   if (a.n_slots <= 0 || a.n_samples <= 0) return hipSuccess;
   dim3 g2((unsigned)((a.n_samples + kApTile - 1) / kApTile), (unsigned)a.n_slots);
   const size_t lds2 = (size_t)a.nsps * sizeof(float4) + (size_t)(a.nsps / 8) * sizeof(float);
-  hipError_t e = hipSuccess;
-  if (a.dtype == FT8_I16) {
-    if ((e = allow_lds(k_sub_apply<int16_t>, lds2)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sub_apply<int16_t>, g2, dim3(kApThreads), lds2, s, a);
-  } else {
-    if ((e = allow_lds(k_sub_apply<float>, lds2)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sub_apply<float>, g2, dim3(kApThreads), lds2, s, a);
-  }
-  return hipGetLastError();
+  if (a.dtype == FT8_I16) return lds_launch(k_sub_apply<int16_t>, g2, dim3(kApThreads), lds2, s, a);
+  return lds_launch(k_sub_apply<float>, g2, dim3(kApThreads), lds2, s, a);
 }
 
 hipError_t launch_merge_pass(ft8_result* out, int32_t* counts, int cap, const ft8_result* out1,

@@ -442,16 +442,10 @@ hipError_t launch_score2(const SyncLaunch& L, const ScoreArgs& a0, hipStream_t s
   const size_t lds = sizeof(float) * G::kFloats;
   static_assert(sizeof(float) * S2Geom<4, 4>::kFloats <= 64 * 1024, "one band fits the default LDS limit");
   static_assert(sizeof(float) * G::kFloats <= 160 * 1024, "one band fits the CU's LDS");
-  if constexpr (sizeof(float) * G::kFloats > 64 * 1024) {
-    // (no geometry built today needs it: bpt = sps = 10's band is 30 rows x 200 columns, 24 KB)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_score2<BPT, SPS, COMPACT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
   const int groups = (L.n_slots + 7) / 8;
   const int64_t blocks = (int64_t)groups * 8 * a.n_bands * a.n_ctiles;
-  hipLaunchKernelGGL((k_score2<BPT, SPS, COMPACT>), dim3((unsigned)blocks), dim3(kS2Threads), lds, s, a);
-  return hipGetLastError();
+  // (no geometry built today needs the opt-in: bpt = sps = 10's band is 30 rows x 200 columns, 24 KB)
+  return lds_launch(k_score2<BPT, SPS, COMPACT>, dim3((unsigned)blocks), dim3(kS2Threads), lds, s, a);
 }
 
 bool score2_path(const SyncLaunch& L) {
@@ -1447,13 +1441,7 @@ hipError_t launch_select(const SyncLaunch& L, hipStream_t s) {
     const size_t budget = 79 * 1024;
     const int V = (int)std::max<size_t>(4096, fixed < budget ? (budget - fixed) / sizeof(float) : 0);
     const size_t lds = fixed + (size_t)V * sizeof(float);
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_topkc),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_topkc, dim3(L.n_slots), dim3(kSelThreads), lds, s, a, M, V);
-    return hipGetLastError();
+    return lds_launch(k_topkc, dim3(L.n_slots), dim3(kSelThreads), lds, s, a, M, V);
   }
   if (L.topk) {
     if (L.wf_f64)

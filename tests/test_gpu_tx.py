@@ -247,6 +247,22 @@ def test_subtract_clean_signal_residual(gpu, fs):
     e_sig = float((x.double() ** 2).sum())
     e_res = float((res.double() ** 2).sum())
     assert e_res < 1e-2 * e_sig, e_res / e_sig
+    # the same slot as int16 PCM with 40 candidates (above the 32 fits of the first k_sub_est
+    # launch, so the rest launch runs), on the same context: the int16 kernels ask for no more LDS
+    # than the float32 kernels above were granted, and every kernel needs its own grant
+    pcm = (x / x.abs().max() * 32000).round().to(gpu.int16)
+    dec16 = SlotDecoder(fs, 2, 2, max_candidates=40, min_score=2, flags=_lib.FT8_FLAG_TOPK, context=ctx)
+    out16, counts16 = dec16.run(pcm, _lib.FT8_I16)
+    recs16 = dec16.records(pcm, _lib.FT8_I16)[0]
+    assert len(recs16) >= 1 and bytes(recs16[0]["payload"]) == bytes(pay)
+    res16 = gpu.empty_like(x)
+    p16 = make_params(dec16.plan(N), 40, 2, 20, _lib.FT8_FLAG_TOPK)
+    ctx.check(_lib.lib().ft8_subtract(ctx.handle, _lib.ptr(pcm), _lib.FT8_I16, _lib.ptr(res16), N, 1, N,
+                                      ctypes.byref(p16), _lib.ptr(out16), _lib.ptr(counts16), 40,
+                                      _lib.stream_handle()), "ft8_subtract")
+    e_sig16 = float(((pcm.double() / 32767) ** 2).sum())
+    e_res16 = float((res16.double() ** 2).sum())
+    assert e_res16 < 1e-2 * e_sig16, e_res16 / e_sig16
 
 
 def test_subtract_redecode_crowded(gpu):
