@@ -79,6 +79,14 @@ TX_SIGNAL_DTYPE = np.dtype({
     "itemsize": 40,
 })
 
+# ft8_text (64 bytes)
+TEXT_DTYPE = np.dtype({
+    "names": ["text", "learn_call", "hash", "learn_hash22", "dup_of", "hash_bits", "i3", "n3", "status", "reserved"],
+    "formats": ["S28", "S12", ("<u4", (2,)), "<u4", "<i2", ("u1", (2,)), "u1", "u1", "u1", ("u1", (5,))],
+    "offsets": [0, 28, 40, 48, 52, 54, 56, 57, 58, 59],
+    "itemsize": 64,
+})
+
 _lib = None
 _lock = threading.Lock()
 _tls = threading.local()
@@ -142,6 +150,9 @@ def lib():
             "ft8_stft_method": ([vp, i32, i32, i32, i64, ctypes.c_int], ctypes.c_int),
             "ft8_stft_screen_stats": ([vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], ctypes.c_int),
             "ft8_pack_decodes": ([vp, vp, vp, i32, i32, i32, i32, vp, vp, vp], ctypes.c_int),
+            "ft8_unpack77": ([vp, vp, vp, i32, i32, vp, vp], ctypes.c_int),
+            "ft8_unpack77_host": ([vp, i32, vp], ctypes.c_int),
+            "ft8_hash_call": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
         }
         stale_ok = os.environ.get("FT8HIP_ALLOW_STALE") == "1"
         for name, (args, res) in sig.items():
@@ -163,7 +174,8 @@ def lib():
 
 # csrc files hashed into FT8_BUILD_ID, in the Makefile's ID_FILES order
 _ID_FILES = ("capi.hip", "stft.hip", "stft3840.hip", "sync.hip", "bp.hip", "tx.hip", "subtract.hip", "drift.hip",
-             "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "heap_replay.h", "../../include/ft8hip.h",
+             "msg.hip", "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "heap_replay.h", "msg77.h",
+             "../../include/ft8hip.h",
              "Makefile")
 
 
@@ -189,7 +201,8 @@ EXPORTED_SYMBOLS = (
     "ft8_crc14", "ft8_ldpc_check", "ft8_set_timing", "ft8_get_timing", "ft8_get_counters", "ft8_get_bp_clock", "ft8_set_pipeline",
     "ft8_encode", "ft8_synthesize", "ft8_subtract", "ft8_stft_argmax", "ft8_drift_fit", "ft8_drift_correct",
     "ft8_build_id", "ft8_build_flags", "ft8_replay_stage", "ft8_set_timing_stages", "ft8_sync_score",
-    "ft8_pack_bytes", "ft8_pack_decodes", "ft8_subtract_fits", "ft8_stft_method", "ft8_stft_screen_stats")
+    "ft8_pack_bytes", "ft8_pack_decodes", "ft8_subtract_fits", "ft8_stft_method", "ft8_stft_screen_stats",
+    "ft8_unpack77", "ft8_unpack77_host", "ft8_hash_call")
 
 
 def limits():

@@ -220,6 +220,7 @@ class SlotDecoder:
         self._plans = {}
         self._out = None
         self._counts = None
+        self._text = None
 
     def plan(self, n_samples) -> Plan:
         if n_samples not in self._plans:
@@ -277,6 +278,58 @@ class SlotDecoder:
         x, code, wf_f64 = device_samples(samples, self.device, int16_is_pcm=int16_is_pcm)
         per_slot = self.records(x, code)
         return [records_to_results(r, self.kw["sample_rate"], self.kw["bins_per_tone"], wf_f64) for r in per_slot]
+
+    def _records_and_texts(self, samples, code=None, int16_is_pcm=True):
+        """run(), then one ft8_unpack77 on the same stream with no host sync in between, then the
+        copies: -> (records per slot, ft8_text records per slot), aligned."""
+        import torch
+        out, counts = self.run(samples, code, int16_is_pcm)
+        n_slots = int(counts.shape[0])
+        need = max(n_slots * self.cap * _lib.TEXT_DTYPE.itemsize, 1)
+        if self._text is None or self._text.numel() < need:
+            self._text = torch.empty(need, dtype=torch.uint8, device=out.device)
+        if n_slots and self.cap:
+            rc = _lib.lib().ft8_unpack77(self.ctx.handle, _lib.ptr(out), _lib.ptr(counts), n_slots, self.cap,
+                                         _lib.ptr(self._text), _lib.stream_handle(out.device))
+            self.ctx.check(rc, "ft8_unpack77")
+        c = counts.cpu().numpy()
+        recs = out[: n_slots * self.cap * _lib.RESULT_DTYPE.itemsize].cpu().numpy().view(_lib.RESULT_DTYPE)
+        txts = self._text[: n_slots * self.cap * _lib.TEXT_DTYPE.itemsize].cpu().numpy().view(_lib.TEXT_DTYPE)
+        recs, txts = recs.reshape(n_slots, self.cap), txts.reshape(n_slots, self.cap)
+        warn_truncated(c, self.cap, stacklevel=4)
+        keep = [min(int(c[s]), self.cap) for s in range(n_slots)]
+        return ([recs[s, :k].copy() for s, k in enumerate(keep)], [txts[s, :k].copy() for s, k in enumerate(keep)])
+
+    def texts(self, samples, code=None, int16_is_pcm=True):
+        """Synchronous: -> list (per slot) of ft8_text arrays (_lib.TEXT_DTYPE) aligned with records():
+        the message text of every decode, unpacked on the device (ft8_unpack77), and dup_of, the
+        slot's first record with the same payload."""
+        return self._records_and_texts(samples, code, int16_is_pcm)[1]
+
+    def messages(self, samples, table=None, unique=True, int16_is_pcm=True):
+        """-> list (per slot) of (text, time_s, freq_hz, score, record) for every decode whose message
+        type is unpacked (ft8_text.status 0), in candidate order; time, frequency and score as decode()
+        gives them.  unique drops the records whose payload an earlier record of the slot carries.
+        table (message.CallsignTable): hashed callsigns it knows are written <CALL>; slots are
+        handled in order, and within a slot every record is resolved before the slot is learned."""
+        from .message import text_of
+        x, code, wf_f64 = device_samples(samples, self.device, int16_is_pcm=int16_is_pcm)
+        recs, txts = self._records_and_texts(x, code)
+        fs, bpt = self.kw["sample_rate"], self.kw["bins_per_tone"]
+        out = []
+        for r, t in zip(recs, txts):
+            sc = r["score"].astype(np.float64 if wf_f64 else np.float32)
+            rows = []
+            for i in range(len(r)):
+                if int(t["status"][i]) != 0 or (unique and int(t["dup_of"][i]) >= 0):
+                    continue
+                text = table.resolve(t[i]) if table is not None else text_of(t[i])
+                rows.append((text, int(r["abs_time"][i]) / fs,
+                             (int(r["abs_freq"][i]) / bpt) * FT8_SYMBOL_FREQ_INTERVAL_HZ, sc[i], r[i]))
+            if table is not None:
+                table.learn(t)
+            out.append(rows)
+        return out
 
     def timing(self, reset=False):
         return self.ctx.timing(reset)

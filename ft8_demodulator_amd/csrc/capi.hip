@@ -1548,6 +1548,19 @@ int ft8_pack_decodes(ft8_ctx* c, const ft8_result* d_records, const int32_t* d_c
   return e == hipSuccess ? FT8_OK : hipfail(c, e, "pack launch");
 }
 
+// like ft8_pack_decodes it touches no context state, so it takes no part in the StreamOrder
+int ft8_unpack77(ft8_ctx* c, const ft8_result* d_records, const int32_t* d_counts, int32_t n_slots, int32_t cap,
+                 ft8_text* d_out, void* stream) {
+  if (!c || n_slots < 0 || cap < 0) return fail(c, FT8_E_ARG, "bad argument");
+  if (cap > INT16_MAX) return fail(c, FT8_E_RANGE, "cap exceeds 32767 (ft8_text.dup_of is 16 bits)");
+  if (n_slots > 0 && cap > 0 && (!d_records || !d_out)) return fail(c, FT8_E_ARG, "null records or output");
+  if (((uintptr_t)d_records & 7) || ((uintptr_t)d_out & 3) || ((uintptr_t)d_counts & 3))
+    return fail(c, FT8_E_ARG, "records must be 8-byte, text records and counts 4-byte aligned");
+  DeviceGuard dg(c->device);
+  hipError_t e = launch_unpack77(d_records, d_counts, n_slots, cap, d_out, (hipStream_t)stream);
+  return e == hipSuccess ? FT8_OK : hipfail(c, e, "unpack77 launch");
+}
+
 int ft8_select_warnings(ft8_ctx* c, int32_t* d_out, int32_t n_slots, void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
   if (!c || !d_out || n_slots < 0) return fail(c, FT8_E_ARG, "bad argument");

@@ -287,6 +287,10 @@ inline __host__ __device__ int64_t pack_header_bytes(int n_slots) { return 8 + (
 hipError_t launch_pack(const ft8_result* rec, const int32_t* counts, int n_slots, int cap, int capacity,
                        int slot_offset, uint8_t* send, ft8_result* overflow, hipStream_t s);
 
+// ft8_unpack77 (msg.hip): records [n_slots][cap] -> text records, one workgroup per slot
+hipError_t launch_unpack77(const ft8_result* rec, const int32_t* counts, int n_slots, int cap, ft8_text* out,
+                           hipStream_t s);
+
 // ---- transmit chain + subtraction (tx.hip, subtract.hip) -------------------------------------
 struct SynthLaunch {
   const uint8_t* tones;        // [n_sig][79]

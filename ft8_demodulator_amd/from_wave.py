@@ -88,10 +88,15 @@ def decode_ft8_from_wave(wave_path: str, freq_min: float = None, freq_max: float
                               device=device)
 
 
-def _print_results(results):
+def _print_results(results, text: bool = False):
+    """text: one extra `Message:` line per result, the payload unpacked to message text."""
     if not results:
         print("No FT8 messages decoded")
         return
+    if text:
+        from .message import text_of, unpack77
+        texts = [text_of(t) if int(t["status"]) == 0 else f"(not decoded: status {int(t['status'])})"
+                 for t in unpack77([bytes(r[0].payload) for r in results])]
     print("\nDecoded FT8 messages:")
     print("-" * 50)
     for message, status, time_sec, freq_hz, score in results:
@@ -99,6 +104,8 @@ def _print_results(results):
         print(f"Frequency: {freq_hz:.1f} Hz")
         print(f"Score: {score:.1f}")
         print(f"Payload: {message.payload.hex()}")
+        if text:
+            print(f"Message: {texts.pop(0)}")
         print(f"CRC check: {status.crc_calculated}")
         print(f"LDPC errors: {status.ldpc_errors}")
         print("-" * 50)
@@ -141,6 +148,7 @@ def main(argv=None):
     parser.add_argument("--min-score", type=float, default=10)
     parser.add_argument("--max-iterations", type=int, default=20)
     parser.add_argument("--correction", type=bool, default=False)
+    parser.add_argument("--text", action="store_true", help="print each payload's message text as well")
     args = parser.parse_args(argv)
     for path in args.wave_file:
         if not os.path.exists(path):
@@ -150,7 +158,7 @@ def main(argv=None):
         per_file = _decode_many(args)
         for path, results in zip(args.wave_file, per_file):
             print(f"\n== {path}")
-            _print_results(results)
+            _print_results(results, args.text)
         return per_file
     args.wave_file = args.wave_file[0]
     results = decode_ft8_from_wave(args.wave_file, freq_min=args.freq_min, freq_max=args.freq_max,
@@ -158,7 +166,7 @@ def main(argv=None):
                                    bins_per_tone=args.bins_per_tone, steps_per_symbol=args.steps_per_symbol,
                                    max_candidates=args.max_candidates, min_score=args.min_score,
                                    max_iterations=args.max_iterations, correction=args.correction)
-    _print_results(results)
+    _print_results(results, args.text)
     return results
 
 

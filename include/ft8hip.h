@@ -236,6 +236,42 @@ int ft8_pack_decodes(ft8_ctx* ctx, const ft8_result* d_records, const int32_t* d
                      int32_t cap, int32_t capacity, int32_t slot_offset, void* d_send, ft8_result* d_overflow,
                      void* stream);
 
+/* ---- message layer: 77-bit payload -> text -----------------------------------------------------
+ * Build-defined, outside reference parity (the reference stops at the payload).  The FT8 message
+ * types unpacked are the standard message (i3 = 1, 2), the message with one non-standard callsign
+ * (i3 = 4), free text (i3 = 0, n3 = 0) and telemetry (i3 = 0, n3 = 5); field layouts in DESIGN.md.
+ * One text record per ft8_result, 64 bytes. */
+typedef struct ft8_text {
+  char     text[28];      /* NUL-padded ASCII, at most 26 characters; hashed calls as "<...>" */
+  char     learn_call[12];/* the callsign carried in full that a receiver adds to its hash table: i3=4 the c58 call;
+                             i3=1/2 the second callsign without /R,/P when it is a standard callsign; else empty */
+  uint32_t hash[2];       /* value of the first / second "<...>" in text, left to right */
+  uint32_t learn_hash22;  /* n22 of learn_call (0 when empty) */
+  int16_t  dup_of;        /* index within the slot of the first ok record with the same 77 bits, -1 if this is it */
+  uint8_t  hash_bits[2];  /* 0, 12 or 22 for each entry of hash[] */
+  uint8_t  i3, n3;        /* n3 is 0 unless i3 == 0 */
+  uint8_t  status;        /* 0 text valid; 1 type not decoded; 2 a field out of range; 3 record not ok (not unpacked) */
+  uint8_t  reserved[5];
+} ft8_text;
+
+/* Text records of a ft8_decode_batch's output (d_records[n_slots][cap], d_counts[n_slots] as that
+ * call wrote them; d_counts NULL: every slot holds cap records): d_out[s * cap + r] is written for
+ * every r < cap.  Records at r >= min(d_counts[s], cap) and records with ok == 0 get status 3,
+ * dup_of -1 and zeros elsewhere, and never serve as a duplicate's original.  Records with status 1
+ * or 2 carry i3 / n3 and zeros elsewhere.  dup_of compares the 77 payload bits ([9] & 0xF8) with
+ * the slot's earlier records.  cap <= 32767.  One kernel on the caller's stream; it uses none of the
+ * context's scratch and allocates nothing, so like ft8_pack_decodes it takes no part in the
+ * context's cross-stream order: call it on the stream that produced d_records (or after an event
+ * of it). */
+int ft8_unpack77(ft8_ctx* ctx, const ft8_result* d_records, const int32_t* d_counts, int32_t n_slots,
+                 int32_t cap, ft8_text* d_out, void* stream);
+/* The same unpacker on the host for n payloads[n][10] in host memory: no context, no GPU.
+ * dup_of = -1 throughout. */
+int ft8_unpack77_host(const uint8_t* payloads, int32_t n, ft8_text* out);
+/* Host: the 22-bit hash of a callsign (n12 = n22 >> 10, n10 = n22 >> 12).  FT8_E_ARG for a
+ * character outside " 0-9A-Z/" or a length above 11. */
+int ft8_hash_call(const char* call, uint32_t* n22);
+
 /* Per-slot flags of the last selection (copied device->device into d_out[n_slots]):
  * bit 0: an exact score tie reached a heap comparison (the reference raises TypeError there,
  *        ftx_types.py:37-47; here ties are ordered by scan index), bit 1: unused (0), bit 2
