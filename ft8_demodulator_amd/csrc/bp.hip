@@ -11,11 +11,13 @@
 //   normalise    ftx_normalize_logl (ft8_decode.py:190-198): mean and variance reproduce NumPy's
 //                pairwise summation order exactly (8 accumulators, blocks of 80 + 94) and
 //                sqrt(24/var) is correctly rounded, so LLRs are bit-identical to the reference.
-//   BP           bp_decode (ldpc_decoder.py:54-113) in float64, edge-parallel: the 522 Tanner-graph
-//                edges are dealt to lanes (9 per lane); variable->check and check->variable
-//                messages live in LDS (one 4.6 KB array, see WaveLds) and every sum/product is evaluated in
-//                the reference's order, without FMA contraction (-ffp-contract=off), so hard
-//                decisions match bit for bit.
+//   BP           bp_decode (ldpc_decoder.py:54-113) in float64: the 522 Tanner-graph edges are dealt
+//                to lanes, 9 per lane (variable-major: three variables' edges; check-major: the
+//                seven edges of the lane's own check, whose products share their left-to-right
+//                prefixes in one lane's registers, plus two edges of the 19 leftover checks);
+//                variable->check and check->variable messages live in LDS (one 4.6 KB array, see
+//                WaveLds) and every sum/product is evaluated in the reference's order, without FMA
+//                contraction (-ffp-contract=off), so hard decisions match bit for bit.
 //   CRC          pack_bits + extract_crc + compute_crc (ft8_decode.py:200-273, crc.py:11-54).
 //
 // Roofline: the kernel touches < 2 KB of HBM per candidate; it is bound by float64 VALU issue
@@ -41,18 +43,16 @@ constexpr int kChkSlots = (FT8_LDPC_M + kWave - 1) / kWave;   // 2
 
 // Fixed kernel shape (round 3: the build-time experiment switches of round 2 are gone; DESIGN.md
 // section 3 lists what each alternative measured, and the fault one of them caused).  Divisions are
-// interleaved three at a time: a variable's three edges, and the nine edge slots of the edge-major
-// phase in three groups.  A group size that does not divide kEdgeSlots indexes past the lane's
-// register arrays -- undefined behaviour, which the compiler answers by deleting the divisions -- so
-// it is pinned and asserted here.
+// interleaved three at a time: a variable's three edges, and the nine products of phase D (seven of
+// the lane's own check, two leftover edges) in three groups.  A group size that does not divide
+// kEdgeSlots indexes past the lane's register arrays -- undefined behaviour, which the compiler
+// answers by deleting the divisions -- so it is pinned and asserted here.
 constexpr int kDivGroup = 3;
 static_assert(kEdgeSlots % kDivGroup == 0 && kVarSlots == kDivGroup, "division groups tile the slots exactly");
-constexpr int kProdGroup = 3;  // check products between scheduling fences (register pressure)
-static_assert(kEdgeSlots % kProdGroup == 0, "product groups tile the edge slots");
 // Resident waves per SIMD the persistent grid is sized for.  The compiler is given a 3-wave register
 // budget: under a 4-wave budget (128 VGPRs) the allocator spills ~50 VGPRs of the fused sweep to
-// scratch, while under the 3-wave budget it needs only 123 -- which still leaves 4 waves resident
-// per SIMD (512 / 128).
+// scratch, while under the 3-wave budget it needs only 111 (117 NaN-safe; 123 before phase D went
+// check-major) -- which still leaves 4 waves resident per SIMD (512 / 128).
 constexpr int kBpWavesPerSimd = 4;
 constexpr int kBpLbWaves = 3;
 constexpr int kBpGridCus = 256;        // MI355X: 256 CUs
@@ -201,29 +201,67 @@ __device__ __forceinline__ void div_rn(double* q, const double* x, const double*
 // 1.0 that stands in for a degree-6 row's missing seventh factor (1.0 * t == t exactly).  Hence:
 //   * factor f of row m' sits at byte 8 m' + 664 f from the array: a row base plus a compile-time
 //     immediate, so the check products need no per-factor address arithmetic;
-//   * edge-major phases (fast_tanh, products, fast_atanh) own index lane + 64 i: the lane address
-//     plus an immediate;
-//   * edge slot i (indices 64 i .. 64 i + 63) holds one row position q, or two adjacent ones qa and
-//     qa + 1 (83 > 64).  The product of "every factor but q" in row order then has, at chain
-//     position qa, t[qa + 1] for the q = qa lanes and t[qa] for the q = qa + 1 lanes -- one
-//     per-lane address; every other factor is common to both groups.
+//   * phase D is check-major for rows m' = 0..63: lane L owns row L, reads its seven factors once
+//     (lane address + 664 f; for L >= 24 the seventh is a constant 1.0 at 498 + L <= 561) and forms
+//     all seven "every factor but q" products from shared left-to-right prefixes;
+//   * the 19 leftover rows m' = 64..82 (all degree 6) are edge-major on two more register slots:
+//     lane 19 q3 + r (q3 < 3, r < 19) owns edges (64 + r, q3) and (64 + r, 3 + q3).  The product of
+//     "every factor but q" over q = q3 of the three lane groups differs only at chain positions 0
+//     and 1 (slot A; 3 and 4 for slot B): t[1] or t[0], then t[1] or t[2] -- two per-lane addresses,
+//     the same two for both slots up to the immediate 3 * 664; every other factor is row base plus
+//     immediate.  Lanes 57..63 repeat the q3 = 2 reads of rows 64..70 and store nothing;
+//   * the tov zeroing owns index lane + 64 i: the lane address plus an immediate.
 // The per-variable (174 x 3 edge) addresses of the variable-major phase are per-lane tables.
 constexpr int kM7 = 24;                              // degree-7 checks (FT8 LDPC(174,91))
 constexpr int kQS = FT8_LDPC_M;                      // index stride of one row position (83)
 constexpr int kQ6 = 6 * kQS;                         // first index of row position 6 (498)
 constexpr int kMsgN = 584;                           // 498 + 83 = 581 used, rounded to 8
 constexpr int kOne = kMsgN - 1;                      // a constant 1.0 (padding variables read it)
-constexpr int kHdr = 1024;                           // LDS bytes before msg (lane addr - 664 > 0)
+constexpr int kHdr = 1024;                           // LDS bytes before msg (the header of WaveLds)
 static_assert(kEdgeSlots * kWave <= kMsgN && kQ6 + kM7 == FT8_LDPC_E, "row-major message layout");
 
-__host__ __device__ constexpr int q_of(int idx) { return idx < kQ6 ? idx / kQS : 6; }
-__host__ __device__ constexpr int qa_of(int i) { return q_of(kWave * i); }
-__host__ __device__ constexpr bool mixed_slot(int i) { return q_of(kWave * i + kWave - 1) != q_of(kWave * i); }
-// first lane of slot i whose row position is qa + 1 (mixed slots)
-__host__ __device__ constexpr int hi_lane(int i) { return kQS * (qa_of(i) + 1) - kWave * i; }
-// byte offset, from a lane's row base register, of the row base itself for slot i's lanes
-// (index of factor 0 of the lane's row = lane + 64 i - 83 q)
-__host__ __device__ constexpr int row_off(int i) { return 8 * (kWave * i - kQS * qa_of(i)); }
+// Phase D's lane mapping (see above): rows 0..kWave-1 check-major, kLeftRows leftover rows edge-major
+constexpr int kLeftRows = FT8_LDPC_M - kWave;        // 19 rows, m' = 64..82
+constexpr int kLeftLanes = 3 * kLeftRows;            // 57 lanes own two leftover edges each
+constexpr int kRowB = 8 * kQS;                       // byte stride of one row position (664)
+static_assert(kWave + kLeftRows == FT8_LDPC_M && kLeftRows == 19, "64 + 19 rows");
+static_assert(kM7 <= kWave, "every leftover row has degree 6");
+static_assert(kLeftLanes <= kWave, "3 x 19 leftover lanes fit the wave");
+static_assert(kQ6 + kWave - 1 < kMsgN, "a check-major lane's seventh factor is a message or a constant");
+static_assert(kEdgeSlots == 7 + 2, "seven check-major products and two leftover ones per lane");
+// the lane -> (q3, r) split of the leftover slots; idle lanes (>= kLeftLanes) fold onto q3 = 2
+__host__ __device__ constexpr int left_q3(int lane) { return lane / kLeftRows < 3 ? lane / kLeftRows : 2; }
+__host__ __device__ constexpr int left_r(int lane) { return lane % kLeftRows; }
+// row position whose factor stands at the two lane-dependent chain positions of slot A (+ 3: slot B)
+__host__ __device__ constexpr int left_f0(int q3) { return q3 == 0 ? 1 : 0; }
+__host__ __device__ constexpr int left_f1(int q3) { return q3 == 2 ? 1 : 2; }
+__host__ __device__ constexpr int msg_idx(int q, int mp) { return q * kQS + mp; }  // q = 6: 498 + m'
+// The mapping as a model: every index phase D reads lies inside msg, each of a leftover edge's five
+// factors is read exactly once and its own never, and the stores cover the 522 edges exactly once.
+__host__ __device__ constexpr bool phase_d_mapping_ok() {
+  int stores[kMsgN] = {};
+  for (int lane = 0; lane < kWave; ++lane) {
+    for (int f = 0; f < 7; ++f) {
+      if (msg_idx(f, lane) >= kMsgN) return false;                  // read
+      if (f < 6 || lane < kM7) stores[msg_idx(f, lane)]++;           // store
+    }
+    const int q3 = left_q3(lane), row = kWave + left_r(lane);
+    for (int s = 0; s < 2; ++s) {
+      const int fs[5] = {3 * s + left_f0(q3), 3 * s + left_f1(q3), 3 * (1 - s), 3 * (1 - s) + 1, 3 * (1 - s) + 2};
+      int seen = 0;
+      for (int k = 0; k < 5; ++k) {
+        if (fs[k] < 0 || fs[k] > 5 || row >= FT8_LDPC_M || msg_idx(fs[k], row) >= kQ6) return false;
+        seen |= 1 << fs[k];
+      }
+      if (seen != (0x3f & ~(1 << (3 * s + q3)))) return false;      // every factor but the edge's own
+      if (lane < kLeftLanes) stores[msg_idx(3 * s + q3, row)]++;
+    }
+  }
+  for (int x = 0; x < kMsgN; ++x)
+    if (stores[x] != (x < FT8_LDPC_E ? 1 : 0)) return false;        // never the constants
+  return true;
+}
+static_assert(phase_d_mapping_ok(), "phase D reads inside msg and produces every edge exactly once");
 
 struct WaveLds {
   uint8_t bits[256];               // hard decision of every variable (written once per candidate)
@@ -715,38 +753,59 @@ __device__ __forceinline__ void atanh_group(double* v, int fast = 0) {
   div_rn<kDivGroup, true>(v, na, nb, fast);
 }
 
-// Phase D's products: for each of the lane's edge slots, the product of the other toc of the edge's
-// check in row order, from 1.0 (1.0 * t0 == t0, so the product starts at the first factor).
-__device__ __forceinline__ void check_products(double* x, uint32_t la, int lane) {
+// Per-lane LDS byte addresses of the leftover slots (registers, built once per wave): the lane's row
+// base, the factors at its two lane-dependent chain positions, and its slot A edge (slot B: + 3 rows)
+struct LeftAddr {
+  uint32_t rb, f0, f1, st;
+};
+
+__device__ __forceinline__ LeftAddr left_addr(uint32_t msg0, int lane) {
+  const int q3 = left_q3(lane);
+  LeftAddr a;
+  a.rb = msg0 + 8u * (uint32_t)(kWave + left_r(lane));
+  a.f0 = a.rb + (uint32_t)(kRowB * left_f0(q3));
+  a.f1 = a.rb + (uint32_t)(kRowB * left_f1(q3));
+  a.st = a.rb + (uint32_t)(kRowB * q3);
+  return a;
+}
+
+// Phase D's products of the lane's own check (row m' = lane): x[q] = the product of the check's toc
+// but t[q], left to right from 1.0 as the reference forms it (ldpc_decoder.py:104-107; 1.0 * t0 == t0,
+// so a chain starts at its first factor).  Edges q >= 2 share the prefix (..(t0 t1)..) t[q-1] bit for
+// bit: 7 reads and 25 multiplies instead of 42 and 35.  A degree-6 row's t[6] is the constant 1.0
+// (p * 1.0 == p) and its x[6] is never stored.
+__device__ __forceinline__ void row_products(double* x, uint32_t la) {
+  double t[7];
 #pragma unroll
-  for (int i = 0; i < kEdgeSlots; ++i) {
-    const int qa = qa_of(i);
-    const bool mx = mixed_slot(i);
-    const bool hi = mx && lane >= hi_lane(i);
-    // row base of the lane (factor 0 of its row): la + row_off(i) for q = qa, 664 less for qa + 1
-    const uint32_t rb = hi ? la - 664u : la;
-    double p = 0.0;
-    bool first = true;
+  for (int f = 0; f < 7; ++f) t[f] = ldv(la + (uint32_t)(kRowB * f));
+  double p = t[1];  // x[0]: no prefix
 #pragma unroll
-    for (int f = 0; f < 7; ++f) {
-      double t;
-      if (mx && f == qa) {        // t[qa + 1] (q = qa lanes) or t[qa] (q = qa + 1 lanes)
-        const uint32_t pa = hi ? rb : rb + 664u;
-        t = ldv(pa + (uint32_t)(row_off(i) + 664 * qa));
-      } else if (mx && f == qa + 1) {
-        continue;
-      } else if (!mx && f == qa) {
-        continue;
-      } else {
-        t = ldv(rb + (uint32_t)(row_off(i) + 664 * f));
-      }
-      p = first ? t : p * t;
-      first = false;
-    }
-    x[i] = p;
-    // bound how far the scheduler hoists these loads (register pressure)
-    if (i % kProdGroup == kProdGroup - 1) asm volatile("" ::: "memory");
+  for (int f = 2; f < 7; ++f) p *= t[f];
+  x[0] = p;
+  double pre = t[0];  // t0 .. t[q-1]
+#pragma unroll
+  for (int q = 1; q < 7; ++q) {
+    p = pre;
+#pragma unroll
+    for (int f = q + 1; f < 7; ++f) p *= t[f];
+    x[q] = p;
+    pre *= t[q];
   }
+}
+
+// Phase D's products of the lane's two leftover edges (row 64 + r, positions q3 and 3 + q3): the
+// five other factors of the degree-6 row in row order, no 1.0 pad: 5 reads and 4 multiplies each
+__device__ __forceinline__ void left_products(double* x, const LeftAddr& a) {
+  double p = ldv(a.f0) * ldv(a.f1);  // slot A: (t1 | t0) (t1 | t2) t3 t4 t5
+#pragma unroll
+  for (int f = 3; f < 6; ++f) p *= ldv(a.rb + (uint32_t)(kRowB * f));
+  x[0] = p;
+  p = ldv(a.rb);                     // slot B: t0 t1 t2 (t4 | t3) (t4 | t5)
+#pragma unroll
+  for (int f = 1; f < 3; ++f) p *= ldv(a.rb + (uint32_t)(kRowB * f));
+  p *= ldv(a.f0 + (uint32_t)(kRowB * 3));
+  p *= ldv(a.f1 + (uint32_t)(kRowB * 3));
+  x[1] = p;
 }
 
 // ---- k_bp: persistent waves, one candidate at a time ----------------------------------------------
@@ -763,10 +822,12 @@ __global__ __launch_bounds__(kWave, kBpLbWaves) void k_bp(BpArgs a) {
   // padding variables (variable slot 2, lanes >= 46) never store their V->C arguments
   const bool var2 = lane + kWave * (kVarSlots - 1) < FT8_LDPC_N;
   const uint64_t var2_mask = (1ull << (FT8_LDPC_N - kWave * (kVarSlots - 1))) - 1ull;
-  // the lane's message address in the edge-major phases (slot i: + 512 i) and the row-base
-  // registers of the two lane groups of a mixed slot (q = qa: la, q = qa + 1: la - 664)
+  // the lane's message address: the row base of its own check in phase D (factor f: + 664 f) and
+  // its slot of the tov zeroing (slot i: + 512 i); and the addresses of its two leftover edges
   uint32_t la = lds_addr(&L.msg[0]) + 8u * (uint32_t)lane;
   asm volatile("" : "+v"(la));  // one register (the generic->LDS cast carries a null test)
+  LeftAddr lf = left_addr(la - 8u * (uint32_t)lane, lane);
+  asm volatile("" : "+v"(lf.rb), "+v"(lf.f0), "+v"(lf.f1), "+v"(lf.st));
 
   // work counters, per wave; flushed once when the wave retires (same-address atomics per
   // candidate would serialise in L2)
@@ -817,8 +878,8 @@ __global__ __launch_bounds__(kWave, kBpLbWaves) void k_bp(BpArgs a) {
     // three tov, forms the hard decision c + ((t0 + t1) + t2) (a wave ballot per variable slot)
     // and the three clipped variable->check sums (c + t_a) + t_b in registers; (B) parity of every
     // check from the ballots; (C) fast_tanh of those registers, a variable's three edges being one
-    // division group, toc stored into each edge's slot; (D) edge-major: check products ->
-    // fast_atanh -> tov.  The first sweep (all tov 0) evaluates fast_tanh once per variable; the
+    // division group, toc stored into each edge's slot; (D) check-major (the lane's own check, then
+    // two edges of the leftover checks): check products -> fast_atanh -> tov.  The first sweep (all tov 0) evaluates fast_tanh once per variable; the
     // last one stops after (B), its message update being unread.
     // tov = 0 on every real edge (indices 0..521; the constants above never change)
 #pragma unroll
@@ -932,13 +993,20 @@ __global__ __launch_bounds__(kWave, kBpLbWaves) void k_bp(BpArgs a) {
       sweep_sync();
       double x[kEdgeSlots];
       // (D) check -> variable messages: tov = -2 fast_atanh(product of the other toc of the check)
-      check_products(x, la, lane);
+      // x[0..6]: the lane's own check, x[7..8]: its two leftover edges; all reads precede the stores
+      row_products(x, la);
+      left_products(&x[7], lf);
 #pragma unroll
       for (int g = 0; g < kEdgeSlots; g += kDivGroup) atanh_group(&x[g], fast);
 #pragma unroll
-      for (int i = 0; i < kEdgeSlots; ++i)
-        if (i < kEdgeSlots - 1 || lane + kWave * i < FT8_LDPC_E)
-          *(__attribute__((address_space(3))) double*)(uintptr_t)(la + 512u * i) = x[i];
+      for (int f = 0; f < 6; ++f)
+        *(__attribute__((address_space(3))) double*)(uintptr_t)(la + (uint32_t)(kRowB * f)) = x[f];
+      if (lane < kM7)  // rows >= 24 have a constant 1.0 there
+        *(__attribute__((address_space(3))) double*)(uintptr_t)(la + (uint32_t)(kRowB * 6)) = x[6];
+      if (lane < kLeftLanes) {
+        *(__attribute__((address_space(3))) double*)(uintptr_t)lf.st = x[7];
+        *(__attribute__((address_space(3))) double*)(uintptr_t)(lf.st + (uint32_t)(kRowB * 3)) = x[8];
+      }
       passes++;
       sweep_sync();
     }
