@@ -87,6 +87,14 @@ TEXT_DTYPE = np.dtype({
     "itemsize": 64,
 })
 
+# ft8_snr_rec (24 bytes)
+SNR_DTYPE = np.dtype({
+    "names": ["snr_db", "signal_db", "noise_db", "dt", "df", "n_symbols", "status", "reserved"],
+    "formats": ["<f8", "<f4", "<f4", "i1", "i1", "u1", "u1", ("u1", (4,))],
+    "offsets": [0, 8, 12, 16, 17, 18, 19, 20],
+    "itemsize": 24,
+})
+
 _lib = None
 _lock = threading.Lock()
 _tls = threading.local()
@@ -153,6 +161,9 @@ def lib():
             "ft8_unpack77": ([vp, vp, vp, i32, i32, vp, vp], ctypes.c_int),
             "ft8_unpack77_host": ([vp, i32, vp], ctypes.c_int),
             "ft8_hash_call": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+            "ft8_noise_floor": ([vp, vp, ctypes.c_int, i32, i32, i32, dbl, vp, vp, vp], ctypes.c_int),
+            "ft8_snr": ([vp, vp, ctypes.c_int, i32, i32, i32, P, i64, vp, vp, i32, vp, i32, vp, vp], ctypes.c_int),
+            "ft8_snr_last": ([vp, vp, vp, i32, i32, vp, vp], ctypes.c_int),
         }
         stale_ok = os.environ.get("FT8HIP_ALLOW_STALE") == "1"
         for name, (args, res) in sig.items():
@@ -174,7 +185,7 @@ def lib():
 
 # csrc files hashed into FT8_BUILD_ID, in the Makefile's ID_FILES order
 _ID_FILES = ("capi.hip", "stft.hip", "stft3840.hip", "sync.hip", "bp.hip", "tx.hip", "subtract.hip", "drift.hip",
-             "msg.hip", "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "heap_replay.h", "msg77.h",
+             "msg.hip", "snr.hip", "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "heap_replay.h", "msg77.h",
              "../../include/ft8hip.h",
              "Makefile")
 
@@ -202,7 +213,7 @@ EXPORTED_SYMBOLS = (
     "ft8_encode", "ft8_synthesize", "ft8_subtract", "ft8_stft_argmax", "ft8_drift_fit", "ft8_drift_correct",
     "ft8_build_id", "ft8_build_flags", "ft8_replay_stage", "ft8_set_timing_stages", "ft8_sync_score",
     "ft8_pack_bytes", "ft8_pack_decodes", "ft8_subtract_fits", "ft8_stft_method", "ft8_stft_screen_stats",
-    "ft8_unpack77", "ft8_unpack77_host", "ft8_hash_call")
+    "ft8_unpack77", "ft8_unpack77_host", "ft8_hash_call", "ft8_noise_floor", "ft8_snr", "ft8_snr_last")
 
 
 def limits():

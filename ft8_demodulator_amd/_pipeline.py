@@ -221,6 +221,8 @@ class SlotDecoder:
         self._out = None
         self._counts = None
         self._text = None
+        self._snr = None
+        self._launched = False  # whether the last run() reached ft8_decode_batch (else: nothing to decode)
 
     def plan(self, n_samples) -> Plan:
         if n_samples not in self._plans:
@@ -253,6 +255,7 @@ class SlotDecoder:
         n_slots, n = int(x.shape[0]), int(x.shape[1])
         out, counts = self._buffers(n_slots)
         plan = self.plan(n)
+        self._launched = False
         if plan.empty or n_slots == 0:
             counts[:n_slots].zero_()
             return out, counts[:n_slots]
@@ -261,6 +264,7 @@ class SlotDecoder:
                                          ctypes.byref(p), _lib.ptr(out), _lib.ptr(counts), self.cap,
                                          _lib.stream_handle(torch.device("cuda", self.device)))
         self.ctx.check(rc, "ft8_decode_batch")
+        self._launched = True
         return out, counts[:n_slots]
 
     def records(self, samples, code=None, int16_is_pcm=True):
@@ -279,9 +283,29 @@ class SlotDecoder:
         per_slot = self.records(x, code)
         return [records_to_results(r, self.kw["sample_rate"], self.kw["bins_per_tone"], wf_f64) for r in per_slot]
 
-    def _records_and_texts(self, samples, code=None, int16_is_pcm=True):
-        """run(), then one ft8_unpack77 on the same stream with no host sync in between, then the
-        copies: -> (records per slot, ft8_text records per slot), aligned."""
+    def _snr_last(self, out, counts):
+        """ft8_snr_last for the records run() just wrote, on the same stream: -> the device buffer of
+        n_slots * cap ft8_snr_rec.  A run() that had nothing to decode (an empty plan: no waterfall)
+        gives every record status 3, as the library does for records past a slot's count."""
+        import torch
+        n_slots = int(counts.shape[0])
+        nbytes = n_slots * self.cap * _lib.SNR_DTYPE.itemsize
+        if self._snr is None or self._snr.numel() < max(nbytes, 1):
+            self._snr = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=out.device)
+        if not self._launched:
+            blank = np.zeros(n_slots * self.cap, dtype=_lib.SNR_DTYPE)
+            blank["status"] = 3
+            self._snr[:nbytes].copy_(torch.from_numpy(blank.view(np.uint8)))
+        elif n_slots and self.cap:
+            rc = _lib.lib().ft8_snr_last(self.ctx.handle, _lib.ptr(out), _lib.ptr(counts), n_slots, self.cap,
+                                         _lib.ptr(self._snr), _lib.stream_handle(out.device))
+            self.ctx.check(rc, "ft8_snr_last")
+        return self._snr
+
+    def _records_and_texts(self, samples, code=None, int16_is_pcm=True, snr=False, stacklevel=4):
+        """run(), then one ft8_unpack77 (and, with snr, one ft8_snr_last) on the same stream with no
+        host sync in between, then the copies: -> (records per slot, ft8_text records per slot[,
+        ft8_snr_rec records per slot]), aligned."""
         import torch
         out, counts = self.run(samples, code, int16_is_pcm)
         n_slots = int(counts.shape[0])
@@ -292,13 +316,20 @@ class SlotDecoder:
             rc = _lib.lib().ft8_unpack77(self.ctx.handle, _lib.ptr(out), _lib.ptr(counts), n_slots, self.cap,
                                          _lib.ptr(self._text), _lib.stream_handle(out.device))
             self.ctx.check(rc, "ft8_unpack77")
+        if snr:
+            d_snr = self._snr_last(out, counts)
         c = counts.cpu().numpy()
         recs = out[: n_slots * self.cap * _lib.RESULT_DTYPE.itemsize].cpu().numpy().view(_lib.RESULT_DTYPE)
         txts = self._text[: n_slots * self.cap * _lib.TEXT_DTYPE.itemsize].cpu().numpy().view(_lib.TEXT_DTYPE)
         recs, txts = recs.reshape(n_slots, self.cap), txts.reshape(n_slots, self.cap)
-        warn_truncated(c, self.cap, stacklevel=4)
+        warn_truncated(c, self.cap, stacklevel=stacklevel)
         keep = [min(int(c[s]), self.cap) for s in range(n_slots)]
-        return ([recs[s, :k].copy() for s, k in enumerate(keep)], [txts[s, :k].copy() for s, k in enumerate(keep)])
+        res = ([recs[s, :k].copy() for s, k in enumerate(keep)], [txts[s, :k].copy() for s, k in enumerate(keep)])
+        if snr:
+            reps = d_snr[: n_slots * self.cap * _lib.SNR_DTYPE.itemsize].cpu().numpy().view(_lib.SNR_DTYPE)
+            reps = reps.reshape(n_slots, self.cap)
+            res += ([reps[s, :k].copy() for s, k in enumerate(keep)],)
+        return res
 
     def texts(self, samples, code=None, int16_is_pcm=True):
         """Synchronous: -> list (per slot) of ft8_text arrays (_lib.TEXT_DTYPE) aligned with records():
@@ -306,30 +337,60 @@ class SlotDecoder:
         slot's first record with the same payload."""
         return self._records_and_texts(samples, code, int16_is_pcm)[1]
 
-    def messages(self, samples, table=None, unique=True, int16_is_pcm=True):
-        """-> list (per slot) of (text, time_s, freq_hz, score, record) for every decode whose message
-        type is unpacked (ft8_text.status 0), in candidate order; time, frequency and score as decode()
-        gives them.  unique drops the records whose payload an earlier record of the slot carries.
-        table (message.CallsignTable): hashed callsigns it knows are written <CALL>; slots are
-        handled in order, and within a slot every record is resolved before the slot is learned."""
+    def snr(self, samples, code=None, int16_is_pcm=True):
+        """Synchronous: -> list (per slot) of ft8_snr_rec arrays (_lib.SNR_DTYPE) aligned with records():
+        the signal report of every decode (snr_db: SNR in 2500 Hz), measured on the device
+        (ft8_snr_last) on the waterfall the decode left there.  Raises NotImplementedError for a
+        decoder built with FT8_FLAG_SUBTRACT (that waterfall is the residual's)."""
+        out, counts = self.run(samples, code, int16_is_pcm)
+        d_snr = self._snr_last(out, counts)
+        c = counts.cpu().numpy()
+        n_slots = len(c)
+        reps = d_snr[: n_slots * self.cap * _lib.SNR_DTYPE.itemsize].cpu().numpy().view(_lib.SNR_DTYPE)
+        reps = reps.reshape(n_slots, self.cap)
+        warn_truncated(c, self.cap, stacklevel=3)
+        return [reps[s, : min(int(c[s]), self.cap)].copy() for s in range(n_slots)]
+
+    def _message_rows(self, samples, table, unique, int16_is_pcm, snr):
         from .message import text_of
         x, code, wf_f64 = device_samples(samples, self.device, int16_is_pcm=int16_is_pcm)
-        recs, txts = self._records_and_texts(x, code)
+        got = self._records_and_texts(x, code, snr=snr, stacklevel=5)  # the warning names messages()' caller
+        recs, txts = got[0], got[1]
         fs, bpt = self.kw["sample_rate"], self.kw["bins_per_tone"]
         out = []
-        for r, t in zip(recs, txts):
+        for s, (r, t) in enumerate(zip(recs, txts)):
             sc = r["score"].astype(np.float64 if wf_f64 else np.float32)
             rows = []
             for i in range(len(r)):
                 if int(t["status"][i]) != 0 or (unique and int(t["dup_of"][i]) >= 0):
                     continue
                 text = table.resolve(t[i]) if table is not None else text_of(t[i])
-                rows.append((text, int(r["abs_time"][i]) / fs,
-                             (int(r["abs_freq"][i]) / bpt) * FT8_SYMBOL_FREQ_INTERVAL_HZ, sc[i], r[i]))
+                row = (text, int(r["abs_time"][i]) / fs,
+                       (int(r["abs_freq"][i]) / bpt) * FT8_SYMBOL_FREQ_INTERVAL_HZ, sc[i], r[i])
+                if snr:
+                    rep = got[2][s][i]
+                    row = row[:1] + (float(rep["snr_db"]) if int(rep["status"]) < 2 else float("nan"),) + row[1:]
+                rows.append(row)
             if table is not None:
                 table.learn(t)
             out.append(rows)
         return out
+
+    def messages(self, samples, table=None, unique=True, int16_is_pcm=True):
+        """-> list (per slot) of (text, time_s, freq_hz, score, record) for every decode whose message
+        type is unpacked (ft8_text.status 0), in candidate order; time, frequency and score as decode()
+        gives them.  unique drops the records whose payload an earlier record of the slot carries.
+        table (message.CallsignTable): hashed callsigns it knows are written <CALL>; slots are
+        handled in order, and within a slot every record is resolved before the slot is learned."""
+        return self._message_rows(samples, table, unique, int16_is_pcm, snr=False)
+
+    def reports(self, samples, table=None, unique=True, int16_is_pcm=True):
+        """messages() with the signal report: -> list (per slot) of (text, snr_db, time_s, freq_hz,
+        score, record); snr_db is the SNR in 2500 Hz (a Python float; NaN where the report's status
+        is 2).  One ft8_decode_batch, one ft8_unpack77 and one ft8_snr_last on the current stream,
+        with no host sync in between.  Raises NotImplementedError for a decoder built with
+        FT8_FLAG_SUBTRACT."""
+        return self._message_rows(samples, table, unique, int16_is_pcm, snr=True)
 
     def timing(self, reset=False):
         return self.ctx.timing(reset)

@@ -146,6 +146,16 @@ struct ft8_ctx {
   // the kernels of the last single-chain ft8_decode_batch, for ft8_replay_stage (benchmarking):
   // valid until the next entry point that may reallocate the context's scratch
   bool replay_ok = false;
+  // ft8_snr_last: the last ft8_decode_batch left its whole waterfall in `wf` (chunked or not) and
+  // snr_batch describes it; cleared wherever replay_ok is.  A and N0 of the report go to snr_A / snr_N0
+  bool snr_ok = false;
+  struct {
+    int n_slots, T, F, cap;
+    bool f64, subtract;
+    double bw_db;  // 10 log10(enbw_hz / 2500) of the batch's geometry
+    int sps, bpt;
+  } snr_batch{};
+  DevBuf snr_A, snr_N0;
   // the stream of the last entry point that enqueued work, and an event recorded on it after that
   // work (StreamOrder): a call on another stream first waits for it
   hipStream_t last_stream = nullptr;
@@ -1084,6 +1094,29 @@ int drift_fit_core(ft8_ctx* c, int stage, const int32_t* idx, int n_slots, int T
   return timed_launch(c, kDriftFit, s, "drift fit launch", [&] { return launch_drift_fit(stage, L, s); });
 }
 
+// ---- signal report ---------------------------------------------------------------------------------
+// 10 log10(enbw_hz / 2500): the equivalent noise bandwidth of the STFT's periodic Hann window with
+// scaling='spectrum' is 1.5 fs / nperseg; the report is the SNR in 2500 Hz
+double snr_bw_db(double fs, int nperseg) { return 10.0 * std::log10(1.5 * fs / (double)nperseg / 2500.0); }
+
+// ft8_decode_batch succeeded: c->wf holds the batch's waterfall [n_slots][T][F]
+void remember_snr_batch(ft8_ctx* c, const ft8_params* p, const Geo& g, int n_slots, int T, int F, int cap, bool f64) {
+  c->snr_batch = {n_slots, T, F, cap, f64, (p->flags & FT8_FLAG_SUBTRACT) != 0, snr_bw_db(rate_of(p), g.nperseg),
+                  p->steps_per_symbol, p->bins_per_tone};
+  c->snr_ok = true;
+}
+
+int check_snr_records(ft8_ctx* c, const ft8_result* d_records, const int32_t* d_counts, int64_t n_slots, int64_t cap,
+                      const ft8_snr_rec* d_out) {
+  if (!d_records || !d_out) return fail(c, FT8_E_ARG, "null records or output");
+  if (n_slots * cap > INT32_MAX) return fail(c, FT8_E_RANGE, "n_slots * cap exceeds 2^31 records");
+  if (((uintptr_t)d_records & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_counts & 3))
+    return fail(c, FT8_E_ARG, "records and reports must be 8-byte, counts 4-byte aligned");
+  return FT8_OK;
+}
+
+int noise_floor_rank(double q, int F) { return (int)std::floor(q * (double)(F - 1)); }
+
 }  // namespace
 
 // ============================================================================================
@@ -1153,7 +1186,7 @@ int ft8_geometry_hz(double fs, int32_t bpt, int32_t sps, int64_t n, int32_t* npe
 int ft8_stft(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots, int64_t slot_stride,
              const ft8_params* p, void* d_wf, void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || !p || (!d_samples && n_slots > 0) || (!d_wf && n_slots > 0)) return fail(c, FT8_E_ARG, "null argument");
   DeviceGuard dg(c->device);
   return do_stft(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, d_wf, (hipStream_t)stream);
@@ -1195,7 +1228,7 @@ int ft8_sync_select(ft8_ctx* c, const void* d_wf, int wf_f64, int32_t n_slots, i
                     const ft8_params* p, int32_t* d_cand, double* d_cand_score, int32_t* d_cand_count,
                     void* d_scores, void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || !p || !d_cand_count) return fail(c, FT8_E_ARG, "null argument");
   if (T < 0 || F < 0 || n_slots < 0) return fail(c, FT8_E_ARG, "negative size");
   DeviceGuard dg(c->device);
@@ -1205,7 +1238,7 @@ int ft8_sync_select(ft8_ctx* c, const void* d_wf, int wf_f64, int32_t n_slots, i
 
 int ft8_sync_score(ft8_ctx* c, const void* d_wf, int wf_f64, int32_t T, int32_t F, int32_t sps, int32_t bpt,
                    const int32_t* d_cand, int32_t n, void* d_out, int32_t* d_err, void* stream) {
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || n < 0 || (n > 0 && (!d_wf || !d_cand || !d_out || !d_err))) return fail(c, FT8_E_ARG, "bad argument");
   if (T <= 0 || F <= 0 || sps <= 0 || bpt <= 0) return fail(c, FT8_E_ARG, "empty waterfall or bad oversampling");
   DeviceGuard dg(c->device);
@@ -1215,7 +1248,7 @@ int ft8_sync_score(ft8_ctx* c, const void* d_wf, int wf_f64, int32_t T, int32_t 
 
 int ft8_llr(ft8_ctx* c, const void* d_wf, int wf_f64, int32_t T, int32_t F, int32_t sps, int32_t bpt,
             const int32_t* d_cand, int32_t n, int normalize, double* d_llr, void* stream) {
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || !d_llr || (!d_cand && n > 0) || sps <= 0 || bpt <= 0) return fail(c, FT8_E_ARG, "bad argument");
   if (n <= 0) return FT8_OK;
   DeviceGuard dg(c->device);
@@ -1236,7 +1269,7 @@ int ft8_llr(ft8_ctx* c, const void* d_wf, int wf_f64, int32_t T, int32_t F, int3
 }
 
 int ft8_normalize(ft8_ctx* c, const double* d_in, int32_t n, double* d_out, void* stream) {
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || (n > 0 && (!d_in || !d_out))) return fail(c, FT8_E_ARG, "bad argument");
   if (n <= 0) return FT8_OK;
   DeviceGuard dg(c->device);
@@ -1253,7 +1286,7 @@ int ft8_normalize(ft8_ctx* c, const double* d_in, int32_t n, double* d_out, void
 int ft8_bp(ft8_ctx* c, const double* d_llr, int32_t n, int32_t max_iterations, uint8_t* d_plain, ft8_result* d_res,
            void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || (!d_llr && n > 0)) return fail(c, FT8_E_ARG, "bad argument");
   if (n <= 0) return FT8_OK;
   DeviceGuard dg(c->device);
@@ -1278,7 +1311,7 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
                      int64_t slot_stride, const ft8_params* p, ft8_result* d_out, int32_t* d_counts,
                      int32_t cap, void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || !p || !d_counts || (n_slots > 0 && !d_samples) || n_slots < 0 || cap < 0)
     return fail(c, FT8_E_ARG, "bad argument");
   if (cap > 0 && !d_out) return fail(c, FT8_E_ARG, "null output with positive capacity");
@@ -1312,6 +1345,7 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   if ((rc = ensure_sel_scratch(c, n_slots, gr, N, f64))) return rc;
   if (!(p->flags & FT8_FLAG_SUBTRACT)) {
     if ((rc = decode_pass(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, d_out, d_counts, cap, s))) return rc;
+    remember_snr_batch(c, p, g, n_slots, T, F, cap, f64);
     whole.done();
     return FT8_OK;
   }
@@ -1336,13 +1370,14 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   hipError_t e = launch_merge_pass(d_out, d_counts, cap, out1, counts1, N, out2, counts2, N, n_slots, s);
   if (e != hipSuccess) return hipfail(c, e, "merge launch");
   c->replay_ok = false;
+  remember_snr_batch(c, p, g, n_slots, T, F, cap, false);
   whole.done();
   return FT8_OK;
 }
 
 int ft8_encode(ft8_ctx* c, const uint8_t* d_msg, int32_t msg_bytes, int32_t n, uint8_t* d_a91, uint8_t* d_codeword,
                uint8_t* d_tones, void* stream) {
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || n < 0 || (n > 0 && !d_msg)) return fail(c, FT8_E_ARG, "bad argument");
   if (msg_bytes != 10 && msg_bytes != 12) return fail(c, FT8_E_ARG, "msg_bytes must be 10 (payload) or 12 (a91)");
   if (n == 0) return FT8_OK;
@@ -1355,7 +1390,7 @@ int ft8_synthesize(ft8_ctx* c, const uint8_t* d_tones, const ft8_tx_signal* d_si
                    int32_t sample_rate, int32_t style, void* d_out, int out_dtype, int64_t n_samples, int32_t n_slots,
                    int64_t slot_stride, void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || n_signals < 0 || n_slots < 0 || n_samples < 0 || sample_rate <= 0) return fail(c, FT8_E_ARG, "bad argument");
   if (style != FT8_TX_PROTOCOL && style != FT8_TX_REFERENCE) return fail(c, FT8_E_ARG, "unknown ft8_tx_style");
   if (out_dtype != FT8_F32 && out_dtype != FT8_F64 && out_dtype != FT8_C64 && out_dtype != FT8_C128)
@@ -1389,7 +1424,7 @@ int ft8_subtract(ft8_ctx* c, const void* d_samples, int dtype, float* d_residual
                  int64_t slot_stride, const ft8_params* p, const ft8_result* d_res, const int32_t* d_counts, int32_t cap,
                  void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || !p || n_slots < 0 || cap < 0 || n_samples < 0) return fail(c, FT8_E_ARG, "bad argument");
   if (n_slots == 0 || n_samples == 0) {
     // nothing to fit: an empty subtraction's (zero) fits are valid, a zero-length one's never written
@@ -1421,7 +1456,7 @@ int ft8_subtract_fits(ft8_ctx* c, ft8_sub_fit* d_out, int32_t n_slots, int32_t c
 int ft8_stft_argmax(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
                     int64_t slot_stride, const ft8_params* p, int32_t* d_idx, void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || !p || (n_slots > 0 && (!d_samples || !d_idx))) return fail(c, FT8_E_ARG, "null argument");
   if (n_slots < 0 || n_samples < 0) return fail(c, FT8_E_ARG, "negative size");
   if (n_slots > 1 && slot_stride < n_samples) return fail(c, FT8_E_ARG, "slot_stride < n_samples");
@@ -1433,7 +1468,7 @@ int ft8_drift_fit(ft8_ctx* c, int32_t stage, const int32_t* d_idx, int32_t n_slo
                   const ft8_drift_params* p, ft8_drift_result* d_res, double* d_metric, int32_t* d_segments,
                   int32_t max_segments, void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || !p) return fail(c, FT8_E_ARG, "null argument");
   if (stage != 1 && stage != 2) return fail(c, FT8_E_ARG, "stage must be 1 or 2");
   if (n_slots < 0 || T < 0 || max_segments < 0) return fail(c, FT8_E_ARG, "negative size");
@@ -1448,7 +1483,7 @@ int ft8_drift_correct(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sa
                       int64_t slot_stride, const ft8_drift_params* p, void* d_out, ft8_drift_result* d_res,
                       void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || !p) return fail(c, FT8_E_ARG, "null argument");
   if (n_slots < 0 || n_samples < 0) return fail(c, FT8_E_ARG, "negative size");
   if (n_slots == 0) return FT8_OK;
@@ -1504,6 +1539,7 @@ int ft8_replay_stage(ft8_ctx* c, int32_t stage, int32_t reps, void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
   if (!c || reps < 0) return fail(c, FT8_E_ARG, "bad argument");
   if (!c->replay_ok) return fail(c, FT8_E_ARG, "no single-chain ft8_decode_batch to replay");
+  c->snr_ok = false;  // a replayed STFT rewrites wf from whatever the caller's sample buffer holds now
   DeviceGuard dg(c->device);
   hipStream_t s = (hipStream_t)stream;
   for (int r = 0; r < reps; ++r) {
@@ -1561,6 +1597,71 @@ int ft8_unpack77(ft8_ctx* c, const ft8_result* d_records, const int32_t* d_count
   return e == hipSuccess ? FT8_OK : hipfail(c, e, "unpack77 launch");
 }
 
+// the two stage calls touch no context state, so like ft8_unpack77 they take no part in the StreamOrder
+int ft8_noise_floor(ft8_ctx* c, const void* d_wf, int wf_f64, int32_t n_slots, int32_t T, int32_t F, double q,
+                    double* d_floor, double* d_colmean, void* stream) {
+  if (!c || n_slots < 0) return fail(c, FT8_E_ARG, "bad argument");
+  if (!(q >= 0.0 && q <= 1.0)) return fail(c, FT8_E_ARG, "q must lie in [0, 1]");
+  if (n_slots == 0) return FT8_OK;
+  if (T <= 0 || F <= 0) return fail(c, FT8_E_ARG, "empty waterfall");
+  if (!d_wf || !d_floor || !d_colmean) return fail(c, FT8_E_ARG, "null argument");
+  if (((uintptr_t)d_wf & (wf_f64 ? 7 : 3)) || ((uintptr_t)d_floor & 7) || ((uintptr_t)d_colmean & 7))
+    return fail(c, FT8_E_ARG, "misaligned buffer");
+  DeviceGuard dg(c->device);
+  hipError_t e = launch_noise_floor(d_wf, wf_f64, n_slots, T, F, noise_floor_rank(q, F), d_floor, d_colmean,
+                                    (hipStream_t)stream);
+  return e == hipSuccess ? FT8_OK : hipfail(c, e, "noise floor launch");
+}
+
+int ft8_snr(ft8_ctx* c, const void* d_wf, int wf_f64, int32_t n_slots, int32_t T, int32_t F, const ft8_params* p,
+            int64_t n_samples, const ft8_result* d_records, const int32_t* d_counts, int32_t cap,
+            const double* d_floor, int32_t radius, ft8_snr_rec* d_out, void* stream) {
+  if (!c || !p || n_slots < 0 || cap < 0) return fail(c, FT8_E_ARG, "bad argument");
+  if (radius < 0 || radius > 1) return fail(c, FT8_E_ARG, "radius must be 0 or 1");
+  Geo g;
+  std::string why;
+  int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
+  if (rc) return fail(c, rc, why);
+  if (n_slots == 0 || cap == 0) return FT8_OK;
+  if (T <= 0 || F <= 0) return fail(c, FT8_E_ARG, "empty waterfall");
+  if (!d_wf || !d_floor) return fail(c, FT8_E_ARG, "null argument");
+  if (((uintptr_t)d_wf & (wf_f64 ? 7 : 3)) || ((uintptr_t)d_floor & 7)) return fail(c, FT8_E_ARG, "misaligned buffer");
+  if ((rc = check_snr_records(c, d_records, d_counts, n_slots, cap, d_out))) return rc;
+  DeviceGuard dg(c->device);
+  hipError_t e = launch_snr(d_wf, wf_f64, n_slots, T, F, p->steps_per_symbol, p->bins_per_tone, d_records, d_counts,
+                            cap, d_floor, radius, snr_bw_db(rate_of(p), g.nperseg), d_out, (hipStream_t)stream);
+  return e == hipSuccess ? FT8_OK : hipfail(c, e, "snr launch");
+}
+
+int ft8_snr_last(ft8_ctx* c, const ft8_result* d_records, const int32_t* d_counts, int32_t n_slots, int32_t cap,
+                 ft8_snr_rec* d_out, void* stream) {
+  StreamOrder order_(c, (hipStream_t)stream);
+  if (!c || n_slots < 0 || cap < 0) return fail(c, FT8_E_ARG, "bad argument");
+  if (n_slots == 0) return FT8_OK;
+  if (!c->snr_ok) return fail(c, FT8_E_ARG, "no ft8_decode_batch whose waterfall is still in the context");
+  const auto& b = c->snr_batch;
+  if (n_slots != b.n_slots || cap != b.cap)
+    return fail(c, FT8_E_ARG, "n_slots / cap differ from the last ft8_decode_batch's (" + std::to_string(b.n_slots) +
+                                  " / " + std::to_string(b.cap) + ")");
+  if (b.subtract)
+    return fail(c, FT8_E_UNSUPPORTED,
+                "the last batch ran FT8_FLAG_SUBTRACT: the context holds the residual's waterfall, without the pass-1 "
+                "signals (use ft8_stft + ft8_noise_floor + ft8_snr)");
+  if (cap == 0) return FT8_OK;
+  int rc;
+  if ((rc = check_snr_records(c, d_records, d_counts, n_slots, cap, d_out))) return rc;
+  DeviceGuard dg(c->device);
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = ensure(c, c->snr_A, sizeof(double) * (size_t)n_slots * b.F))) return rc;
+  if ((rc = ensure(c, c->snr_N0, sizeof(double) * (size_t)n_slots))) return rc;
+  hipError_t e = launch_noise_floor(c->wf.p, b.f64, n_slots, b.T, b.F, noise_floor_rank(0.25, b.F),
+                                    c->snr_N0.as<double>(), c->snr_A.as<double>(), s);
+  if (e != hipSuccess) return hipfail(c, e, "noise floor launch");
+  e = launch_snr(c->wf.p, b.f64, n_slots, b.T, b.F, b.sps, b.bpt, d_records, d_counts, cap, c->snr_N0.as<double>(), 1,
+                 b.bw_db, d_out, s);
+  return e == hipSuccess ? FT8_OK : hipfail(c, e, "snr launch");
+}
+
 int ft8_select_warnings(ft8_ctx* c, int32_t* d_out, int32_t n_slots, void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
   if (!c || !d_out || n_slots < 0) return fail(c, FT8_E_ARG, "bad argument");
@@ -1573,7 +1674,7 @@ int ft8_select_warnings(ft8_ctx* c, int32_t* d_out, int32_t n_slots, void* strea
 }
 
 int ft8_crc14(ft8_ctx* c, const uint8_t* d_msg, const int32_t* d_nbits, int32_t n, uint16_t* d_crc, void* stream) {
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || (n > 0 && (!d_msg || !d_nbits || !d_crc))) return fail(c, FT8_E_ARG, "bad argument");
   DeviceGuard dg(c->device);
   hipError_t e = launch_crc14(d_msg, d_nbits, n, d_crc, (hipStream_t)stream);
@@ -1581,7 +1682,7 @@ int ft8_crc14(ft8_ctx* c, const uint8_t* d_msg, const int32_t* d_nbits, int32_t 
 }
 
 int ft8_ldpc_check(ft8_ctx* c, const uint8_t* d_bits, int32_t n, int32_t* d_errors, void* stream) {
-  if (c) c->replay_ok = false;
+  if (c) c->replay_ok = c->snr_ok = false;
   if (!c || (n > 0 && (!d_bits || !d_errors))) return fail(c, FT8_E_ARG, "bad argument");
   DeviceGuard dg(c->device);
   hipError_t e = launch_ldpc_check(d_bits, n, d_errors, (hipStream_t)stream);

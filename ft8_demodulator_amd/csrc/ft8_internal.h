@@ -291,6 +291,16 @@ hipError_t launch_pack(const ft8_result* rec, const int32_t* counts, int n_slots
 hipError_t launch_unpack77(const ft8_result* rec, const int32_t* counts, int n_slots, int cap, ft8_text* out,
                            hipStream_t s);
 
+// ---- signal report (snr.hip) -------------------------------------------------------------------
+// k_noise_floor: colmean[n_slots][F] = the time mean of every column's linear power; k_noise_rank:
+// floor_out[n_slots] = its element of rank `rank` sorted ascending (NaNs last), one workgroup per slot
+hipError_t launch_noise_floor(const void* wf, int wf_f64, int n_slots, int T, int F, int rank, double* floor_out,
+                              double* colmean, hipStream_t s);
+// k_snr: records [n_slots][cap] -> reports, one wave per record; bw_db = 10 log10(enbw_hz / 2500)
+hipError_t launch_snr(const void* wf, int wf_f64, int n_slots, int T, int F, int sps, int bpt, const ft8_result* rec,
+                      const int32_t* counts, int cap, const double* floor_in, int radius, double bw_db,
+                      ft8_snr_rec* out, hipStream_t s);
+
 // ---- transmit chain + subtraction (tx.hip, subtract.hip) -------------------------------------
 struct SynthLaunch {
   const uint8_t* tones;        // [n_sig][79]

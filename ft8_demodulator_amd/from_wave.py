@@ -88,8 +88,39 @@ def decode_ft8_from_wave(wave_path: str, freq_min: float = None, freq_max: float
                               device=device)
 
 
-def _print_results(results, text: bool = False):
-    """text: one extra `Message:` line per result, the payload unpacked to message text."""
+def decode_ft8_from_wave_snr(wave_path: str, freq_min: float = None, freq_max: float = None, time_min: float = None,
+                             time_max: float = None, bins_per_tone: int = 2, steps_per_symbol: int = 2,
+                             max_candidates: int = 20, min_score: float = 10, max_iterations: int = 20,
+                             device=None) -> tuple:
+    """decode_ft8_from_wave with the signal report (build-defined): -> (results, snr_db), the same
+    5-tuples and one SNR in 2500 Hz (dB, float) per result, measured on the device on the waterfall
+    of the same decode (SlotDecoder.snr / ft8_snr_last)."""
+    import torch
+    from . import _lib
+    from ._pipeline import SlotDecoder, make_plan, records_to_results
+    data, dtype, sample_rate = _read_raw(wave_path)
+    _lib.require_gpu()
+    dev = torch.device("cuda", _lib.device_index(device))
+    if dtype == np.int16:
+        x, code = torch.from_numpy(np.array(data, copy=True)).to(dev), _lib.FT8_I16
+    else:
+        h = data.astype(np.float32)
+        h /= np.iinfo(dtype).max
+        x, code = torch.from_numpy(h).to(dev), _lib.FT8_F32
+    plan = make_plan(int(x.shape[0]), sample_rate, bins_per_tone, steps_per_symbol, freq_min, freq_max, time_min,
+                     time_max)
+    if plan.empty or max_candidates <= 0:
+        return [], []
+    dec = SlotDecoder(sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score, max_iterations,
+                      freq_min, freq_max, time_min, time_max, device=dev)
+    recs, _, reps = dec._records_and_texts(x.unsqueeze(0), code, snr=True)
+    snr_db = [float(r["snr_db"]) if int(r["status"]) < 2 else float("nan") for r in reps[0]]
+    return records_to_results(recs[0], sample_rate, bins_per_tone, False), snr_db
+
+
+def _print_results(results, text: bool = False, snr=None):
+    """text: one extra `Message:` line per result, the payload unpacked to message text.  snr (one
+    value per result): one extra `SNR:` line per result, dB in 2500 Hz."""
     if not results:
         print("No FT8 messages decoded")
         return
@@ -99,10 +130,12 @@ def _print_results(results, text: bool = False):
                  for t in unpack77([bytes(r[0].payload) for r in results])]
     print("\nDecoded FT8 messages:")
     print("-" * 50)
-    for message, status, time_sec, freq_hz, score in results:
+    for k, (message, status, time_sec, freq_hz, score) in enumerate(results):
         print(f"Time: {time_sec:.2f} seconds")
         print(f"Frequency: {freq_hz:.1f} Hz")
         print(f"Score: {score:.1f}")
+        if snr is not None:
+            print(f"SNR: {snr[k]:.1f} dB")
         print(f"Payload: {message.payload.hex()}")
         if text:
             print(f"Message: {texts.pop(0)}")
@@ -149,11 +182,27 @@ def main(argv=None):
     parser.add_argument("--max-iterations", type=int, default=20)
     parser.add_argument("--correction", type=bool, default=False)
     parser.add_argument("--text", action="store_true", help="print each payload's message text as well")
+    parser.add_argument("--snr", action="store_true", help="print each decode's SNR in 2500 Hz as well")
     args = parser.parse_args(argv)
     for path in args.wave_file:
         if not os.path.exists(path):
             print(f"Error: File {path} does not exist")
             sys.exit(1)
+    if args.snr:
+        # the report comes from the decode's own waterfall: one file at a time, each decoded once
+        if args.correction:
+            decode_ft8_from_wave(args.wave_file[0], correction=True)  # raises as without --snr
+        per_file = []
+        for path in args.wave_file:
+            results, snr = decode_ft8_from_wave_snr(
+                path, freq_min=args.freq_min, freq_max=args.freq_max, time_min=args.time_min, time_max=args.time_max,
+                bins_per_tone=args.bins_per_tone, steps_per_symbol=args.steps_per_symbol,
+                max_candidates=args.max_candidates, min_score=args.min_score, max_iterations=args.max_iterations)
+            if len(args.wave_file) > 1:
+                print(f"\n== {path}")
+            _print_results(results, args.text, snr)
+            per_file.append(results)
+        return per_file if len(args.wave_file) > 1 else per_file[0]
     if len(args.wave_file) > 1:
         per_file = _decode_many(args)
         for path, results in zip(args.wave_file, per_file):

@@ -272,6 +272,60 @@ int ft8_unpack77_host(const uint8_t* payloads, int32_t n, ft8_text* out);
  * character outside " 0-9A-Z/" or a length above 11. */
 int ft8_hash_call(const char* call, uint32_t* n22);
 
+/* ---- signal report: the SNR of every decode ------------------------------------------------------
+ * Build-defined, outside reference parity (the reference stops at the payload).  The estimator
+ * (DESIGN.md section 10), on a waterfall d_wf[n_slots][T][F] as ft8_stft writes it (dB, float32 or
+ * float64; every value is widened to double and all arithmetic is double):
+ *   P[t][f]  = 10^(wf[t][f] / 10)
+ *   A[f]     = mean over t of P[t][f], added in the order t = 0 .. T-1
+ *   N0       = the element of rank floor(q (F-1)) of A sorted ascending (no interpolation; NaNs last)
+ *   M(dt,df) = mean over the symbols k = 0 .. 78 whose row lies in [0, T) of
+ *              P[abs_time + dt + k steps_per_symbol][abs_freq + df + tone[k] bins_per_tone],
+ *              tone[] the record's payload re-encoded, added in the order of k; dt, df in
+ *              [-radius, radius], of which only the df with abs_freq + df >= 0 and
+ *              abs_freq + df + 7 bins_per_tone <= F - 1 are considered; offsets with no row in range
+ *              or a NaN mean are skipped; the first largest M wins (dt outer, df inner, ascending)
+ *   S        = M - N0, raised to 1e-3 N0 (status 1) when below it
+ *   snr_db   = 10 log10(S / N0) + 10 log10(enbw_hz / 2500), enbw_hz = 1.5 fs / nperseg (the
+ *              equivalent noise bandwidth of the STFT's periodic Hann window): the SNR in 2500 Hz.
+ * One report per ft8_result, 24 bytes. */
+typedef struct ft8_snr_rec {
+  double  snr_db;
+  float   signal_db;      /* 10 log10 S */
+  float   noise_db;       /* 10 log10 N0 */
+  int8_t  dt, df;         /* the grid offset whose mean was taken */
+  uint8_t n_symbols;      /* symbols of it whose row lies in [0, T) */
+  uint8_t status;         /* 0 valid; 1 valid, S was raised to 1e-3 N0; 2 no admissible offset or symbol (zeros
+                             elsewhere); 3 record not ok or past the slot's count (zeros elsewhere) */
+  uint8_t reserved[4];
+} ft8_snr_rec;
+
+/* A and N0 of every slot: d_colmean[n_slots][F] (required) and d_floor[n_slots].  q in [0, 1].  T and
+ * F >= 1; any F is taken.  Two kernels on the caller's stream (the means, reading the waterfall
+ * once; the quantile, reading d_colmean); they use none of the context's scratch, so the call takes
+ * no part in the context's cross-stream order. */
+int ft8_noise_floor(ft8_ctx* ctx, const void* d_wf, int wf_f64, int32_t n_slots, int32_t T, int32_t F, double q,
+                    double* d_floor, double* d_colmean, void* stream);
+/* The reports of d_records[n_slots][cap] (d_counts as for ft8_unpack77, NULL: every slot holds cap
+ * records) against d_floor[n_slots]: d_out[s * cap + r] is written for every r < cap.  p gives
+ * bins_per_tone, steps_per_symbol and, with n_samples, the STFT geometry (nperseg, for enbw_hz).
+ * radius 0 or 1.  One kernel on the caller's stream, no context scratch, no part in the
+ * cross-stream order. */
+int ft8_snr(ft8_ctx* ctx, const void* d_wf, int wf_f64, int32_t n_slots, int32_t T, int32_t F, const ft8_params* p,
+            int64_t n_samples, const ft8_result* d_records, const int32_t* d_counts, int32_t cap,
+            const double* d_floor, int32_t radius, ft8_snr_rec* d_out, void* stream);
+/* ft8_noise_floor (q = 0.25) and ft8_snr (radius 1) on the waterfall the last ft8_decode_batch of this context left
+ * in its scratch, for that call's records: n_slots and cap must equal that call's n_slots and
+ * max_results_per_slot, and no other entry point that uses the context's scratch (nor ft8_llr,
+ * ft8_sync_score, ft8_normalize, ft8_encode, ft8_crc14, ft8_ldpc_check) may have run on the context
+ * in between -- FT8_E_ARG otherwise; ft8_unpack77 and ft8_pack_decodes may.  A pipelined (chunked)
+ * batch is as good as a single chain: the chunks write one contiguous waterfall.  After an
+ * FT8_FLAG_SUBTRACT batch the scratch holds the waterfall of the residual, from which the pass-1
+ * signals are gone: FT8_E_UNSUPPORTED (measure those with ft8_stft + ft8_noise_floor + ft8_snr).
+ * Three kernels (ft8_noise_floor's two, ft8_snr's one).  A and N0 live in the context's scratch, so the call takes part in the cross-stream order. */
+int ft8_snr_last(ft8_ctx* ctx, const ft8_result* d_records, const int32_t* d_counts, int32_t n_slots, int32_t cap,
+                 ft8_snr_rec* d_out, void* stream);
+
 /* Per-slot flags of the last selection (copied device->device into d_out[n_slots]):
  * bit 0: an exact score tie reached a heap comparison (the reference raises TypeError there,
  *        ftx_types.py:37-47; here ties are ordered by scan index), bit 1: unused (0), bit 2
