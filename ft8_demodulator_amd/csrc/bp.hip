@@ -22,6 +22,7 @@
 //
 // Roofline: the kernel touches < 2 KB of HBM per candidate; it is bound by float64 VALU issue
 // (two IEEE divisions per edge per iteration, ~30 float64 ops per edge per iteration).
+#include "div_shared.h"
 #include "ft8_internal.h"
 #include "heap_replay.h"
 
@@ -42,17 +43,49 @@ constexpr int kChkSlots = (FT8_LDPC_M + kWave - 1) / kWave;   // 2
 // phases are branch-free and the per-lane chains (18 IEEE divisions per sweep) interleave.
 
 // Fixed kernel shape (round 3: the build-time experiment switches of round 2 are gone; DESIGN.md
-// section 3 lists what each alternative measured, and the fault one of them caused).  Divisions are
-// interleaved three at a time: a variable's three edges, and the nine products of phase D (seven of
-// the lane's own check, two leftover edges) in three groups.  A group size that does not divide
-// kEdgeSlots indexes past the lane's register arrays -- undefined behaviour, which the compiler
-// answers by deleting the divisions -- so it is pinned and asserted here.
+// section 3 lists what each alternative measured, and the fault one of them caused).  The
+// per-division sequences (div_fast, div_rn: tiny arguments, NaN inputs) are interleaved three at a
+// time: a variable's three edges, and the nine products of phase D (seven of the lane's own check,
+// two leftover edges) in three groups.  A group size that does not divide kEdgeSlots indexes past the
+// lane's register arrays -- undefined behaviour, which the compiler answers by deleting the
+// divisions -- so it is pinned and asserted here.
 constexpr int kDivGroup = 3;
 static_assert(kEdgeSlots % kDivGroup == 0 && kVarSlots == kDivGroup, "division groups tile the slots exactly");
+// On the short path of a candidate without NaN inputs, a sharing group of divisions takes ONE
+// v_rcp_f64 (div_shared.h).  Every member of a sharing group is a real, finite, in-range denominator,
+// padding included (see the sweep):
+//   fast_tanh   nb = -30240 + z (-3360 - 30 z), z = y^2 <= 9.94^2:  -6.6e5 <= nb <= -30240
+//   fast_atanh  nb = -472.5 + x2 (525 - 112.5 x2), x2 <= 1.0073^12: -472.5 <= nb <= -33.6
+// so a 9-fold product has magnitude in [33.6^9, 6.6e5^9] = [5.4e13, 2.4e52]: no overflow, and the
+// product and its reciprocal are normal numbers far from either end of the range.
+// The grouping is the largest the register file admits at four waves per SIMD (DESIGN.md section 3
+// has every grouping's VGPR count and time):
+//   phase C  kShareC: 3 = one variable's edges at a time, 9 = the lane's nine edges at once;
+//   phase D  kShareD: the first sharing group (3, 6 or 9 products); the rest go three at a time.
+// 9 + (6, 3) is 3 seeds per sweep for 18 divisions at 123 VGPRs; 9 products at once in phase D need
+// 135 and 4 + 5 need 129 -- three waves, slower than no sharing at all.  The NaN-safe instantiation
+// carries the per-division sequences too (9 + (6, 3) would be 135 VGPRs) and keeps groups of three.
+template <bool NANSAFE> constexpr int kShareC = NANSAFE ? 3 : 9;
+template <bool NANSAFE> constexpr int kShareD = NANSAFE ? 3 : 6;
+template <int C, int D>
+constexpr bool share_tiling_ok() {
+  return (C == kDivGroup || C == kVarSlots * 3) && D >= kDivGroup && D <= kEdgeSlots && D % kDivGroup == 0;
+}
+static_assert(share_tiling_ok<kShareC<false>, kShareD<false>>() && share_tiling_ok<kShareC<true>, kShareD<true>>(),
+              "sharing groups are whole division groups and tile both phases exactly");
+constexpr double kTanhDenMax = 30240.0 + 98.81 * (3360.0 + 30.0 * 98.81);  // |nb| at |y| = 9.94
+constexpr double kAtanhDenMax = 472.5;
+constexpr double kAtanhDenMin = 33.6;
+constexpr double pow_c(double b, int n) { return n == 0 ? 1.0 : b * pow_c(b, n - 1); }
+static_assert(pow_c(kTanhDenMax, kEdgeSlots) < 0x1p+900 && pow_c(kAtanhDenMax, kEdgeSlots) < 0x1p+900 &&
+                  pow_c(kAtanhDenMin, kEdgeSlots) > 1.0,
+              "a phase's product of denominators is finite and its reciprocal normal");
 // Resident waves per SIMD the persistent grid is sized for.  The compiler is given a 3-wave register
 // budget: under a 4-wave budget (128 VGPRs) the allocator spills ~50 VGPRs of the fused sweep to
-// scratch, while under the 3-wave budget it needs only 111 (117 NaN-safe; 123 before phase D went
-// check-major) -- which still leaves 4 waves resident per SIMD (512 / 128).
+// scratch, while under the 3-wave budget it needs only 123 (both instantiations; 111 / 117 before
+// the sharing groups) -- which still leaves 4 waves resident per SIMD (512 / 128).  The scheduler
+// uses whatever that budget allows, so the sharing groups are fenced (sched_barrier) to one at a
+// time: left free, it interleaves all nine chains of phase D and takes 147 VGPRs.
 constexpr int kBpWavesPerSimd = 4;
 constexpr int kBpLbWaves = 3;
 constexpr int kBpGridCus = 256;        // MI355X: 256 CUs
@@ -102,6 +135,12 @@ __device__ __forceinline__ double pymax4(double a, double b, double c, double d)
 // caller scales by -2, ldpc_decoder.py:108).  On the fast path every quotient is normal, so
 // RN(x / (-b/2)) == -2 RN(x/b) exactly and the scaling costs nothing; the full path divides by
 // b = -2 y (exact) and scales the quotient.
+//
+// Where the short path holds for the whole wave and the candidate has no NaN input, the sweep does
+// not run this sequence per division: a sharing group (kShareC, kShareD) derives its reciprocals
+// from one v_rcp_f64 of the group's product (div_shared.h) and keeps this sequence's last Newton
+// step and quotient tail per division.  div_fast / div_rn remain for everything else.
+//
 // the short sequence alone, for callers that established its preconditions themselves
 template <int N>
 __device__ __forceinline__ void div_fast(double* q, const double* x, const double* y) {
@@ -123,6 +162,11 @@ __device__ __forceinline__ void div_fast(double* q, const double* x, const doubl
 #pragma unroll
   for (int i = 0; i < N; ++i) q[i] = __builtin_fma(e[i], r[i], m[i]);
 }
+
+// the hardware seed of the shared-reciprocal form (div_shared.h)
+struct RcpHw {
+  __device__ __forceinline__ double operator()(double v) const { return __builtin_amdgcn_rcp(v); }
+};
 
 template <int N, bool NEG2 = false>
 __device__ __forceinline__ void div_rn(double* q, const double* x, const double* y_in, int fast = 0) {
@@ -670,6 +714,22 @@ __device__ __forceinline__ double clip2(double T, bool nan_in) {
   return (nan_in && T != T) ? T : y;
 }
 
+// fast_tanh's folded polynomials of K clipped arguments and their K quotients on one reciprocal, in
+// place: only for a wave on the short path whose candidate has no NaN input (a NaN in one
+// denominator's argument would reach its group mates through the product; in the reference it
+// stays on its own edge).
+template <int K>
+__device__ __forceinline__ void tanh_shared(double* v) {
+  double na[K], nb[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const double yv = v[i], z = yv * yv;
+    na[i] = yv * (15120.0 + z * (420.0 + z));
+    nb[i] = -30240.0 + z * (-3360.0 + z * -30.0);
+  }
+  div_shared<K, kDivGroup>(v, na, nb, RcpHw());
+}
+
 // fast_tanh (ldpc_decoder.py:11-20) of kDivGroup clipped arguments in place: y = clip(T, +-2 c) in,
 // toc out (see the sweep's phase C for the scaling argument)
 // fast: the caller established the short division for the whole wave (sweep_fast)
@@ -751,6 +811,19 @@ __device__ __forceinline__ void atanh_group(double* v, int fast = 0) {
     nb[i] = (-472.5 + x2 * (525.0 + x2 * -112.5));
   }
   div_rn<kDivGroup, true>(v, na, nb, fast);
+}
+
+// the same for K products on one shared reciprocal (short path, no NaN input: see tanh_shared)
+template <int K>
+__device__ __forceinline__ void atanh_shared(double* v) {
+  double na[K], nb[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const double xv = v[i], x2 = xv * xv;
+    na[i] = xv * (945.0 + x2 * __builtin_fma(x2, 64.0, -735.0));
+    nb[i] = (-472.5 + x2 * (525.0 + x2 * -112.5));
+  }
+  div_shared<K, kDivGroup>(v, na, nb, RcpHw());
 }
 
 // Per-lane LDS byte addresses of the leftover slots (registers, built once per wave): the lane's row
@@ -872,6 +945,8 @@ __global__ __launch_bounds__(kWave, kBpLbWaves) void k_bp(BpArgs a) {
     // then ends the first sweep exactly as in the reference) or none: only the plain-LLR entry
     // point (ft8_bp, NANSAFE) needs the test.
     const bool nan_in = NANSAFE && __ballot(cv_[0] != cv_[0] || cv_[1] != cv_[1] || cv_[2] != cv_[2]) != 0;
+    int nan_s = __builtin_amdgcn_readfirstlane(nan_in ? 1 : 0);  // the same as a scalar 0 / 1
+    asm volatile("" : "+s"(nan_s));
 
     // ---- belief propagation (ldpc_decoder.py:54-113) ----------------------------------------
     // One sweep = the reference iteration.  (A) variable-major: each lane reads its variables'
@@ -974,15 +1049,38 @@ __global__ __launch_bounds__(kWave, kBpLbWaves) void k_bp(BpArgs a) {
       // wave-uniform int (a bool crossing blocks would be kept as a VALU lane mask)
       int fast = __builtin_amdgcn_readfirstlane(sweep_fast(y) ? 1 : 0);
       asm volatile("" : "+s"(fast));  // opaque SGPR: branches test it with s_cmp
+      // One reciprocal per sharing group (kShareC, kShareD; div_shared.h) when the wave is on the
+      // short path and the candidate has no NaN input.  Every member of a group is then a finite argument
+      // in fast_tanh's / fast_atanh's range, padding included: variable slot 2 of lanes >= 46 holds
+      // +-1.0 (above); a degree-6 row's x[6] is the full product of its six toc (times the constant
+      // 1.0); the leftover slots of lanes >= 57 repeat real rows' products (left_q3).  None of them
+      // is stored, and none can spoil the lane's real edges.
+      // Without NaN handling share is fast itself: the per-division paths then run only for a wave
+      // off the short path and get no flag (fast1 = 0; a group's own test decides).
+      int share = fast;
+      if constexpr (NANSAFE) {
+        share = fast & ~nan_s;
+        asm volatile("" : "+s"(share));
+      }
+      const int fast1 = NANSAFE ? fast : 0;  // the per-division paths' flag
       if (sweep0) {  // one fast_tanh per variable
         double v[kVarSlots] = {y[0][0], y[1][0], y[2][0]};
-        tanh_group(v, fast);
+        if (share) tanh_shared<kVarSlots>(v);
+        else tanh_group(v, fast1);
 #pragma unroll
         for (int j = 0; j < kVarSlots; ++j) y[j][0] = y[j][1] = y[j][2] = v[j];
+      } else if (share && kShareC<NANSAFE> == kEdgeSlots) {  // the lane's nine divisions on one reciprocal
+        static_assert(sizeof(y) == sizeof(double) * kEdgeSlots, "y is nine contiguous arguments");
+        tanh_shared<kEdgeSlots>(&y[0][0]);
       }
 #pragma unroll
       for (int j = 0; j < kVarSlots; ++j) {
-        if (!sweep0) tanh_group(y[j], fast);
+        if (!sweep0 && share && kShareC<NANSAFE> == kDivGroup) {
+          tanh_shared<kDivGroup>(y[j]);
+          __builtin_amdgcn_sched_barrier(0);
+        } else if (!sweep0 && !share) {
+          tanh_group(y[j], fast1);
+        }
         if (j < kVarSlots - 1 || var2) {
           *(__attribute__((address_space(3))) double*)(uintptr_t)tb.va[j] = y[j][0];
           *(__attribute__((address_space(3))) double*)(uintptr_t)tb.va1[j] = y[j][1];
@@ -996,8 +1094,20 @@ __global__ __launch_bounds__(kWave, kBpLbWaves) void k_bp(BpArgs a) {
       // x[0..6]: the lane's own check, x[7..8]: its two leftover edges; all reads precede the stores
       row_products(x, la);
       left_products(&x[7], lf);
+      if (share) {
+        // one sharing group at a time: the groups' chains are independent, and a scheduler free to
+        // interleave all nine would hold every group's temporaries at once (147 VGPRs, three waves)
+        atanh_shared<kShareD<NANSAFE>>(x);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int g = 0; g < kEdgeSlots; g += kDivGroup) atanh_group(&x[g], fast);
+        for (int g = kShareD<NANSAFE>; g < kEdgeSlots; g += kDivGroup) {
+          atanh_shared<kDivGroup>(&x[g]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      } else {
+#pragma unroll
+        for (int g = 0; g < kEdgeSlots; g += kDivGroup) atanh_group(&x[g], fast1);
+      }
 #pragma unroll
       for (int f = 0; f < 6; ++f)
         *(__attribute__((address_space(3))) double*)(uintptr_t)(la + (uint32_t)(kRowB * f)) = x[f];
