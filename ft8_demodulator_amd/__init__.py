@@ -5,8 +5,9 @@ decode_ft8_message, calculate_spectrogram, select_frequency_band,
 create_waterfall_from_spectrogram, ft8_find_candidates, ft8_decode_candidate, bp_decode,
 ldpc_check, compute_crc/extract_crc/add_crc and the FT8* dataclasses -- plus the WAV entry
 point (from_wave), a batched slot decoder (SlotDecoder, decode_slots), the message layer
-(pack77, unpack77, CallsignTable: payload <-> text) and the signal report (SlotDecoder.reports,
-snr_reference: each decode's SNR in 2500 Hz).  Every numeric stage runs in
+(pack77, unpack77, CallsignTable: payload <-> text), the signal report (SlotDecoder.reports,
+snr_reference: each decode's SNR in 2500 Hz) and a-priori decoding (SlotDecoder(ap=["CQ ? ?"]),
+ap_hypothesis, ap_index: failed candidates retried with known message bits).  Every numeric stage runs in
 hand-written HIP kernels (csrc/) reached through the C-ABI library libft8hip.so; there is no
 CPU fallback: calls fail loudly when the library or a GPU is missing.
 """
@@ -23,3 +24,4 @@ from .from_wave import decode_ft8_from_wave, read_wave_file  # noqa: E402,F401
 from ._pipeline import SlotDecoder, decode_slots  # noqa: E402,F401
 from .message import CallsignTable, hash_call, pack77, pack_telemetry, unpack77  # noqa: E402,F401
 from .snr import snr_reference  # noqa: E402,F401
+from .ap import ap_hypothesis, ap_index  # noqa: E402,F401

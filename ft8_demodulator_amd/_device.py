@@ -139,6 +139,23 @@ def bp(llrs, max_iterations):
     return plain.cpu().numpy(), res.cpu().numpy().view(_lib.RESULT_DTYPE)
 
 
+def ap_decode(llrs, records, max_iterations):
+    """ft8_ap_decode: LLRs [n, 174] and the records ft8_bp wrote from them -> (records updated by the
+    context's a-priori hypotheses (Context.set_ap), hard int16 [n])."""
+    torch = _lib.require_gpu()
+    ctx = _lib.context()
+    a = torch.from_numpy(np.ascontiguousarray(np.asarray(llrs, dtype=np.float64).reshape(-1, 174))).cuda()
+    n = a.shape[0]
+    rec = np.ascontiguousarray(np.asarray(records, dtype=_lib.RESULT_DTYPE).reshape(-1))
+    if len(rec) != n:
+        raise ValueError(f"{n} LLR vectors but {len(rec)} records")
+    res = torch.from_numpy(np.concatenate([rec.view(np.uint8), np.zeros(8, np.uint8)])).to(a.device)
+    hard = torch.zeros(max(n, 1), dtype=torch.int16, device=a.device)
+    ctx.check(_lib.lib().ft8_ap_decode(ctx.handle, _lib.ptr(a), _lib.ptr(res), n, int(max_iterations),
+                                       _lib.ptr(hard), _lib.stream_handle()), "ft8_ap_decode")
+    return res.cpu().numpy()[: n * _lib.RESULT_DTYPE.itemsize].view(_lib.RESULT_DTYPE).copy(), hard.cpu().numpy()[:n]
+
+
 def crc14(msgs, nbits):
     torch = _lib.require_gpu()
     ctx = _lib.context()

@@ -16,7 +16,8 @@ LIB_PATH = os.environ.get("FT8HIP_LIB", os.path.join(_HERE, "lib", "libft8hip.so
 
 FT8_F32, FT8_F64, FT8_C64, FT8_C128, FT8_I16 = 0, 1, 2, 3, 4
 FT8_OK, FT8_E_ARG, FT8_E_HIP, FT8_E_UNSUPPORTED, FT8_E_NOMEM, FT8_E_RANGE = 0, -1, -2, -3, -4, -5
-FT8_FLAG_TOPK, FT8_FLAG_SUBTRACT = 1, 2
+FT8_FLAG_TOPK, FT8_FLAG_SUBTRACT, FT8_FLAG_AP = 1, 2, 4
+FT8_AP_MAX_HYP = 8
 FT8_TX_PROTOCOL, FT8_TX_REFERENCE = 0, 1
 FT8_STFT_STOCKHAM, FT8_STFT_PACKED3840, FT8_STFT_CHIRPZ, FT8_STFT_DFT = 0, 1, 2, 3
 N_STAGES = 12
@@ -86,6 +87,9 @@ TEXT_DTYPE = np.dtype({
     "offsets": [0, 28, 40, 48, 52, 54, 56, 57, 58, 59],
     "itemsize": 64,
 })
+
+# ft8_ap_hyp (20 bytes): 77 mask bits and 77 value bits, laid out like ft8_result.payload
+AP_HYP_DTYPE = np.dtype([("mask", "u1", (10,)), ("value", "u1", (10,))])
 
 # ft8_snr_rec (24 bytes)
 SNR_DTYPE = np.dtype({
@@ -164,6 +168,8 @@ def lib():
             "ft8_noise_floor": ([vp, vp, ctypes.c_int, i32, i32, i32, dbl, vp, vp, vp], ctypes.c_int),
             "ft8_snr": ([vp, vp, ctypes.c_int, i32, i32, i32, P, i64, vp, vp, i32, vp, i32, vp, vp], ctypes.c_int),
             "ft8_snr_last": ([vp, vp, vp, i32, i32, vp, vp], ctypes.c_int),
+            "ft8_set_ap": ([vp, vp, i32, i32], ctypes.c_int),
+            "ft8_ap_decode": ([vp, vp, vp, i32, i32, vp, vp], ctypes.c_int),
         }
         stale_ok = os.environ.get("FT8HIP_ALLOW_STALE") == "1"
         for name, (args, res) in sig.items():
@@ -185,7 +191,7 @@ def lib():
 
 # csrc files hashed into FT8_BUILD_ID, in the Makefile's ID_FILES order
 _ID_FILES = ("capi.hip", "stft.hip", "stft3840.hip", "sync.hip", "bp.hip", "tx.hip", "subtract.hip", "drift.hip",
-             "msg.hip", "snr.hip", "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "heap_replay.h", "msg77.h",
+             "msg.hip", "snr.hip", "ap.hip", "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "heap_replay.h", "msg77.h",
              "div_shared.h",
              "../../include/ft8hip.h",
              "Makefile")
@@ -214,7 +220,8 @@ EXPORTED_SYMBOLS = (
     "ft8_encode", "ft8_synthesize", "ft8_subtract", "ft8_stft_argmax", "ft8_drift_fit", "ft8_drift_correct",
     "ft8_build_id", "ft8_build_flags", "ft8_replay_stage", "ft8_set_timing_stages", "ft8_sync_score",
     "ft8_pack_bytes", "ft8_pack_decodes", "ft8_subtract_fits", "ft8_stft_method", "ft8_stft_screen_stats",
-    "ft8_unpack77", "ft8_unpack77_host", "ft8_hash_call", "ft8_noise_floor", "ft8_snr", "ft8_snr_last")
+    "ft8_unpack77", "ft8_unpack77_host", "ft8_hash_call", "ft8_noise_floor", "ft8_snr", "ft8_snr_last",
+    "ft8_set_ap", "ft8_ap_decode")
 
 
 def limits():
@@ -293,6 +300,16 @@ class Context:
         grid's resident waves per SIMD (1..4)."""
         self.check(lib().ft8_set_pipeline(self.handle, int(chunk_slots), int(n_streams), int(bp_waves_per_simd)),
                    "ft8_set_pipeline")
+
+    def set_ap(self, hyps=(), max_hard_errors: int = 174):
+        """ft8_set_ap: the context's a-priori hypotheses, [(mask bytes, value bytes)] as ap.ap_hypothesis
+        builds them (empty: clear), and the hard-error limit of an accepted AP decode (174: none)."""
+        h = np.zeros(max(len(hyps), 1), dtype=AP_HYP_DTYPE)
+        for i, (m, v) in enumerate(hyps):
+            h["mask"][i] = np.frombuffer(bytes(m), dtype=np.uint8)
+            h["value"][i] = np.frombuffer(bytes(v), dtype=np.uint8)
+        self.check(lib().ft8_set_ap(self.handle, h.ctypes.data_as(ctypes.c_void_p), len(hyps), int(max_hard_errors)),
+                   "ft8_set_ap")
 
     def replay(self, stage: str, reps: int = 1, stream=None):
         """ft8_replay_stage: re-launch one kernel of the last ft8_decode_batch `reps` times."""

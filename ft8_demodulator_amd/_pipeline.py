@@ -201,7 +201,20 @@ class SlotDecoder:
 
     def __init__(self, sample_rate=12000, bins_per_tone=2, steps_per_symbol=2, max_candidates=20,
                  min_score=10, max_iterations=20, freq_min=None, freq_max=None, time_min=None,
-                 time_max=None, device=None, flags=0, max_results_per_slot=None, context=None):
+                 time_max=None, device=None, flags=0, max_results_per_slot=None, context=None, ap=None,
+                 ap_max_hard_errors=None):
+        """ap: a-priori patterns (ap.ap_hypothesis, e.g. ["CQ ? ?", "K1ABC ? ?"], tried in order on every
+        candidate BP fails on; at most 8) -- sets FT8_FLAG_AP; None: plain decoding.  ap_max_hard_errors:
+        the most hard decisions of an accepted AP decode that may contradict the received LLRs' signs
+        (default ap.DEFAULT_MAX_HARD_ERRORS = 36; 174: no limit)."""
+        from . import ap as _ap
+        self.ap_patterns = None if ap is None else tuple(ap)
+        self.ap_hyps = None if ap is None else [_ap.ap_hypothesis(p) for p in self.ap_patterns]
+        self.ap_max_hard_errors = int(_ap.DEFAULT_MAX_HARD_ERRORS if ap_max_hard_errors is None else ap_max_hard_errors)
+        if ap is not None:
+            if not 1 <= len(self.ap_hyps) <= _lib.FT8_AP_MAX_HYP:
+                raise ValueError(f"ap takes 1..{_lib.FT8_AP_MAX_HYP} patterns")
+            flags |= _lib.FT8_FLAG_AP
         self.kw = dict(sample_rate=sample_rate, bins_per_tone=bins_per_tone, steps_per_symbol=steps_per_symbol,
                        freq_min=freq_min, freq_max=freq_max, time_min=time_min, time_max=time_max)
         self.max_candidates = int(max_candidates)
@@ -260,6 +273,8 @@ class SlotDecoder:
             counts[:n_slots].zero_()
             return out, counts[:n_slots]
         p = make_params(plan, self.max_candidates, self.min_score, self.max_iterations, self.flags)
+        if self.ap_hyps is not None:  # a host-side setting; the context may serve other decoders too
+            self.ctx.set_ap(self.ap_hyps, self.ap_max_hard_errors)
         rc = _lib.lib().ft8_decode_batch(self.ctx.handle, _lib.ptr(x), int(code), n, n_slots, n,
                                          ctypes.byref(p), _lib.ptr(out), _lib.ptr(counts), self.cap,
                                          _lib.stream_handle(torch.device("cuda", self.device)))

@@ -156,6 +156,11 @@ struct ft8_ctx {
     int sps, bpt;
   } snr_batch{};
   DevBuf snr_A, snr_N0;
+  // a-priori decoding (ft8_set_ap): the hypotheses, the hard-error limit, and the AP pass's scratch
+  // (ApLaunch), sized for the records of one ft8_decode_batch / ft8_ap_decode
+  std::vector<ft8_ap_hyp> ap_hyps;
+  int ap_max_hard = FT8_LDPC_N;
+  DevBuf ap_amax, ap_list, ap_count, ap_cand, ap_score, ap_llr, ap_plain, ap_res;
   // the stream of the last entry point that enqueued work, and an event recorded on it after that
   // work (StreamOrder): a call on another stream first waits for it
   hipStream_t last_stream = nullptr;
@@ -719,7 +724,7 @@ SelScratch sel_scratch_at(const ft8_ctx* c, int slot0, const Grid& g, int N, boo
 int check_search_params(ft8_ctx* c, const ft8_params* p, bool limit_first) {
   if (p->steps_per_symbol <= 0 || p->bins_per_tone <= 0) return fail(c, FT8_E_ARG, "bad oversampling factors");
   const bool over = p->max_candidates > kMaxCandidates;
-  if ((p->flags & ~(FT8_FLAG_TOPK | FT8_FLAG_SUBTRACT)) && !(limit_first && over))
+  if ((p->flags & ~(FT8_FLAG_TOPK | FT8_FLAG_SUBTRACT | FT8_FLAG_AP)) && !(limit_first && over))
     return fail(c, FT8_E_ARG, "unknown bits in ft8_params.flags");
   if (over) return fail(c, FT8_E_RANGE, "max_candidates > " + std::to_string(kMaxCandidates) + " is not supported");
   return FT8_OK;
@@ -802,6 +807,74 @@ int do_sync_select(ft8_ctx* c, const void* d_wf, int wf_f64, int n_slots, int T,
   return FT8_OK;
 }
 
+// ---- a-priori decoding ---------------------------------------------------------------------------
+// the AP pass's scratch for n_records records in n_slots lists (ft8hip.h states the sizes)
+int ensure_ap_scratch(ft8_ctx* c, size_t n_slots, size_t n_records) {
+  int rc;
+  if ((rc = ensure(c, c->ap_amax, sizeof(double) * n_records))) return rc;
+  if ((rc = ensure(c, c->ap_list, sizeof(int32_t) * n_records))) return rc;
+  if ((rc = ensure(c, c->ap_count, sizeof(int32_t) * n_slots))) return rc;
+  if ((rc = ensure(c, c->ap_cand, sizeof(int32_t) * 2 * n_records))) return rc;
+  if ((rc = ensure(c, c->ap_score, sizeof(double) * n_records))) return rc;
+  if ((rc = ensure(c, c->ap_llr, sizeof(double) * FT8_LDPC_N * n_records))) return rc;
+  if ((rc = ensure(c, c->ap_plain, (size_t)FT8_LDPC_N * n_records))) return rc;
+  return ensure(c, c->ap_res, sizeof(ft8_result) * n_records);
+}
+
+// The AP pass over res[n_slots][N] and llr[n_slots][N][174], the context's hypotheses one after
+// another (ap.hip).  The pass's scratch starts at slot `slot0` of the buffers ensure_ap_scratch sized
+// (record slot0 * N), so the chunks of a pipelined batch do not share any; `counter` is the k_bp claim
+// counter the pass's launches draw their tickets from.
+int ap_pass(ft8_ctx* c, const double* llr, ft8_result* res, const int32_t* cand_count, const int32_t* cand_in,
+            const double* score_in, int n_slots, int N, int slot0, int max_iterations, int16_t* hard, int counter,
+            hipStream_t s) {
+  const size_t r0 = (size_t)slot0 * N;
+  ApLaunch A{};
+  A.llr = llr;
+  A.res = res;
+  A.cand_count = cand_count;
+  A.cand_in = cand_in;
+  A.score_in = score_in;
+  A.n_slots = n_slots;
+  A.N = N;
+  A.max_hard = c->ap_max_hard;
+  A.amax = c->ap_amax.as<double>() + r0;
+  A.list = c->ap_list.as<int32_t>() + r0;
+  A.count = c->ap_count.as<int32_t>() + slot0;
+  A.cand = c->ap_cand.as<int32_t>() + 2 * r0;
+  A.score = c->ap_score.as<double>() + r0;
+  A.llr_h = c->ap_llr.as<double>() + (size_t)FT8_LDPC_N * r0;
+  A.plain = c->ap_plain.as<uint8_t>() + (size_t)FT8_LDPC_N * r0;
+  A.res_h = c->ap_res.as<ft8_result>() + r0;
+  A.hard = hard;
+  hipError_t e = launch_ap_amax(A, s);
+  if (e != hipSuccess) return hipfail(c, e, "ap launch");
+  BpLaunch B{};
+  B.cand = A.cand;
+  B.cand_score = A.score;
+  B.cand_count = A.count;
+  B.N = N;
+  B.n_slots = n_slots;
+  B.n_items = n_slots * N;
+  B.mode = 0;
+  B.max_iterations = max_iterations;
+  B.llr_in = A.llr_h;
+  B.plain_out = const_cast<uint8_t*>(A.plain);  // k_bp writes what k_ap_merge reads
+  B.res = const_cast<ft8_result*>(A.res_h);
+  B.work = c->work.as<unsigned long long>() + counter;
+  B.work_base = &c->work_base[counter];
+  wire_bp_stats(c, B);
+  B.grid_waves = c->bp_waves;
+  for (size_t h = 0; h < c->ap_hyps.size(); ++h) {
+    A.hyp = c->ap_hyps[h];
+    A.h = (int)h;
+    if ((e = launch_ap_prepare(A, s)) != hipSuccess) return hipfail(c, e, "ap launch");
+    if ((e = launch_bp(B, s)) != hipSuccess) return hipfail(c, e, "ap bp launch");
+    if ((e = launch_ap_merge(A, s)) != hipSuccess) return hipfail(c, e, "ap launch");
+  }
+  return FT8_OK;
+}
+
 int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
                 int64_t slot_stride, const ft8_params* p, ft8_result* d_out, int32_t* d_counts, int32_t cap,
                 hipStream_t s) {
@@ -818,8 +891,10 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
   const int csz = (c->n_streams > 0 && c->chunk_slots > 0) ? c->chunk_slots : n_slots;
   const int n_chunks = (n_slots + csz - 1) / csz;
   const int n_str = (c->n_streams > 0 && n_chunks > 1) ? std::min(c->n_streams, n_chunks) : 0;
-  // k_bp claim counters: [0] belongs to ft8_bp (a caller stream), [1 + k] to chunk k
-  if ((rc = ensure_work(c, n_chunks + 1, s))) return rc;
+  // k_bp claim counters: [0] belongs to ft8_bp / ft8_ap_decode (a caller stream), [1 + k] to chunk k,
+  // [1 + n_chunks + k] to chunk k's a-priori pass
+  const bool ap = (p->flags & FT8_FLAG_AP) != 0;
+  if ((rc = ensure_work(c, (ap ? 2 : 1) * n_chunks + 1, s))) return rc;
   hipError_t e = hipSuccess;
   if (n_str > 0) {
     while ((int)c->streams.size() < n_str) {
@@ -878,6 +953,10 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     B.warn = sc.warn;
     if ((rc = timed_launch(c, kLlr, cs, "llr launch", [&] { return launch_llr(B, cs); }))) return rc;
     if ((rc = timed_launch(c, kBp, cs, "bp launch", [&] { return launch_bp(B, cs); }))) return rc;
+    // the tie order k_compact applies permutes positions, not records, so AP works on res_all as it is
+    if (ap && (rc = ap_pass(c, B.llr_in, B.res, cand_count, cand, cand_score, ns, N, c0, p->max_iterations, nullptr,
+                            1 + n_chunks + k, cs)))
+      return rc;
     CompactLaunch C{};
     C.res = B.res;
     C.cand_count = cand_count;
@@ -896,7 +975,7 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     if ((e = hipEventRecord(c->joins[i], c->streams[i])) != hipSuccess) return hipfail(c, e, "join");
     if ((e = hipStreamWaitEvent(s, c->joins[i], 0)) != hipSuccess) return hipfail(c, e, "join wait");
   }
-  c->replay_ok = n_chunks == 1;
+  c->replay_ok = n_chunks == 1 && !ap;  // a replayed k_bp would overwrite the rescued records
   return FT8_OK;
 }
 
@@ -1307,6 +1386,37 @@ int ft8_bp(ft8_ctx* c, const double* d_llr, int32_t n, int32_t max_iterations, u
   return timed_launch(c, kBp, s, "bp launch", [&] { return launch_bp(L, s); });
 }
 
+int ft8_set_ap(ft8_ctx* c, const ft8_ap_hyp* hyps, int32_t n, int32_t max_hard_errors) {
+  if (!c || n < 0 || (n > 0 && !hyps)) return fail(c, FT8_E_ARG, "bad argument");
+  if (n > FT8_AP_MAX_HYP) return fail(c, FT8_E_RANGE, "more than " + std::to_string(FT8_AP_MAX_HYP) + " hypotheses");
+  if (max_hard_errors < 0 || max_hard_errors > FT8_LDPC_N) return fail(c, FT8_E_ARG, "max_hard_errors outside [0, 174]");
+  for (int i = 0; i < n; ++i)
+    if ((hyps[i].mask[9] | hyps[i].value[9]) & 7) return fail(c, FT8_E_ARG, "a hypothesis bit outside the 77 message bits");
+  c->ap_hyps.assign(hyps, hyps + n);
+  c->ap_max_hard = max_hard_errors;
+  return FT8_OK;
+}
+
+int ft8_ap_decode(ft8_ctx* c, const double* d_llr, ft8_result* d_res, int32_t n, int32_t max_iterations,
+                  int16_t* d_hard, void* stream) {
+  StreamOrder order_(c, (hipStream_t)stream);
+  if (c) c->replay_ok = c->snr_ok = false;
+  if (!c || n < 0 || (n > 0 && (!d_llr || !d_res))) return fail(c, FT8_E_ARG, "bad argument");
+  if (c->ap_hyps.empty()) return fail(c, FT8_E_ARG, "no hypotheses set (ft8_set_ap)");
+  if (n == 0) return FT8_OK;
+  DeviceGuard dg(c->device);
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = ensure_work(c, 1, s))) return rc;  // counter [0], as ft8_bp: both run on a caller stream, in order
+  if ((rc = ensure_ap_scratch(c, 1, (size_t)n))) return rc;
+  if (d_hard) {
+    hipError_t e = hipMemsetAsync(d_hard, 0xFF, sizeof(int16_t) * (size_t)n, s);  // -1 throughout
+    if (e != hipSuccess) return hipfail(c, e, "memset");
+  }
+  // records without slot structure: one list of n
+  return ap_pass(c, d_llr, d_res, nullptr, nullptr, nullptr, 1, n, 0, max_iterations, d_hard, 0, s);
+}
+
 int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
                      int64_t slot_stride, const ft8_params* p, ft8_result* d_out, int32_t* d_counts,
                      int32_t cap, void* stream) {
@@ -1323,6 +1433,10 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   std::string why;
   int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
   if (rc) return fail(c, rc, why);
+  if (p->flags & FT8_FLAG_AP) {  // also where there is nothing to search
+    if (p->flags & FT8_FLAG_SUBTRACT) return fail(c, FT8_E_UNSUPPORTED, "FT8_FLAG_AP with FT8_FLAG_SUBTRACT is not supported");
+    if (c->ap_hyps.empty()) return fail(c, FT8_E_ARG, "FT8_FLAG_AP without hypotheses (ft8_set_ap)");
+  }
   const int T = p->t_hi - p->t_lo, F = p->f_hi - p->f_lo;
   const bool f64 = is_f64_dtype(dtype);
   const int N = p->max_candidates;
@@ -1343,6 +1457,7 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   if ((rc = ensure(c, c->res_all, sizeof(ft8_result) * (size_t)n_slots * N))) return rc;
   if ((rc = ensure(c, c->llr, sizeof(double) * FT8_LDPC_N * (size_t)n_slots * N))) return rc;
   if ((rc = ensure_sel_scratch(c, n_slots, gr, N, f64))) return rc;
+  if ((p->flags & FT8_FLAG_AP) && (rc = ensure_ap_scratch(c, (size_t)n_slots, (size_t)n_slots * N))) return rc;
   if (!(p->flags & FT8_FLAG_SUBTRACT)) {
     if ((rc = decode_pass(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, d_out, d_counts, cap, s))) return rc;
     remember_snr_batch(c, p, g, n_slots, T, F, cap, f64);

@@ -282,6 +282,34 @@ struct CompactLaunch {
 };
 hipError_t launch_compact(const CompactLaunch& a, hipStream_t s);
 
+// ---- a-priori decoding (ap.hip) ----------------------------------------------------------------
+// One hypothesis' retry of the failed candidates of res[n_slots][N] (ft8hip.h, "a-priori decoding"):
+// k_ap_amax (once per AP pass) -> per hypothesis: k_ap_list + k_ap_clamp, launch_bp in mode 0 over the
+// compacted lists (cand / score / count below as its candidate lists, llr_h as its LLRs, plain and
+// res_h as its outputs), k_ap_merge.  Every array is [n_slots][N] (x 174 for llr / llr_h / plain).
+struct ApLaunch {
+  const double* llr;           // the LLRs plain BP consumed
+  ft8_result* res;             // in / out: the records plain BP wrote
+  const int32_t* cand_count;   // [n_slots], null: every slot holds N records
+  const int32_t* cand_in;      // nullable [n_slots][N][2] and [n_slots][N]: the candidates' positions and
+  const double* score_in;      // scores (copied to the compacted lists; zeros without them)
+  int n_slots, N;
+  ft8_ap_hyp hyp;              // the hypothesis of this attempt, by value
+  int h, max_hard;
+  double* amax;                // a = 1.01 max |L| of every candidate, 0 where it is not to be retried
+  int32_t* list;               // per slot: original indices of the candidates this attempt retries
+  int32_t* count;              // [n_slots] their number
+  int32_t* cand;               // compacted [n_slots][N][2]
+  double* score;               // compacted
+  double* llr_h;               // compacted, clamped LLRs
+  const uint8_t* plain;        // launch_bp's hard decisions of the compacted lists
+  const ft8_result* res_h;     // launch_bp's records of them
+  int16_t* hard;               // nullable [n_slots * N], by original index: hard_h of an accepted attempt
+};
+hipError_t launch_ap_amax(const ApLaunch& a, hipStream_t s);
+hipError_t launch_ap_prepare(const ApLaunch& a, hipStream_t s);  // k_ap_list, k_ap_clamp
+hipError_t launch_ap_merge(const ApLaunch& a, hipStream_t s);
+
 // ft8_pack_decodes (bp.hip): one workgroup packs a batch's decodes for the all-gather
 inline __host__ __device__ int64_t pack_header_bytes(int n_slots) { return 8 + ((4 * (int64_t)n_slots + 7) & ~7ll); }
 hipError_t launch_pack(const ft8_result* rec, const int32_t* counts, int n_slots, int cap, int capacity,

@@ -88,15 +88,13 @@ def decode_ft8_from_wave(wave_path: str, freq_min: float = None, freq_max: float
                               device=device)
 
 
-def decode_ft8_from_wave_snr(wave_path: str, freq_min: float = None, freq_max: float = None, time_min: float = None,
-                             time_max: float = None, bins_per_tone: int = 2, steps_per_symbol: int = 2,
-                             max_candidates: int = 20, min_score: float = 10, max_iterations: int = 20,
-                             device=None) -> tuple:
-    """decode_ft8_from_wave with the signal report (build-defined): -> (results, snr_db), the same
-    5-tuples and one SNR in 2500 Hz (dB, float) per result, measured on the device on the waterfall
-    of the same decode (SlotDecoder.snr / ft8_snr_last)."""
+def _decode_with_reports(wave_path, freq_min, freq_max, time_min, time_max, bins_per_tone, steps_per_symbol,
+                         max_candidates, min_score, max_iterations, device, ap=None, ap_max_hard_errors=None):
+    """One file through SlotDecoder (any PCM width) with the signal report -> (results, snr_db, patterns):
+    patterns[i] is the a-priori pattern that rescued result i, None for a plain decode."""
     import torch
     from . import _lib
+    from .ap import ap_index
     from ._pipeline import SlotDecoder, make_plan, records_to_results
     data, dtype, sample_rate = _read_raw(wave_path)
     _lib.require_gpu()
@@ -110,17 +108,44 @@ def decode_ft8_from_wave_snr(wave_path: str, freq_min: float = None, freq_max: f
     plan = make_plan(int(x.shape[0]), sample_rate, bins_per_tone, steps_per_symbol, freq_min, freq_max, time_min,
                      time_max)
     if plan.empty or max_candidates <= 0:
-        return [], []
+        return [], [], []
     dec = SlotDecoder(sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score, max_iterations,
-                      freq_min, freq_max, time_min, time_max, device=dev)
+                      freq_min, freq_max, time_min, time_max, device=dev, ap=ap, ap_max_hard_errors=ap_max_hard_errors)
     recs, _, reps = dec._records_and_texts(x.unsqueeze(0), code, snr=True)
     snr_db = [float(r["snr_db"]) if int(r["status"]) < 2 else float("nan") for r in reps[0]]
-    return records_to_results(recs[0], sample_rate, bins_per_tone, False), snr_db
+    patterns = [dec.ap_patterns[ap_index(r) - 1] if ap_index(r) else None for r in recs[0]]
+    return records_to_results(recs[0], sample_rate, bins_per_tone, False), snr_db, patterns
 
 
-def _print_results(results, text: bool = False, snr=None):
+def decode_ft8_from_wave_snr(wave_path: str, freq_min: float = None, freq_max: float = None, time_min: float = None,
+                             time_max: float = None, bins_per_tone: int = 2, steps_per_symbol: int = 2,
+                             max_candidates: int = 20, min_score: float = 10, max_iterations: int = 20,
+                             device=None) -> tuple:
+    """decode_ft8_from_wave with the signal report (build-defined): -> (results, snr_db), the same
+    5-tuples and one SNR in 2500 Hz (dB, float) per result, measured on the device on the waterfall
+    of the same decode (SlotDecoder.snr / ft8_snr_last)."""
+    return _decode_with_reports(wave_path, freq_min, freq_max, time_min, time_max, bins_per_tone, steps_per_symbol,
+                                max_candidates, min_score, max_iterations, device)[:2]
+
+
+def decode_ft8_from_wave_ap(wave_path: str, ap, ap_max_hard_errors: int = None, freq_min: float = None,
+                            freq_max: float = None, time_min: float = None, time_max: float = None,
+                            bins_per_tone: int = 2, steps_per_symbol: int = 2, max_candidates: int = 20,
+                            min_score: float = 10, max_iterations: int = 20, device=None) -> tuple:
+    """decode_ft8_from_wave with a-priori decoding (build-defined): candidates BP fails on are retried
+    with the patterns `ap` (ap.ap_hypothesis, e.g. ["CQ ? ?"]) -> (results, patterns, snr_db): the same
+    5-tuples in candidate order, per result the pattern that rescued it (None for a plain decode), and
+    its SNR in 2500 Hz as decode_ft8_from_wave_snr gives it."""
+    results, snr_db, patterns = _decode_with_reports(
+        wave_path, freq_min, freq_max, time_min, time_max, bins_per_tone, steps_per_symbol, max_candidates, min_score,
+        max_iterations, device, ap=ap, ap_max_hard_errors=ap_max_hard_errors)
+    return results, patterns, snr_db
+
+
+def _print_results(results, text: bool = False, snr=None, ap=None):
     """text: one extra `Message:` line per result, the payload unpacked to message text.  snr (one
-    value per result): one extra `SNR:` line per result, dB in 2500 Hz."""
+    value per result): one extra `SNR:` line per result, dB in 2500 Hz.  ap (one pattern or None per
+    result): one extra `AP: <pattern>` line for every a-priori decode."""
     if not results:
         print("No FT8 messages decoded")
         return
@@ -139,6 +164,8 @@ def _print_results(results, text: bool = False, snr=None):
         print(f"Payload: {message.payload.hex()}")
         if text:
             print(f"Message: {texts.pop(0)}")
+        if ap is not None and ap[k] is not None:
+            print(f"AP: {ap[k]}")
         print(f"CRC check: {status.crc_calculated}")
         print(f"LDPC errors: {status.ldpc_errors}")
         print("-" * 50)
@@ -183,11 +210,32 @@ def main(argv=None):
     parser.add_argument("--correction", type=bool, default=False)
     parser.add_argument("--text", action="store_true", help="print each payload's message text as well")
     parser.add_argument("--snr", action="store_true", help="print each decode's SNR in 2500 Hz as well")
+    parser.add_argument("--ap", action="append", metavar="PATTERN",
+                        help='retry failed candidates with these message bits known, e.g. "CQ ? ?" or '
+                             '"K1ABC ? ?" (repeatable, tried in order; an AP decode is marked with its pattern)')
+    parser.add_argument("--ap-max-hard-errors", type=int, default=None,
+                        help="most hard decisions of an AP decode that may contradict the received bits (default 36)")
     args = parser.parse_args(argv)
     for path in args.wave_file:
         if not os.path.exists(path):
             print(f"Error: File {path} does not exist")
             sys.exit(1)
+    if args.ap:
+        # like --snr: one file at a time, each decoded once on the batched path
+        if args.correction:
+            decode_ft8_from_wave(args.wave_file[0], correction=True)  # raises as without --ap
+        per_file = []
+        for path in args.wave_file:
+            results, patterns, snr = decode_ft8_from_wave_ap(
+                path, args.ap, args.ap_max_hard_errors, freq_min=args.freq_min, freq_max=args.freq_max,
+                time_min=args.time_min, time_max=args.time_max, bins_per_tone=args.bins_per_tone,
+                steps_per_symbol=args.steps_per_symbol, max_candidates=args.max_candidates, min_score=args.min_score,
+                max_iterations=args.max_iterations)
+            if len(args.wave_file) > 1:
+                print(f"\n== {path}")
+            _print_results(results, args.text, snr if args.snr else None, patterns)
+            per_file.append(results)
+        return per_file if len(args.wave_file) > 1 else per_file[0]
     if args.snr:
         # the report comes from the decode's own waterfall: one file at a time, each decoded once
         if args.correction:

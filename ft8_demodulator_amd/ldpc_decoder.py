@@ -28,3 +28,11 @@ def bp_decode_batch(codewords: np.ndarray, max_iterations: int):
     """Batched bp_decode: LLRs [n, 174] -> (plain [n, 174] uint8, min_errors [n])."""
     plain, rec = _device.bp(np.asarray(codewords, dtype=np.float64).reshape(-1, FTX_LDPC_N), max_iterations)
     return plain, rec["ldpc_errors"].astype(np.int64)
+
+
+def ap_decode_batch(llrs: np.ndarray, records: np.ndarray, max_iterations: int):
+    """A-priori retry (ft8_ap_decode) of the failed records ft8_bp wrote from llrs [n, 174], with the
+    hypotheses of the thread's context (_lib.context().set_ap): -> (updated records, hard int16 [n]:
+    the hard errors of an accepted AP decode, -1 otherwise).  The contract is in include/ft8hip.h;
+    ap.ap_restate is its NumPy restatement."""
+    return _device.ap_decode(llrs, records, max_iterations)

@@ -70,8 +70,8 @@ typedef struct ft8_params {
                                nperseg 1921); sample_rate is then ignored.  0: use sample_rate. */
 } ft8_params;
 
-/* ft8_params.flags.  Both are build-defined extensions OUTSIDE reference parity (the reference
- * has neither); with flags = 0 every result is the reference's.
+/* ft8_params.flags.  All are build-defined extensions OUTSIDE reference parity (the reference
+ * has none of them); with flags = 0 every result is the reference's.
  *   FT8_FLAG_TOPK      candidate selection keeps the max_candidates highest passing scores
  *                      (ties in scan order), sorted by score descending, instead of reproducing
  *                      ft8_find_candidates' heap quirk (ft8_decode.py:131-137, which keeps the
@@ -80,9 +80,14 @@ typedef struct ft8_params {
  *                      pass 1 is re-modulated (ft8_encode + GFSK), fitted to the slot (time/
  *                      frequency refinement, per-symbol complex amplitude) and subtracted, and
  *                      the residual is decoded again.  New messages are appended after the
- *                      pass-1 results with pass_index = 1.  F32 and I16 samples only. */
+ *                      pass-1 results with pass_index = 1.  F32 and I16 samples only.
+ *   FT8_FLAG_AP        ft8_decode_batch retries every candidate BP failed on with the context's
+ *                      a-priori hypotheses (ft8_set_ap; "a-priori decoding" below).  Rescued
+ *                      candidates come out in candidate order among the plain decodes, with
+ *                      pass_index >> 4 = hypothesis index + 1.  Not with FT8_FLAG_SUBTRACT. */
 #define FT8_FLAG_TOPK 1
 #define FT8_FLAG_SUBTRACT 2
+#define FT8_FLAG_AP 4
 
 /* One decoded (or attempted) candidate, 40 bytes, 8-byte aligned. */
 typedef struct ft8_result {
@@ -96,7 +101,8 @@ typedef struct ft8_result {
   uint16_t cand_index;     /* position in the reference candidate order */
   uint8_t payload[10];     /* FT8Message.payload (77 bits, [9] & 0xF8) */
   uint8_t ok;              /* 1: LDPC converged and CRC matched (ft8_decode_candidate True) */
-  uint8_t pass_index;      /* 0: decoded from the slot; 1: decoded after subtraction (FT8_FLAG_SUBTRACT) */
+  uint8_t pass_index;      /* low nibble 0: decoded from the slot; 1: decoded after subtraction (FT8_FLAG_SUBTRACT);
+                              high nibble 0: plain BP; h + 1: a-priori hypothesis h (FT8_FLAG_AP, ft8_ap_decode) */
 } ft8_result;
 
 /* One transmitted FT8 signal for ft8_synthesize, 40 bytes. */
@@ -204,7 +210,9 @@ int ft8_bp(ft8_ctx* ctx, const double* d_llr, int32_t n, int32_t max_iterations,
  * Replaces decode_ft8_message (ft8_decode.py:288-394) for a batch of independent slots:
  * STFT -> sync/select -> LLR -> BP -> CRC, all on the device.  Writes, per slot s, the successful
  * decodes in candidate order to d_out[s][0 .. d_counts[s]) (capped at max_results_per_slot;
- * d_counts holds the uncapped count). */
+ * d_counts holds the uncapped count).  With FT8_FLAG_AP the a-priori pass ("a-priori decoding"
+ * below) runs between BP and the compaction, on the batch's own LLRs and records: FT8_E_ARG when the
+ * context holds no hypotheses, FT8_E_UNSUPPORTED together with FT8_FLAG_SUBTRACT. */
 int ft8_decode_batch(ft8_ctx* ctx, const void* d_samples, int dtype, int64_t n_samples,
                      int32_t n_slots, int64_t slot_stride, const ft8_params* p,
                      ft8_result* d_out, int32_t* d_counts, int32_t max_results_per_slot,
@@ -325,6 +333,46 @@ int ft8_snr(ft8_ctx* ctx, const void* d_wf, int wf_f64, int32_t n_slots, int32_t
  * Three kernels (ft8_noise_floor's two, ft8_snr's one).  A and N0 live in the context's scratch, so the call takes part in the cross-stream order. */
 int ft8_snr_last(ft8_ctx* ctx, const ft8_result* d_records, const int32_t* d_counts, int32_t n_slots, int32_t cap,
                  ft8_snr_rec* d_out, void* stream);
+
+/* ---- a-priori decoding: retry failed candidates with known message bits ----------------------------
+ * Build-defined, outside reference parity (the reference decodes every candidate once).  A candidate
+ * enters a-priori (AP) decoding when plain BP left ok == 0.  With L[174] its LLRs as BP consumed them
+ * (normalised doubles, positive = bit 1) and the context's hypotheses h = 0 .. H-1 (77 mask bits and
+ * 77 value bits each, laid out like ft8_result.payload: MSB first, [9] & 0xF8):
+ *   a        = 1.01 * max_i |L[i]| (one multiply in double); a NaN (any L[i] NaN) or a == 0 leaves the
+ *              candidate as it is.  L[i] is finite or NaN.
+ *   L_h[i]   = +a where i < 77 and mask bit i and value bit i are set, -a where mask bit i is set and
+ *              value bit i is not, L[i] everywhere else
+ *   attempt h = bp_decode(L_h, max_iterations) and the reference tail, exactly as ft8_bp runs them;
+ *              it is accepted when (1) the tail says ok, (2) the decoded payload agrees with value on
+ *              every masked bit, and (3) hard_h = #{ i < 174 : plain_h[i] != (L[i] > 0) } <=
+ *              max_hard_errors -- counted against the UNCLAMPED L.
+ * The first accepted h wins (hypotheses run one after another; a rescued candidate is not retried).
+ * The winning record gets ok = 1, that attempt's payload, crc_extracted, crc_calculated and
+ * ldpc_errors, and pass_index |= (h + 1) << 4; score, slot, abs_time, abs_freq and cand_index do not
+ * change.  A candidate no hypothesis rescues keeps the record plain BP wrote.
+ * Scratch (context-owned, grow-only) for n records: 174 * 8 n bytes of clamped LLRs, 174 n bytes of
+ * hard decisions, and 68 n bytes of lists and records (n = n_slots * max_candidates in
+ * ft8_decode_batch). */
+typedef struct ft8_ap_hyp {
+  uint8_t mask[10];
+  uint8_t value[10];
+} ft8_ap_hyp; /* 20 bytes */
+#define FT8_AP_MAX_HYP 8
+
+/* The context's hypotheses (a context setting, like ft8_set_pipeline): hyps[n] in HOST memory is
+ * copied into the context, from where every AP launch takes its hypothesis as a kernel argument.
+ * n = 0 clears them; n > FT8_AP_MAX_HYP: FT8_E_RANGE; a mask or value bit outside the 77, or
+ * max_hard_errors outside [0, 174] (174: no limit): FT8_E_ARG. */
+int ft8_set_ap(ft8_ctx* ctx, const ft8_ap_hyp* hyps, int32_t n, int32_t max_hard_errors);
+/* The stage call, on records as ft8_bp wrote them from the same d_llr[n][174]: records with ok == 0
+ * are tried against the context's hypotheses and updated in place per the contract above (the n
+ * records are one list).  d_hard[n] (nullable): hard_h of an accepted AP decode, -1 otherwise.  Per
+ * hypothesis three small kernels and one k_bp launch (whose work ft8_get_counters counts with the
+ * plain launches').  Uses the context's scratch, so it takes part in the cross-stream order.  n = 0
+ * does nothing; no hypotheses set: FT8_E_ARG. */
+int ft8_ap_decode(ft8_ctx* ctx, const double* d_llr, ft8_result* d_res, int32_t n, int32_t max_iterations,
+                  int16_t* d_hard, void* stream);
 
 /* Per-slot flags of the last selection (copied device->device into d_out[n_slots]):
  * bit 0: an exact score tie reached a heap comparison (the reference raises TypeError there,
@@ -470,7 +518,8 @@ const char* ft8_build_flags(void);
  * (same buffers, same arguments; every stage is idempotent on its inputs), so a kernel's duration
  * can be measured by wall clock over back-to-back launches, without events between stages.  Valid
  * while the caller's buffers of that call are alive and until any other entry point of this
- * context runs (FT8_E_ARG otherwise).  No reference counterpart. */
+ * context runs (FT8_E_ARG otherwise, and after an FT8_FLAG_SUBTRACT or FT8_FLAG_AP batch, whose
+ * stages are not idempotent).  No reference counterpart. */
 int ft8_replay_stage(ft8_ctx* ctx, int32_t stage, int32_t reps, void* stream);
 
 /* ---- per-stage device timing (HIP events on the caller's stream) --------------------------- */

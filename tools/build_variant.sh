@@ -15,7 +15,7 @@ BASE="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-mat
 /opt/rocm/bin/hipcc $BASE $EXTRA $3 -c $F.hip -o ../../build/var/$1_$F.o
 /opt/rocm/bin/hipcc $BASE "-DFT8_BUILD_ID=\"$SRC_ID+variant-$1:$F\"" "-DFT8_BUILD_FLAGS=\"variant $1: $F.hip $3\"" \
   -c capi.hip -o ../../build/var/$1_capi.o
-OBJS=$(for s in capi stft stft3840 sync bp tx subtract drift msg; do
+OBJS=$(for s in capi stft stft3840 sync bp tx subtract drift msg ap; do
   if [ $s = $F ] || [ $s = capi ]; then echo ../../build/var/$1_$s.o; else echo ../../build/$s.o; fi; done)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o ../../variants/$1.so $OBJS
 echo "variants/$1.so  ($F.hip: $3)"
