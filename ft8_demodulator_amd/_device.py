@@ -116,10 +116,16 @@ def llr(wf, cand_list, normalize):
     return out.cpu().numpy()
 
 
+def _llr_rows(x):
+    """LLRs (anything array-like of n * 174 values) -> float64 device tensor [n, 174]."""
+    torch = _lib.require_gpu()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, 174))).cuda()
+
+
 def normalize(x):
     torch = _lib.require_gpu()
     ctx = _lib.context()
-    a = torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, 174))).cuda()
+    a = _llr_rows(x)
     out = torch.empty_like(a)
     ctx.check(_lib.lib().ft8_normalize(ctx.handle, _lib.ptr(a), a.shape[0], _lib.ptr(out), _lib.stream_handle()),
               "ft8_normalize")
@@ -130,7 +136,7 @@ def bp(llrs, max_iterations):
     """LLRs [n, 174] -> (plain uint8 [n, 174], records structured [n])."""
     torch = _lib.require_gpu()
     ctx = _lib.context()
-    a = torch.from_numpy(np.ascontiguousarray(np.asarray(llrs, dtype=np.float64).reshape(-1, 174))).cuda()
+    a = _llr_rows(llrs)
     n = a.shape[0]
     plain = torch.zeros(n, 174, dtype=torch.uint8, device=a.device)
     res = torch.zeros(n * _lib.RESULT_DTYPE.itemsize, dtype=torch.uint8, device=a.device)
@@ -144,7 +150,7 @@ def ap_decode(llrs, records, max_iterations):
     context's a-priori hypotheses (Context.set_ap), hard int16 [n])."""
     torch = _lib.require_gpu()
     ctx = _lib.context()
-    a = torch.from_numpy(np.ascontiguousarray(np.asarray(llrs, dtype=np.float64).reshape(-1, 174))).cuda()
+    a = _llr_rows(llrs)
     n = a.shape[0]
     rec = np.ascontiguousarray(np.asarray(records, dtype=_lib.RESULT_DTYPE).reshape(-1))
     if len(rec) != n:

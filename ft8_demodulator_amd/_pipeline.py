@@ -11,6 +11,8 @@ LLR and codeword is processed by the HIP kernels of libft8hip.so.
 from __future__ import annotations
 
 import ctypes
+import os
+import sys
 from dataclasses import dataclass
 
 import numpy as np
@@ -155,13 +157,22 @@ def device_samples(wave_data, device=None, int16_is_pcm=False):
     return x, code, wf_f64
 
 
+def record_columns(recs: np.ndarray, sample_rate, bins_per_tone: int, wf_f64: bool):
+    """Device records -> (time_s, freq_hz, score), one entry per record: time_sec = abs_time /
+    sample_rate and freq_hz = (abs_freq / bins_per_tone) * 6.25 as lists of Python floats
+    (ft8_decode.py:387-388), score as an array of the waterfall's dtype."""
+    tsec = [t / sample_rate for t in recs["abs_time"].tolist()]
+    fhz = [(f / bins_per_tone) * FT8_SYMBOL_FREQ_INTERVAL_HZ for f in recs["abs_freq"].tolist()]
+    return tsec, fhz, recs["score"].astype(np.float64 if wf_f64 else np.float32)
+
+
 def records_to_results(recs: np.ndarray, sample_rate: int, bins_per_tone: int, wf_f64: bool):
     """Device records (ok only, candidate order) -> [(FT8Message, FT8DecodeStatus, time_sec,
     freq_hz, score)] exactly as decode_ft8_message returns them (ft8_decode.py:383-391).
 
-    time_sec = abs_time / sample_rate and freq_hz = (abs_freq / bins_per_tone) * 6.25 as Python
-    floats, score as the waterfall dtype's NumPy scalar.  Columns are converted once per call (the
-    per-record work is only the object construction)."""
+    time_sec, freq_hz (Python floats) and score (the waterfall dtype's NumPy scalar) are
+    record_columns': columns are converted once per call (the per-record work is only the object
+    construction)."""
     n = len(recs)
     if n == 0:
         return []
@@ -169,9 +180,7 @@ def records_to_results(recs: np.ndarray, sample_rate: int, bins_per_tone: int, w
     crc_c = recs["crc_calculated"].tolist()
     crc_e = recs["crc_extracted"].tolist()
     errs = recs["ldpc_errors"].tolist()
-    tsec = [t / sample_rate for t in recs["abs_time"].tolist()]
-    fhz = [(f / bins_per_tone) * FT8_SYMBOL_FREQ_INTERVAL_HZ for f in recs["abs_freq"].tolist()]
-    sc = recs["score"].astype(np.float64 if wf_f64 else np.float32)
+    tsec, fhz, sc = record_columns(recs, sample_rate, bins_per_tone, wf_f64)
     out = []
     for i in range(n):
         msg = FT8Message(payload=bytearray(payload[10 * i: 10 * i + 10]), hash=crc_c[i])
@@ -180,15 +189,31 @@ def records_to_results(recs: np.ndarray, sample_rate: int, bins_per_tone: int, w
     return out
 
 
-def warn_truncated(counts: np.ndarray, cap: int, stacklevel: int = 2) -> None:
+def split_slots(raw_u8: np.ndarray, dtype, counts, cap: int) -> list:
+    """A host copy of a device buffer of n_slots * cap fixed-size records -> list (per slot) of the
+    slot's first min(count, cap) records as a `dtype` array that owns its data."""
+    dtype = np.dtype(dtype)
+    n_slots = len(counts)
+    rows = raw_u8[: n_slots * cap * dtype.itemsize].view(dtype).reshape(n_slots, cap)
+    return [rows[s, : min(int(counts[s]), cap)].copy() for s in range(n_slots)]
+
+
+_PACKAGE_DIR = os.path.dirname(os.path.abspath(__file__)) + os.sep
+
+
+def warn_truncated(counts: np.ndarray, cap: int) -> None:
     """RuntimeWarning when a slot decoded more messages than its record capacity holds (the device
-    keeps the first `cap` in candidate order and counts the rest)."""
+    keeps the first `cap` in candidate order and counts the rest).  The warning names the first
+    frame outside this package: whoever called into it, through however many of its wrappers."""
     over = np.nonzero(counts > cap)[0]
     if over.size:
         import warnings
+        level, frame = 2, sys._getframe(1)
+        while frame.f_back is not None and os.path.abspath(frame.f_code.co_filename).startswith(_PACKAGE_DIR):
+            level, frame = level + 1, frame.f_back
         warnings.warn(f"{over.size} slot(s) decoded more messages than max_results_per_slot={cap} "
                       f"(e.g. slot {int(over[0])}: {int(counts[over[0]])}); the records beyond it were dropped",
-                      RuntimeWarning, stacklevel=stacklevel + 1)
+                      RuntimeWarning, stacklevel=level)
 
 
 class SlotDecoder:
@@ -231,10 +256,7 @@ class SlotDecoder:
         default_cap = max(self.max_candidates, 1) * (2 if flags & _lib.FT8_FLAG_SUBTRACT else 1)
         self.cap = int(max_results_per_slot if max_results_per_slot is not None else default_cap)
         self._plans = {}
-        self._out = None
-        self._counts = None
-        self._text = None
-        self._snr = None
+        self._bufs = {}
         self._launched = False  # whether the last run() reached ft8_decode_batch (else: nothing to decode)
 
     def plan(self, n_samples) -> Plan:
@@ -242,15 +264,20 @@ class SlotDecoder:
             self._plans[n_samples] = make_plan(n_samples, **self.kw)
         return self._plans[n_samples]
 
+    def _buf(self, name, n, dtype=None):
+        """The decoder's device buffer `name`, grown (never shrunk) to at least n elements (uint8
+        unless dtype is given); never empty, so its pointer is always valid."""
+        import torch
+        b = self._bufs.get(name)
+        if b is None or b.numel() < n:
+            b = self._bufs[name] = torch.empty(max(n, 1), dtype=dtype or torch.uint8,
+                                               device=torch.device("cuda", self.device))
+        return b
+
     def _buffers(self, n_slots):
         import torch
-        dev = torch.device("cuda", self.device)
-        need = n_slots * self.cap * _lib.RESULT_DTYPE.itemsize
-        if self._out is None or self._out.numel() < max(need, 1):
-            self._out = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        if self._counts is None or self._counts.numel() < n_slots:
-            self._counts = torch.empty(max(n_slots, 1), dtype=torch.int32, device=dev)
-        return self._out, self._counts
+        return (self._buf("out", n_slots * self.cap * _lib.RESULT_DTYPE.itemsize),
+                self._buf("counts", n_slots, torch.int32))
 
     def run(self, samples, code=None, int16_is_pcm=True):
         """Asynchronous launch on the current stream.  samples: GPU tensor [B, N] (or [N]).
@@ -282,22 +309,6 @@ class SlotDecoder:
         self._launched = True
         return out, counts[:n_slots]
 
-    def records(self, samples, code=None, int16_is_pcm=True):
-        """Synchronous: -> list (per slot) of structured ft8_result arrays (ok decodes, candidate order)."""
-        out, counts = self.run(samples, code, int16_is_pcm)
-        c = counts.cpu().numpy()
-        n_slots = len(c)
-        recs = out[: n_slots * self.cap * _lib.RESULT_DTYPE.itemsize].cpu().numpy().view(_lib.RESULT_DTYPE)
-        recs = recs.reshape(n_slots, self.cap) if n_slots else recs.reshape(0, self.cap)
-        warn_truncated(c, self.cap, stacklevel=3)
-        return [recs[s, : min(int(c[s]), self.cap)].copy() for s in range(n_slots)]
-
-    def decode(self, samples, int16_is_pcm=True):
-        """-> list (per slot) of the reference's 5-tuples."""
-        x, code, wf_f64 = device_samples(samples, self.device, int16_is_pcm=int16_is_pcm)
-        per_slot = self.records(x, code)
-        return [records_to_results(r, self.kw["sample_rate"], self.kw["bins_per_tone"], wf_f64) for r in per_slot]
-
     def _snr_last(self, out, counts):
         """ft8_snr_last for the records run() just wrote, on the same stream: -> the device buffer of
         n_slots * cap ft8_snr_rec.  A run() that had nothing to decode (an empty plan: no waterfall)
@@ -305,87 +316,78 @@ class SlotDecoder:
         import torch
         n_slots = int(counts.shape[0])
         nbytes = n_slots * self.cap * _lib.SNR_DTYPE.itemsize
-        if self._snr is None or self._snr.numel() < max(nbytes, 1):
-            self._snr = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=out.device)
+        d_snr = self._buf("snr", nbytes)
         if not self._launched:
             blank = np.zeros(n_slots * self.cap, dtype=_lib.SNR_DTYPE)
             blank["status"] = 3
-            self._snr[:nbytes].copy_(torch.from_numpy(blank.view(np.uint8)))
+            d_snr[:nbytes].copy_(torch.from_numpy(blank.view(np.uint8)))
         elif n_slots and self.cap:
             rc = _lib.lib().ft8_snr_last(self.ctx.handle, _lib.ptr(out), _lib.ptr(counts), n_slots, self.cap,
-                                         _lib.ptr(self._snr), _lib.stream_handle(out.device))
+                                         _lib.ptr(d_snr), _lib.stream_handle(out.device))
             self.ctx.check(rc, "ft8_snr_last")
-        return self._snr
+        return d_snr
 
-    def _records_and_texts(self, samples, code=None, int16_is_pcm=True, snr=False, stacklevel=4):
-        """run(), then one ft8_unpack77 (and, with snr, one ft8_snr_last) on the same stream with no
-        host sync in between, then the copies: -> (records per slot, ft8_text records per slot[,
-        ft8_snr_rec records per slot]), aligned."""
-        import torch
+    def _fetch(self, samples, code=None, int16_is_pcm=True, records=True, text=False, snr=False):
+        """run(), then with text one ft8_unpack77 and with snr one ft8_snr_last, all on the current
+        stream with no host sync in between; only then the copies to the host and the truncation
+        warning: -> (records, ft8_text records, ft8_snr_rec records), each a list per slot, aligned,
+        or None where it was not asked for."""
         out, counts = self.run(samples, code, int16_is_pcm)
         n_slots = int(counts.shape[0])
-        need = max(n_slots * self.cap * _lib.TEXT_DTYPE.itemsize, 1)
-        if self._text is None or self._text.numel() < need:
-            self._text = torch.empty(need, dtype=torch.uint8, device=out.device)
-        if n_slots and self.cap:
-            rc = _lib.lib().ft8_unpack77(self.ctx.handle, _lib.ptr(out), _lib.ptr(counts), n_slots, self.cap,
-                                         _lib.ptr(self._text), _lib.stream_handle(out.device))
-            self.ctx.check(rc, "ft8_unpack77")
+        d_text = d_snr = None
+        if text:
+            d_text = self._buf("text", n_slots * self.cap * _lib.TEXT_DTYPE.itemsize)
+            if n_slots and self.cap:
+                rc = _lib.lib().ft8_unpack77(self.ctx.handle, _lib.ptr(out), _lib.ptr(counts), n_slots, self.cap,
+                                             _lib.ptr(d_text), _lib.stream_handle(out.device))
+                self.ctx.check(rc, "ft8_unpack77")
         if snr:
             d_snr = self._snr_last(out, counts)
         c = counts.cpu().numpy()
-        recs = out[: n_slots * self.cap * _lib.RESULT_DTYPE.itemsize].cpu().numpy().view(_lib.RESULT_DTYPE)
-        txts = self._text[: n_slots * self.cap * _lib.TEXT_DTYPE.itemsize].cpu().numpy().view(_lib.TEXT_DTYPE)
-        recs, txts = recs.reshape(n_slots, self.cap), txts.reshape(n_slots, self.cap)
-        warn_truncated(c, self.cap, stacklevel=stacklevel)
-        keep = [min(int(c[s]), self.cap) for s in range(n_slots)]
-        res = ([recs[s, :k].copy() for s, k in enumerate(keep)], [txts[s, :k].copy() for s, k in enumerate(keep)])
-        if snr:
-            reps = d_snr[: n_slots * self.cap * _lib.SNR_DTYPE.itemsize].cpu().numpy().view(_lib.SNR_DTYPE)
-            reps = reps.reshape(n_slots, self.cap)
-            res += ([reps[s, :k].copy() for s, k in enumerate(keep)],)
-        return res
+        warn_truncated(c, self.cap)
+        n = n_slots * self.cap
+        return tuple(d if d is None else split_slots(d[: n * dt.itemsize].cpu().numpy(), dt, c, self.cap)
+                     for d, dt in ((out if records else None, _lib.RESULT_DTYPE), (d_text, _lib.TEXT_DTYPE),
+                                   (d_snr, _lib.SNR_DTYPE)))
+
+    def records(self, samples, code=None, int16_is_pcm=True):
+        """Synchronous: -> list (per slot) of structured ft8_result arrays (ok decodes, candidate order)."""
+        return self._fetch(samples, code, int16_is_pcm)[0]
+
+    def decode(self, samples, int16_is_pcm=True):
+        """-> list (per slot) of the reference's 5-tuples."""
+        x, code, wf_f64 = device_samples(samples, self.device, int16_is_pcm=int16_is_pcm)
+        per_slot = self.records(x, code)
+        return [records_to_results(r, self.kw["sample_rate"], self.kw["bins_per_tone"], wf_f64) for r in per_slot]
 
     def texts(self, samples, code=None, int16_is_pcm=True):
         """Synchronous: -> list (per slot) of ft8_text arrays (_lib.TEXT_DTYPE) aligned with records():
         the message text of every decode, unpacked on the device (ft8_unpack77), and dup_of, the
         slot's first record with the same payload."""
-        return self._records_and_texts(samples, code, int16_is_pcm)[1]
+        return self._fetch(samples, code, int16_is_pcm, text=True)[1]
 
     def snr(self, samples, code=None, int16_is_pcm=True):
         """Synchronous: -> list (per slot) of ft8_snr_rec arrays (_lib.SNR_DTYPE) aligned with records():
         the signal report of every decode (snr_db: SNR in 2500 Hz), measured on the device
         (ft8_snr_last) on the waterfall the decode left there.  Raises NotImplementedError for a
         decoder built with FT8_FLAG_SUBTRACT (that waterfall is the residual's)."""
-        out, counts = self.run(samples, code, int16_is_pcm)
-        d_snr = self._snr_last(out, counts)
-        c = counts.cpu().numpy()
-        n_slots = len(c)
-        reps = d_snr[: n_slots * self.cap * _lib.SNR_DTYPE.itemsize].cpu().numpy().view(_lib.SNR_DTYPE)
-        reps = reps.reshape(n_slots, self.cap)
-        warn_truncated(c, self.cap, stacklevel=3)
-        return [reps[s, : min(int(c[s]), self.cap)].copy() for s in range(n_slots)]
+        return self._fetch(samples, code, int16_is_pcm, records=False, snr=True)[2]
 
     def _message_rows(self, samples, table, unique, int16_is_pcm, snr):
         from .message import text_of
+        from .snr import snr_db_or_nan
         x, code, wf_f64 = device_samples(samples, self.device, int16_is_pcm=int16_is_pcm)
-        got = self._records_and_texts(x, code, snr=snr, stacklevel=5)  # the warning names messages()' caller
-        recs, txts = got[0], got[1]
-        fs, bpt = self.kw["sample_rate"], self.kw["bins_per_tone"]
+        recs, txts, reps = self._fetch(x, code, text=True, snr=snr)
         out = []
         for s, (r, t) in enumerate(zip(recs, txts)):
-            sc = r["score"].astype(np.float64 if wf_f64 else np.float32)
+            tsec, fhz, sc = record_columns(r, self.kw["sample_rate"], self.kw["bins_per_tone"], wf_f64)
+            db = snr_db_or_nan(reps[s]) if snr else None
             rows = []
             for i in range(len(r)):
                 if int(t["status"][i]) != 0 or (unique and int(t["dup_of"][i]) >= 0):
                     continue
                 text = table.resolve(t[i]) if table is not None else text_of(t[i])
-                row = (text, int(r["abs_time"][i]) / fs,
-                       (int(r["abs_freq"][i]) / bpt) * FT8_SYMBOL_FREQ_INTERVAL_HZ, sc[i], r[i])
-                if snr:
-                    rep = got[2][s][i]
-                    row = row[:1] + (float(rep["snr_db"]) if int(rep["status"]) < 2 else float("nan"),) + row[1:]
-                rows.append(row)
+                rows.append((text,) + ((db[i],) if snr else ()) + (tsec[i], fhz[i], sc[i], r[i]))
             if table is not None:
                 table.learn(t)
             out.append(rows)
@@ -415,3 +417,21 @@ def decode_slots(samples, sample_rate=12000, **kwargs):
     """One-call form of SlotDecoder: samples [B, N] (GPU tensor, float32/int16/...) -> list (per
     slot) of decode_ft8_message's 5-tuples."""
     return SlotDecoder(sample_rate=sample_rate, **kwargs).decode(samples)
+
+
+def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_candidates=20, min_score=10,
+               max_iterations=20, freq_min=None, freq_max=None, time_min=None, time_max=None, *, flags=0, snr=False,
+               ap=None, ap_max_hard_errors=None):
+    """One slot, x [N] on the GPU with its ft8 dtype code, through a SlotDecoder of its own:
+    -> (decode_ft8_message's 5-tuples, with snr the ft8_snr_rec records aligned with them else None,
+    the ft8_result records).  Nothing is launched when the masks leave nothing or max_candidates <= 0."""
+    recs, reps = np.zeros(0, _lib.RESULT_DTYPE), np.zeros(0, _lib.SNR_DTYPE) if snr else None
+    plan = make_plan(int(x.shape[0]), sample_rate, bins_per_tone, steps_per_symbol, freq_min, freq_max, time_min,
+                     time_max)
+    if not plan.empty and max_candidates > 0:
+        dec = SlotDecoder(sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score, max_iterations,
+                          freq_min, freq_max, time_min, time_max, device=x.device, flags=flags, ap=ap,
+                          ap_max_hard_errors=ap_max_hard_errors)
+        recs, _, reps = (v if v is None else v[0] for v in dec._fetch(x.unsqueeze(0), code, snr=snr))
+    wf_f64 = code in (_lib.FT8_F64, _lib.FT8_C128)
+    return records_to_results(recs, sample_rate, bins_per_tone, wf_f64), reps, recs

@@ -15,8 +15,6 @@ import wave
 
 import numpy as np
 
-from .ft8_decode import decode_ft8_message
-
 
 def _read_raw(wave_path: str, verbose: bool = False):
     with wave.open(wave_path, "rb") as wf:
@@ -52,6 +50,32 @@ def read_wave_file(wave_path: str, verbose: bool = False) -> tuple:
     return x, sample_rate
 
 
+def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_errors: int = None, device=None,
+                 verbose: bool = False, **decode_kw) -> tuple:
+    """One file, any PCM width, as one slot through _pipeline.decode_one -> (results, snr_db, patterns).
+    snr_db (with snr, else None): one SNR in 2500 Hz per result.  patterns (with ap, else None): per
+    result the a-priori pattern that rescued it, None for a plain decode."""
+    import torch
+    from . import _lib
+    from ._pipeline import decode_one
+    from .ap import ap_index
+    from .snr import snr_db_or_nan
+    data, dtype, sample_rate = _read_raw(wave_path, verbose)
+    _lib.require_gpu()
+    dev = torch.device("cuda", _lib.device_index(device))
+    if dtype == np.int16:   # raw PCM: the STFT kernel applies read_wave_file's float32 x / 32767
+        x, code = torch.from_numpy(np.array(data, copy=True)).to(dev), _lib.FT8_I16
+    else:
+        h = data.astype(np.float32)
+        h /= np.iinfo(dtype).max
+        x, code = torch.from_numpy(h).to(dev), _lib.FT8_F32
+    ap = None if ap is None else tuple(ap)
+    results, reports, recs = decode_one(x, code, sample_rate, snr=snr, ap=ap, ap_max_hard_errors=ap_max_hard_errors,
+                                        **decode_kw)
+    return (results, snr_db_or_nan(reports) if snr else None,
+            None if ap is None else [ap[ap_index(r) - 1] if ap_index(r) else None for r in recs])
+
+
 def decode_ft8_from_wave(wave_path: str, freq_min: float = None, freq_max: float = None, time_min: float = None,
                          time_max: float = None, bins_per_tone: int = 2, steps_per_symbol: int = 2,
                          max_candidates: int = 20, min_score: float = 10, max_iterations: int = 20,
@@ -64,57 +88,10 @@ def decode_ft8_from_wave(wave_path: str, freq_min: float = None, freq_max: float
         # ft8_demodulator_amd.frequency_correction.correct_frequency_drift (GPU).
         raise TypeError("argument of type 'FT8Waterfall' is not iterable "
                         "(from_wave.py:152-158 passes a waterfall as correct_frequency_drift's params)")
-    data, dtype, sample_rate = _read_raw(wave_path, verbose)
-    if dtype == np.int16:
-        import torch
-        from . import _lib
-        from ._pipeline import SlotDecoder, make_plan, records_to_results
-        _lib.require_gpu()
-        dev = torch.device("cuda", _lib.device_index(device))
-        x = torch.from_numpy(np.array(data, copy=True)).to(dev)
-        plan = make_plan(int(x.shape[0]), sample_rate, bins_per_tone, steps_per_symbol, freq_min, freq_max,
-                         time_min, time_max)
-        if plan.empty or max_candidates <= 0:
-            return []
-        dec = SlotDecoder(sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score, max_iterations,
-                          freq_min, freq_max, time_min, time_max, device=dev)
-        recs = dec.records(x.unsqueeze(0), code=_lib.FT8_I16)[0]
-        return records_to_results(recs, sample_rate, bins_per_tone, False)
-    x = data.astype(np.float32)
-    x /= np.iinfo(dtype).max
-    return decode_ft8_message(x, sample_rate, bins_per_tone=bins_per_tone, steps_per_symbol=steps_per_symbol,
-                              max_candidates=max_candidates, min_score=min_score, max_iterations=max_iterations,
-                              freq_min=freq_min, freq_max=freq_max, time_min=time_min, time_max=time_max,
-                              device=device)
-
-
-def _decode_with_reports(wave_path, freq_min, freq_max, time_min, time_max, bins_per_tone, steps_per_symbol,
-                         max_candidates, min_score, max_iterations, device, ap=None, ap_max_hard_errors=None):
-    """One file through SlotDecoder (any PCM width) with the signal report -> (results, snr_db, patterns):
-    patterns[i] is the a-priori pattern that rescued result i, None for a plain decode."""
-    import torch
-    from . import _lib
-    from .ap import ap_index
-    from ._pipeline import SlotDecoder, make_plan, records_to_results
-    data, dtype, sample_rate = _read_raw(wave_path)
-    _lib.require_gpu()
-    dev = torch.device("cuda", _lib.device_index(device))
-    if dtype == np.int16:
-        x, code = torch.from_numpy(np.array(data, copy=True)).to(dev), _lib.FT8_I16
-    else:
-        h = data.astype(np.float32)
-        h /= np.iinfo(dtype).max
-        x, code = torch.from_numpy(h).to(dev), _lib.FT8_F32
-    plan = make_plan(int(x.shape[0]), sample_rate, bins_per_tone, steps_per_symbol, freq_min, freq_max, time_min,
-                     time_max)
-    if plan.empty or max_candidates <= 0:
-        return [], [], []
-    dec = SlotDecoder(sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score, max_iterations,
-                      freq_min, freq_max, time_min, time_max, device=dev, ap=ap, ap_max_hard_errors=ap_max_hard_errors)
-    recs, _, reps = dec._records_and_texts(x.unsqueeze(0), code, snr=True)
-    snr_db = [float(r["snr_db"]) if int(r["status"]) < 2 else float("nan") for r in reps[0]]
-    patterns = [dec.ap_patterns[ap_index(r) - 1] if ap_index(r) else None for r in recs[0]]
-    return records_to_results(recs[0], sample_rate, bins_per_tone, False), snr_db, patterns
+    return _decode_file(wave_path, device=device, verbose=verbose, freq_min=freq_min, freq_max=freq_max,
+                        time_min=time_min, time_max=time_max, bins_per_tone=bins_per_tone,
+                        steps_per_symbol=steps_per_symbol, max_candidates=max_candidates, min_score=min_score,
+                        max_iterations=max_iterations)[0]
 
 
 def decode_ft8_from_wave_snr(wave_path: str, freq_min: float = None, freq_max: float = None, time_min: float = None,
@@ -124,8 +101,9 @@ def decode_ft8_from_wave_snr(wave_path: str, freq_min: float = None, freq_max: f
     """decode_ft8_from_wave with the signal report (build-defined): -> (results, snr_db), the same
     5-tuples and one SNR in 2500 Hz (dB, float) per result, measured on the device on the waterfall
     of the same decode (SlotDecoder.snr / ft8_snr_last)."""
-    return _decode_with_reports(wave_path, freq_min, freq_max, time_min, time_max, bins_per_tone, steps_per_symbol,
-                                max_candidates, min_score, max_iterations, device)[:2]
+    return _decode_file(wave_path, snr=True, device=device, freq_min=freq_min, freq_max=freq_max, time_min=time_min,
+                        time_max=time_max, bins_per_tone=bins_per_tone, steps_per_symbol=steps_per_symbol,
+                        max_candidates=max_candidates, min_score=min_score, max_iterations=max_iterations)[:2]
 
 
 def decode_ft8_from_wave_ap(wave_path: str, ap, ap_max_hard_errors: int = None, freq_min: float = None,
@@ -136,9 +114,11 @@ def decode_ft8_from_wave_ap(wave_path: str, ap, ap_max_hard_errors: int = None, 
     with the patterns `ap` (ap.ap_hypothesis, e.g. ["CQ ? ?"]) -> (results, patterns, snr_db): the same
     5-tuples in candidate order, per result the pattern that rescued it (None for a plain decode), and
     its SNR in 2500 Hz as decode_ft8_from_wave_snr gives it."""
-    results, snr_db, patterns = _decode_with_reports(
-        wave_path, freq_min, freq_max, time_min, time_max, bins_per_tone, steps_per_symbol, max_candidates, min_score,
-        max_iterations, device, ap=ap, ap_max_hard_errors=ap_max_hard_errors)
+    results, snr_db, patterns = _decode_file(
+        wave_path, snr=True, ap=ap, ap_max_hard_errors=ap_max_hard_errors, device=device, freq_min=freq_min,
+        freq_max=freq_max, time_min=time_min, time_max=time_max, bins_per_tone=bins_per_tone,
+        steps_per_symbol=steps_per_symbol, max_candidates=max_candidates, min_score=min_score,
+        max_iterations=max_iterations)
     return results, patterns, snr_db
 
 
@@ -171,24 +151,21 @@ def _print_results(results, text: bool = False, snr=None, ap=None):
         print("-" * 50)
 
 
-def _decode_many(args):
+def _decode_many(paths, correction, kw):
     """Several files (build-defined extension of the reference CLI): 16-bit PCM files of one sample
     rate and length are decoded as batches through the streaming path (stream.decode_wave_files);
     any other file -- and every file with --correction -- one at a time.  Results per file, in order."""
     from .stream import decode_wave_files
-    kw = dict(freq_min=args.freq_min, freq_max=args.freq_max, time_min=args.time_min, time_max=args.time_max,
-              bins_per_tone=args.bins_per_tone, steps_per_symbol=args.steps_per_symbol,
-              max_candidates=args.max_candidates, min_score=args.min_score, max_iterations=args.max_iterations)
-    out = [None] * len(args.wave_file)
+    out = [None] * len(paths)
     groups = {}
-    for i, path in enumerate(args.wave_file):
+    for i, path in enumerate(paths):
         raw, dt, fs = _read_raw(path)
-        if args.correction or dt != np.int16:
-            out[i] = decode_ft8_from_wave(path, correction=args.correction, **kw)
+        if correction or dt != np.int16:
+            out[i] = decode_ft8_from_wave(path, correction=correction, **kw)
         else:
             groups.setdefault((fs, raw.shape[0]), []).append(i)
     for idx in groups.values():
-        res = decode_wave_files([args.wave_file[i] for i in idx], **kw)
+        res = decode_wave_files([paths[i] for i in idx], **kw)
         for i, r in zip(idx, res):
             out[i] = r
     return out
@@ -216,55 +193,33 @@ def main(argv=None):
     parser.add_argument("--ap-max-hard-errors", type=int, default=None,
                         help="most hard decisions of an AP decode that may contradict the received bits (default 36)")
     args = parser.parse_args(argv)
-    for path in args.wave_file:
+    paths = args.wave_file
+    for path in paths:
         if not os.path.exists(path):
             print(f"Error: File {path} does not exist")
             sys.exit(1)
-    if args.ap:
-        # like --snr: one file at a time, each decoded once on the batched path
+    kw = dict(freq_min=args.freq_min, freq_max=args.freq_max, time_min=args.time_min, time_max=args.time_max,
+              bins_per_tone=args.bins_per_tone, steps_per_symbol=args.steps_per_symbol,
+              max_candidates=args.max_candidates, min_score=args.min_score, max_iterations=args.max_iterations)
+    many = len(paths) > 1
+    if args.ap or args.snr:
+        # the report comes from the decode's own waterfall, an AP decode's mark from its own record:
+        # one file at a time, each decoded once (lazily: a file is printed before the next is decoded)
         if args.correction:
-            decode_ft8_from_wave(args.wave_file[0], correction=True)  # raises as without --ap
-        per_file = []
-        for path in args.wave_file:
-            results, patterns, snr = decode_ft8_from_wave_ap(
-                path, args.ap, args.ap_max_hard_errors, freq_min=args.freq_min, freq_max=args.freq_max,
-                time_min=args.time_min, time_max=args.time_max, bins_per_tone=args.bins_per_tone,
-                steps_per_symbol=args.steps_per_symbol, max_candidates=args.max_candidates, min_score=args.min_score,
-                max_iterations=args.max_iterations)
-            if len(args.wave_file) > 1:
-                print(f"\n== {path}")
-            _print_results(results, args.text, snr if args.snr else None, patterns)
-            per_file.append(results)
-        return per_file if len(args.wave_file) > 1 else per_file[0]
-    if args.snr:
-        # the report comes from the decode's own waterfall: one file at a time, each decoded once
-        if args.correction:
-            decode_ft8_from_wave(args.wave_file[0], correction=True)  # raises as without --snr
-        per_file = []
-        for path in args.wave_file:
-            results, snr = decode_ft8_from_wave_snr(
-                path, freq_min=args.freq_min, freq_max=args.freq_max, time_min=args.time_min, time_max=args.time_max,
-                bins_per_tone=args.bins_per_tone, steps_per_symbol=args.steps_per_symbol,
-                max_candidates=args.max_candidates, min_score=args.min_score, max_iterations=args.max_iterations)
-            if len(args.wave_file) > 1:
-                print(f"\n== {path}")
-            _print_results(results, args.text, snr)
-            per_file.append(results)
-        return per_file if len(args.wave_file) > 1 else per_file[0]
-    if len(args.wave_file) > 1:
-        per_file = _decode_many(args)
-        for path, results in zip(args.wave_file, per_file):
+            decode_ft8_from_wave(paths[0], correction=True)  # raises as without the flags
+        decoded = (_decode_file(path, snr=args.snr, ap=args.ap, ap_max_hard_errors=args.ap_max_hard_errors, **kw)
+                   for path in paths)
+    elif many:
+        decoded = ((results, None, None) for results in _decode_many(paths, args.correction, kw))
+    else:
+        decoded = [(decode_ft8_from_wave(paths[0], correction=args.correction, **kw), None, None)]
+    per_file = []
+    for path, (results, snr, patterns) in zip(paths, decoded):
+        if many:
             print(f"\n== {path}")
-            _print_results(results, args.text)
-        return per_file
-    args.wave_file = args.wave_file[0]
-    results = decode_ft8_from_wave(args.wave_file, freq_min=args.freq_min, freq_max=args.freq_max,
-                                   time_min=args.time_min, time_max=args.time_max,
-                                   bins_per_tone=args.bins_per_tone, steps_per_symbol=args.steps_per_symbol,
-                                   max_candidates=args.max_candidates, min_score=args.min_score,
-                                   max_iterations=args.max_iterations, correction=args.correction)
-    _print_results(results, args.text)
-    return results
+        _print_results(results, args.text, snr, patterns)
+        per_file.append(results)
+    return per_file if many else per_file[0]
 
 
 if __name__ == "__main__":

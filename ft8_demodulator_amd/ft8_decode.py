@@ -22,7 +22,7 @@ from typing import List, Tuple
 import numpy as np
 
 from . import _device, _lib
-from ._pipeline import SlotDecoder, device_samples, make_plan, records_to_results
+from ._pipeline import decode_one, device_samples, make_plan
 from .crc import compute_crc, extract_crc
 from .ftx_types import FT8Candidate, FT8DecodeStatus, FT8Message, FT8Protocol, FT8Waterfall  # noqa: F401
 from .spectrogram_analyse import FT8_SYMBOL_DURATION_S, FT8_SYMBOL_FREQ_INTERVAL_HZ, calculate_spectrogram  # noqa: F401
@@ -150,20 +150,17 @@ def decode_ft8_message(wave_data, sample_rate: int, bins_per_tone: int = 2, step
     Build-defined options (outside reference parity, defaults reproduce the reference):
     selection="topk" keeps the max_candidates highest scores; subtract=True subtracts the decoded
     signals and decodes the residual once more, appending new messages (float32 input only)."""
-    x, code, wf_f64 = device_samples(wave_data, device)
+    x, code, _ = device_samples(wave_data, device)
     if x.dim() != 1:
         raise ValueError("wave_data must be one-dimensional")
-    plan = make_plan(int(x.shape[0]), sample_rate, bins_per_tone, steps_per_symbol, freq_min, freq_max,
-                     time_min, time_max)
-    results = []
-    if not plan.empty and max_candidates > 0:
-        dec = SlotDecoder(sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score, max_iterations,
-                          freq_min, freq_max, time_min, time_max, device=x.device,
-                          flags=selection_flags(selection, subtract))
-        recs = dec.records(x.unsqueeze(0), code)[0]
-        results = records_to_results(recs, sample_rate, bins_per_tone, wf_f64)
-    if plot and not plan.empty:
-        _plot(wave_data, sample_rate, bins_per_tone, steps_per_symbol, plan, max_candidates, min_score)
+    results = decode_one(x, code, sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score,
+                         max_iterations, freq_min, freq_max, time_min, time_max,
+                         flags=selection_flags(selection, subtract))[0]
+    if plot:
+        plan = make_plan(int(x.shape[0]), sample_rate, bins_per_tone, steps_per_symbol, freq_min, freq_max,
+                         time_min, time_max)
+        if not plan.empty:
+            _plot(wave_data, sample_rate, bins_per_tone, steps_per_symbol, plan, max_candidates, min_score)
     if verbose:
         print(f"Decoded messages: {results}")
     return results

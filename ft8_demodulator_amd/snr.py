@@ -115,6 +115,12 @@ def snr_reference(wf, records, counts=None, sample_rate=12000, bins_per_tone=2, 
     return (out, info) if details else out
 
 
+def snr_db_or_nan(reports) -> list:
+    """ft8_snr_rec records -> one Python float each: snr_db, NaN where the report's status is 2 or 3
+    (nothing was measured)."""
+    return [float(r["snr_db"]) if int(r["status"]) < 2 else float("nan") for r in reports]
+
+
 # ---- the stage calls, for waterfalls on the GPU ---------------------------------------------------------
 def _wf3(wf):
     torch = _lib.require_gpu()

@@ -135,7 +135,7 @@ class StreamDecoder:
         cap = self.dec.cap
         recs = self.hout[i][: nb * cap * _lib.RESULT_DTYPE.itemsize].numpy().view(_lib.RESULT_DTYPE).reshape(nb, cap)
         raw = self.hcnt[i][:nb].numpy()
-        warn_truncated(raw, cap, stacklevel=3)
+        warn_truncated(raw, cap)
         cnt = np.minimum(raw, cap)
         out = [[] for _ in range(nb)]
         # every decode of the batch converted in one call (slot-major, candidate order), then dealt

@@ -425,6 +425,21 @@ def test_reports_are_messages_with_snr(gpu, decoded, text_slots):
     assert dec.reports(short) == [[], []] and [len(v) for v in dec.snr(short)] == [0, 0]
 
 
+@pytest.mark.parametrize("method", ["records", "decode", "texts", "snr", "messages", "reports"])
+def test_every_surface_decodes_once(gpu, decoded, text_slots, method):
+    """Each public call is one ft8_decode_batch, whatever side outputs it fetches."""
+    _, _, decoder = decoded
+    dec = decoder()                      # on a context of its own
+    dec.ctx.set_timing(True, stages=["decode_batch"])
+    try:
+        dec.timing(reset=True)
+        got = getattr(dec, method)(text_slots)
+        assert dec.timing()["decode_batch"][1] == 1
+        assert len(got) == 2 and all(len(v) >= 1 for v in got)
+    finally:
+        dec.ctx.set_timing(False)
+
+
 def test_from_wave_snr_flag(gpu, capsys):
     from ft8_demodulator_amd.from_wave import _print_results, decode_ft8_from_wave, main
     wav = os.path.join(DATA, "synth_cfg1.wav")

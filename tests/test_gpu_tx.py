@@ -400,3 +400,11 @@ def test_subtract_capacity_holds_both_passes(gpu):
         r2 = small.records(x)
     assert any("max_results_per_slot=2" in str(m.message) for m in w)
     assert all(len(r) <= 2 for r in r2)
+    # the warning names this file, the caller of the package, once per call, through however many
+    # of the package's own wrappers the call goes
+    for method in (small.records, small.texts, small.messages):
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            method(x)
+        assert [os.path.abspath(m.filename) for m in w if "max_results_per_slot=2" in str(m.message)] == \
+               [os.path.abspath(__file__)], method.__name__

@@ -63,6 +63,157 @@ def test_result_assembly():
     assert _lib.RESULT_DTYPE.itemsize == 40
 
 
+def test_record_columns_are_the_results_columns():
+    from ft8_demodulator_amd import _lib
+    from ft8_demodulator_amd._pipeline import record_columns, records_to_results
+    r = np.zeros(3, dtype=_lib.RESULT_DTYPE)
+    r["score"] = [np.float32(29.03573), 0.1, -3.25]      # 0.1 is not a float32: the cast shows
+    r["abs_time"], r["abs_freq"] = [2, -7, 1801], [177, 0, 3]
+    r["ok"] = 1
+    for wf_f64 in (False, True):
+        for fs in (20000, 12000.5):
+            tsec, fhz, sc = record_columns(r, fs, 2, wf_f64)
+            res = records_to_results(r, fs, 2, wf_f64)
+            assert type(tsec) is list and type(fhz) is list and len(tsec) == len(fhz) == len(sc) == 3
+            assert sc.dtype == (np.float64 if wf_f64 else np.float32)
+            for i, (_, _, t, f, s) in enumerate(res):
+                assert (tsec[i], fhz[i], sc[i]) == (t, f, s)
+                assert (type(tsec[i]), type(fhz[i]), type(sc[i])) == (type(t), type(f), type(s)) == \
+                       (float, float, np.float64 if wf_f64 else np.float32)
+    assert tsec == [2 / 12000.5, -7 / 12000.5, 1801 / 12000.5] and fhz == [553.125, 0.0, 9.375]
+    empty = record_columns(r[:0], 12000, 2, False)
+    assert empty[0] == [] and empty[1] == [] and empty[2].shape == (0,) and empty[2].dtype == np.float32
+
+
+def test_split_slots():
+    from ft8_demodulator_amd import _lib
+    from ft8_demodulator_amd._pipeline import split_slots
+    cap, counts = 3, np.array([0, 2, 5], dtype=np.int32)
+    rng = np.random.default_rng(5)
+    for dtype in (_lib.RESULT_DTYPE, _lib.TEXT_DTYPE, _lib.SNR_DTYPE):
+        raw = rng.integers(0, 256, size=3 * cap * dtype.itemsize + 7, dtype=np.uint8)   # a grown buffer: longer
+        src = raw[: 3 * cap * dtype.itemsize].view(dtype).reshape(3, cap)
+        assert len({row.tobytes() for row in src.reshape(-1)}) == 3 * cap            # distinct rows
+        keep = raw.copy()
+        got = split_slots(raw, dtype, counts, cap)
+        assert [len(g) for g in got] == [0, 2, 3] and all(g.dtype == dtype for g in got)
+        for s, g in enumerate(got):
+            assert g.tobytes() == src[s, : len(g)].tobytes()
+            assert g.flags.owndata and not np.shares_memory(g, raw)
+            g.view(np.uint8)[...] ^= 0xFF                                              # writing to a result ...
+        assert np.array_equal(raw, keep)                                               # ... leaves the source alone
+        assert split_slots(raw[:0], dtype, np.zeros(0, dtype=np.int32), cap) == []
+        assert split_slots(raw, dtype, [], cap) == []
+
+
+TRUNCATED_TEXT = ("1 slot(s) decoded more messages than max_results_per_slot=2 (e.g. slot 1: 4); "
+                  "the records beyond it were dropped")
+
+
+def test_warn_truncated_names_the_caller():
+    import warnings
+    from ft8_demodulator_amd._pipeline import warn_truncated
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        warn_truncated(np.array([1, 4], dtype=np.int32), 2)
+    assert len(w) == 1 and w[0].category is RuntimeWarning and str(w[0].message) == TRUNCATED_TEXT
+    assert os.path.abspath(w[0].filename) == os.path.abspath(__file__)
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        warn_truncated(np.array([1, 2], dtype=np.int32), 2)
+    assert w == []
+
+
+# ---- from_wave.main: which decode path each flag combination takes, and what it prints -------------------
+def _canned_results():
+    from ft8_demodulator_amd.ftx_types import FT8DecodeStatus, FT8Message
+    return [(FT8Message(payload=bytearray.fromhex(h), hash=100 + k),
+             FT8DecodeStatus(ldpc_errors=k, crc_extracted=100 + k, crc_calculated=100 + k),
+             0.5 + k, 1000.0 + 12.5 * k, np.float32(12.5 + k))
+            for k, h in enumerate(["000000204def1a8a1988", "09bde3501a95851fa508"])]
+
+
+CANNED_SNR = [-12.34, 3.0]
+CANNED_BLOCKS = [   # (line, the flag that prints it) per result; the second result is the a-priori decode
+    [("Time: 0.50 seconds", None), ("Frequency: 1000.0 Hz", None), ("Score: 12.5", None), ("SNR: -12.3 dB", "snr"),
+     ("Payload: 000000204def1a8a1988", None), ("Message: CQ K1ABC FN42", "text"), ("CRC check: 100", None),
+     ("LDPC errors: 0", None)],
+    [("Time: 1.50 seconds", None), ("Frequency: 1012.5 Hz", None), ("Score: 13.5", None), ("SNR: 3.0 dB", "snr"),
+     ("Payload: 09bde3501a95851fa508", None), ("Message: K1ABC <...> 73", "text"), ("AP: CQ ? ?", "ap"),
+     ("CRC check: 101", None), ("LDPC errors: 1", None)]]
+
+
+def _expected_print(paths, flags):
+    out = []
+    for path in paths:
+        if len(paths) > 1:
+            out += ["", f"== {path}"]
+        out += ["", "Decoded FT8 messages:", "-" * 50]
+        for block in CANNED_BLOCKS:
+            out += [line for line, flag in block if flag is None or flag in flags] + ["-" * 50]
+    return "\n".join(out) + "\n"
+
+
+@pytest.mark.parametrize("n_files", [1, 2])
+@pytest.mark.parametrize("flags", [(), ("snr",), ("ap",), ("ap", "snr", "text")], ids=lambda f: "+".join(f) or "plain")
+def test_from_wave_main_dispatch(monkeypatch, capsys, tmp_path, n_files, flags):
+    from ft8_demodulator_amd import from_wave
+    paths = [str(tmp_path / f"slot{i}.wav") for i in range(n_files)]
+    for p in paths:
+        open(p, "wb").close()
+    calls = []
+
+    def decode_file(path, **kw):
+        calls.append(("_decode_file", path, kw))
+        return (_canned_results(), list(CANNED_SNR) if kw["snr"] else None,
+                [None, kw["ap"][0]] if kw["ap"] is not None else None)
+
+    def decode_plain(path, **kw):
+        calls.append(("decode_ft8_from_wave", path, kw))
+        return _canned_results()
+
+    def decode_many(paths_, correction, kw):
+        calls.append(("_decode_many", list(paths_), correction, kw))
+        return [_canned_results() for _ in paths_]
+
+    monkeypatch.setattr(from_wave, "_decode_file", decode_file)
+    monkeypatch.setattr(from_wave, "decode_ft8_from_wave", decode_plain)
+    monkeypatch.setattr(from_wave, "_decode_many", decode_many)
+    argv = paths + ["--max-candidates", "30", "--freq-min", "100"]
+    for f in flags:
+        argv += {"snr": ["--snr"], "ap": ["--ap", "CQ ? ?"], "text": ["--text"]}[f]
+    kw = dict(freq_min=100.0, freq_max=None, time_min=None, time_max=None, bins_per_tone=2, steps_per_symbol=2,
+              max_candidates=30, min_score=10, max_iterations=20)
+    got = from_wave.main(argv)
+    if "ap" in flags or "snr" in flags:
+        ap = ["CQ ? ?"] if "ap" in flags else None
+        assert calls == [("_decode_file", p, dict(kw, snr="snr" in flags, ap=ap, ap_max_hard_errors=None))
+                         for p in paths]
+    elif n_files > 1:
+        assert calls == [("_decode_many", paths, False, kw)]
+    else:
+        assert calls == [("decode_ft8_from_wave", paths[0], dict(kw, correction=False))]
+    assert capsys.readouterr().out == _expected_print(paths, flags)
+    key = [(bytes(m.payload), t, f, float(sc)) for m, _, t, f, sc in _canned_results()]
+    per_file = got if n_files > 1 else [got]
+    assert type(got) is list and len(per_file) == n_files
+    assert all([(bytes(m.payload), t, f, float(sc)) for m, _, t, f, sc in res] == key for res in per_file)
+
+
+def test_from_wave_main_correction_with_snr_raises(monkeypatch, tmp_path):
+    from ft8_demodulator_amd import from_wave
+
+    def unexpected(*a, **kw):
+        raise AssertionError("nothing is decoded once --correction has raised")
+
+    monkeypatch.setattr(from_wave, "_decode_file", unexpected)
+    monkeypatch.setattr(from_wave, "_decode_many", unexpected)
+    path = str(tmp_path / "slot.wav")
+    open(path, "wb").close()        # never read: the error comes first
+    with pytest.raises(TypeError, match="FT8Waterfall"):
+        from_wave.main([path, "--correction", "True", "--snr"])
+
+
 def test_read_wave_file_semantics():
     import wave
     from ft8_demodulator_amd import read_wave_file
