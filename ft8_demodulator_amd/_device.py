@@ -162,6 +162,44 @@ def ap_decode(llrs, records, max_iterations):
     return res.cpu().numpy()[: n * _lib.RESULT_DTYPE.itemsize].view(_lib.RESULT_DTYPE).copy(), hard.cpu().numpy()[:n]
 
 
+def coherent_llr(samples, cand, slot_of, sample_rate=12000, bins_per_tone=2, steps_per_symbol=2, t_lo=0, f_lo=0,
+                 code=None):
+    """ft8_coherent_llr: samples [n_slots, n_samples] (float32, or int16 PCM; NumPy or a GPU tensor with
+    its ft8 dtype `code`), candidates cand [n, 2] = (abs_time, abs_freq) of the slots slot_of [n]
+    -> (LLRs float64 [n, 174], fits coherent.FIT_DTYPE [n])."""
+    from ._pipeline import device_samples
+    from .coherent import FIT_DTYPE
+    torch = _lib.require_gpu()
+    ctx = _lib.context()
+    x = samples
+    if code is None and isinstance(samples, np.ndarray) and samples.dtype == np.int16:   # raw PCM, as a tensor is
+        x, code = torch.from_numpy(np.ascontiguousarray(samples)).cuda(), _lib.FT8_I16
+    elif code is None:
+        x, code, _ = device_samples(samples, int16_is_pcm=True)
+    if x.dim() == 1:
+        x = x.unsqueeze(0)
+    x = x.contiguous()
+    n_slots, ns = int(x.shape[0]), int(x.shape[1])
+    c = np.ascontiguousarray(np.asarray(cand, dtype=np.int32).reshape(-1, 2))
+    so = np.ascontiguousarray(np.asarray(slot_of, dtype=np.int32).reshape(-1))
+    n = len(c)
+    if len(so) != n:
+        raise ValueError(f"{n} candidates but {len(so)} slot indices")
+    p = _lib.Ft8Params()
+    fs = _lib.sample_rate_hz(sample_rate)
+    p.sample_rate, p.sample_rate_hz = int(fs), fs
+    p.bins_per_tone, p.steps_per_symbol = int(bins_per_tone), int(steps_per_symbol)
+    p.t_lo, p.f_lo = int(t_lo), int(f_lo)
+    d_c = torch.from_numpy(np.concatenate([c.reshape(-1), np.zeros(2, np.int32)])).to(x.device)
+    d_so = torch.from_numpy(np.concatenate([so, np.zeros(1, np.int32)])).to(x.device)
+    d_llr = torch.zeros(max(n, 1), 174, dtype=torch.float64, device=x.device)
+    d_fit = torch.zeros(max(n, 1) * FIT_DTYPE.itemsize, dtype=torch.uint8, device=x.device)
+    ctx.check(_lib.lib().ft8_coherent_llr(ctx.handle, _lib.ptr(x), int(code), ns, n_slots, ns, ctypes.byref(p),
+                                          _lib.ptr(d_c), _lib.ptr(d_so), n, _lib.ptr(d_llr), _lib.ptr(d_fit),
+                                          _lib.stream_handle()), "ft8_coherent_llr")
+    return d_llr.cpu().numpy()[:n], d_fit.cpu().numpy()[: n * FIT_DTYPE.itemsize].view(FIT_DTYPE).copy()
+
+
 def crc14(msgs, nbits):
     torch = _lib.require_gpu()
     ctx = _lib.context()

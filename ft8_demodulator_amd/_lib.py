@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("FT8HIP_LIB", os.path.join(_HERE, "lib", "libft8hip.so
 
 FT8_F32, FT8_F64, FT8_C64, FT8_C128, FT8_I16 = 0, 1, 2, 3, 4
 FT8_OK, FT8_E_ARG, FT8_E_HIP, FT8_E_UNSUPPORTED, FT8_E_NOMEM, FT8_E_RANGE = 0, -1, -2, -3, -4, -5
-FT8_FLAG_TOPK, FT8_FLAG_SUBTRACT, FT8_FLAG_AP = 1, 2, 4
+FT8_FLAG_TOPK, FT8_FLAG_SUBTRACT, FT8_FLAG_AP, FT8_FLAG_COHERENT = 1, 2, 4, 8
 FT8_AP_MAX_HYP = 8
 FT8_TX_PROTOCOL, FT8_TX_REFERENCE = 0, 1
 FT8_STFT_STOCKHAM, FT8_STFT_PACKED3840, FT8_STFT_CHIRPZ, FT8_STFT_DFT = 0, 1, 2, 3
@@ -170,6 +170,8 @@ def lib():
             "ft8_snr_last": ([vp, vp, vp, i32, i32, vp, vp], ctypes.c_int),
             "ft8_set_ap": ([vp, vp, i32, i32], ctypes.c_int),
             "ft8_ap_decode": ([vp, vp, vp, i32, i32, vp, vp], ctypes.c_int),
+            "ft8_set_coherent": ([vp, i32], ctypes.c_int),
+            "ft8_coherent_llr": ([vp, vp, ctypes.c_int, i64, i32, i64, P, vp, vp, i32, vp, vp, vp], ctypes.c_int),
         }
         stale_ok = os.environ.get("FT8HIP_ALLOW_STALE") == "1"
         for name, (args, res) in sig.items():
@@ -191,7 +193,7 @@ def lib():
 
 # csrc files hashed into FT8_BUILD_ID, in the Makefile's ID_FILES order
 _ID_FILES = ("capi.hip", "stft.hip", "stft3840.hip", "sync.hip", "bp.hip", "tx.hip", "subtract.hip", "drift.hip",
-             "msg.hip", "snr.hip", "ap.hip", "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "heap_replay.h", "msg77.h",
+             "msg.hip", "snr.hip", "ap.hip", "coherent.hip", "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "heap_replay.h", "msg77.h",
              "div_shared.h",
              "../../include/ft8hip.h",
              "Makefile")
@@ -221,7 +223,7 @@ EXPORTED_SYMBOLS = (
     "ft8_build_id", "ft8_build_flags", "ft8_replay_stage", "ft8_set_timing_stages", "ft8_sync_score",
     "ft8_pack_bytes", "ft8_pack_decodes", "ft8_subtract_fits", "ft8_stft_method", "ft8_stft_screen_stats",
     "ft8_unpack77", "ft8_unpack77_host", "ft8_hash_call", "ft8_noise_floor", "ft8_snr", "ft8_snr_last",
-    "ft8_set_ap", "ft8_ap_decode")
+    "ft8_set_ap", "ft8_ap_decode", "ft8_set_coherent", "ft8_coherent_llr")
 
 
 def limits():
@@ -310,6 +312,11 @@ class Context:
             h["value"][i] = np.frombuffer(bytes(v), dtype=np.uint8)
         self.check(lib().ft8_set_ap(self.handle, h.ctypes.data_as(ctypes.c_void_p), len(hyps), int(max_hard_errors)),
                    "ft8_set_ap")
+
+    def set_coherent(self, max_per_slot: int = 0):
+        """ft8_set_coherent: how many failed candidates per slot an FT8_FLAG_COHERENT batch demodulates
+        again from the samples (0: every one)."""
+        self.check(lib().ft8_set_coherent(self.handle, int(max_per_slot)), "ft8_set_coherent")
 
     def replay(self, stage: str, reps: int = 1, stream=None):
         """ft8_replay_stage: re-launch one kernel of the last ft8_decode_batch `reps` times."""

@@ -227,12 +227,23 @@ class SlotDecoder:
     def __init__(self, sample_rate=12000, bins_per_tone=2, steps_per_symbol=2, max_candidates=20,
                  min_score=10, max_iterations=20, freq_min=None, freq_max=None, time_min=None,
                  time_max=None, device=None, flags=0, max_results_per_slot=None, context=None, ap=None,
-                 ap_max_hard_errors=None):
+                 ap_max_hard_errors=None, coherent=None):
         """ap: a-priori patterns (ap.ap_hypothesis, e.g. ["CQ ? ?", "K1ABC ? ?"], tried in order on every
         candidate BP fails on; at most 8) -- sets FT8_FLAG_AP; None: plain decoding.  ap_max_hard_errors:
         the most hard decisions of an accepted AP decode that may contradict the received LLRs' signs
-        (default ap.DEFAULT_MAX_HARD_ERRORS = 36; 174: no limit)."""
+        (default ap.DEFAULT_MAX_HARD_ERRORS = 36; 174: no limit).
+        coherent: True or a count -- sets FT8_FLAG_COHERENT: per slot that many of the best-scoring
+        candidates BP fails on (True: 32, 0: every one) are demodulated again coherently from the samples
+        (coherent.py) and decoded from those LLRs; None / False: off."""
         from . import ap as _ap
+        from . import coherent as _coh
+        if coherent is None or coherent is False:
+            self.coherent = None
+        else:
+            self.coherent = _coh.DEFAULT_MAX_PER_SLOT if coherent is True else int(coherent)
+            if self.coherent < 0:
+                raise ValueError("coherent takes True or a count >= 0")
+            flags |= _lib.FT8_FLAG_COHERENT
         self.ap_patterns = None if ap is None else tuple(ap)
         self.ap_hyps = None if ap is None else [_ap.ap_hypothesis(p) for p in self.ap_patterns]
         self.ap_max_hard_errors = int(_ap.DEFAULT_MAX_HARD_ERRORS if ap_max_hard_errors is None else ap_max_hard_errors)
@@ -302,6 +313,8 @@ class SlotDecoder:
         p = make_params(plan, self.max_candidates, self.min_score, self.max_iterations, self.flags)
         if self.ap_hyps is not None:  # a host-side setting; the context may serve other decoders too
             self.ctx.set_ap(self.ap_hyps, self.ap_max_hard_errors)
+        if self.coherent is not None:
+            self.ctx.set_coherent(self.coherent)
         rc = _lib.lib().ft8_decode_batch(self.ctx.handle, _lib.ptr(x), int(code), n, n_slots, n,
                                          ctypes.byref(p), _lib.ptr(out), _lib.ptr(counts), self.cap,
                                          _lib.stream_handle(torch.device("cuda", self.device)))
@@ -421,7 +434,7 @@ def decode_slots(samples, sample_rate=12000, **kwargs):
 
 def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_candidates=20, min_score=10,
                max_iterations=20, freq_min=None, freq_max=None, time_min=None, time_max=None, *, flags=0, snr=False,
-               ap=None, ap_max_hard_errors=None):
+               ap=None, ap_max_hard_errors=None, coherent=None):
     """One slot, x [N] on the GPU with its ft8 dtype code, through a SlotDecoder of its own:
     -> (decode_ft8_message's 5-tuples, with snr the ft8_snr_rec records aligned with them else None,
     the ft8_result records).  Nothing is launched when the masks leave nothing or max_candidates <= 0."""
@@ -431,7 +444,7 @@ def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_ca
     if not plan.empty and max_candidates > 0:
         dec = SlotDecoder(sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score, max_iterations,
                           freq_min, freq_max, time_min, time_max, device=x.device, flags=flags, ap=ap,
-                          ap_max_hard_errors=ap_max_hard_errors)
+                          ap_max_hard_errors=ap_max_hard_errors, coherent=coherent)
         recs, _, reps = (v if v is None else v[0] for v in dec._fetch(x.unsqueeze(0), code, snr=snr))
     wf_f64 = code in (_lib.FT8_F64, _lib.FT8_C128)
     return records_to_results(recs, sample_rate, bins_per_tone, wf_f64), reps, recs

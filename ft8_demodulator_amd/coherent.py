@@ -1,0 +1,163 @@
+"""Coherent re-demodulation of a candidate from the samples: the contract of include/ft8hip.h
+("coherent re-demodulation", ft8_coherent_llr / FT8_FLAG_COHERENT) restated in NumPy, in float64.
+
+A candidate that belief propagation fails on is demodulated again from the slot's samples instead of
+the Hann STFT's dB bins: mixed down and box-car decimated to Q samples per symbol, fine-synchronised
+on the 21 Costas symbols (start offsets of D samples, tone-0 offsets of a quarter bin), and its LLRs
+formed from matched rectangular symbol windows at the refined point.  The device runs it
+(csrc/coherent.hip); this module restates it for tests and tools.  Nothing here runs on the decode
+path.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+TONE_HZ = 6.25
+COSTAS = (3, 1, 4, 0, 6, 5, 2)
+GRAY = (0, 1, 3, 2, 5, 6, 4, 7)   # FT8_Gray_map: s2[j] = s[GRAY[j]] (ft8_extract_symbol)
+SYNC_SYMBOLS = tuple(b + i for b in (0, 36, 72) for i in range(7))
+SYNC_TONES = COSTAS * 3
+DATA_SYMBOLS = tuple(range(7, 36)) + tuple(range(43, 72))
+N_DF = 5                           # tone-0 offsets: (j - 2) bin / 4, j = 0 .. 4
+DEFAULT_MAX_PER_SLOT = 32          # SlotDecoder(coherent=True)
+
+# ft8_coh_fit (16 bytes)
+FIT_DTYPE = np.dtype({
+    "names": ["dt_s", "df_hz", "metric", "n_sync", "status", "dt_index", "df_index"],
+    "formats": ["<f4", "<f4", "<f4", "u1", "u1", "i1", "u1"],
+    "offsets": [0, 4, 8, 12, 13, 14, 15],
+    "itemsize": 16,
+})
+STATUS_VALID, STATUS_NOTHING, STATUS_NOT_ATTEMPTED = 0, 2, 3
+
+
+def sub_q(nsps: int) -> int:
+    """Decimated samples per symbol: the largest divisor of nsps in [8, 32], 0 when there is none."""
+    for q in range(32, 7, -1):
+        if nsps % q == 0:
+            return q
+    return 0
+
+
+def geometry(nperseg: int, steps_per_symbol: int):
+    """-> (hop, Q, D, Mt, Mg); ValueError where the pass is unsupported (no Q, or hop does not divide nsps)."""
+    nsps, sps = int(nperseg), int(steps_per_symbol)
+    Q = sub_q(nsps)
+    if Q == 0 or sps <= 0 or nsps % sps != 0:
+        raise ValueError("coherent re-demodulation needs nsps with a divisor in [8, 32] and hop | nsps")
+    hop, D = nsps // sps, nsps // Q
+    Mt = -((-hop) // (2 * D))      # ceil((hop / 2) / D)
+    return hop, Q, D, Mt, Mt + 1
+
+
+def coherent_index(record) -> int:
+    """1 when the coherent pass produced the record's decode (pass_index bit 1), else 0."""
+    return (int(record["pass_index"]) >> 1) & 1
+
+
+def _as_float64(x: np.ndarray) -> np.ndarray:
+    x = np.asarray(x)
+    if x.dtype == np.int16:
+        return (x.astype(np.float32) / np.float32(32767.0)).astype(np.float64)   # as the STFT scales PCM
+    if x.dtype != np.float32:
+        raise NotImplementedError("coherent re-demodulation takes float32 or int16 samples")
+    return x.astype(np.float64)
+
+
+def _llr_of_spectra(s: np.ndarray) -> np.ndarray:
+    """s [58, 8] dB by tone -> [58, 3] max-of-4 differences after the Gray map (ft8_extract_symbol)."""
+    s2 = s[:, GRAY]
+    return np.stack([
+        s2[:, [4, 5, 6, 7]].max(1) - s2[:, [0, 1, 2, 3]].max(1),
+        s2[:, [2, 3, 6, 7]].max(1) - s2[:, [0, 1, 4, 5]].max(1),
+        s2[:, [1, 3, 5, 7]].max(1) - s2[:, [0, 2, 4, 6]].max(1)], axis=1)
+
+
+def coherent_restate(samples, cand, slot_of, fs, nperseg, nfft, steps_per_symbol, t_lo=0, f_lo=0, details=False):
+    """samples [n_slots, n_samples] (float32, or int16 PCM), cand [n, 2] = (abs_time, abs_freq), slot_of [n]
+    -> (llr float64 [n, 174], fits FIT_DTYPE [n]); with details also the list of every candidate's
+    metric grid [2 Mt + 1, 5] (None where no sync symbol was present)."""
+    x_all = np.asarray(samples)
+    if x_all.ndim == 1:
+        x_all = x_all[None, :]
+    n_slots, n_samples = x_all.shape
+    cand = np.asarray(cand, dtype=np.int64).reshape(-1, 2)
+    slot_of = np.asarray(slot_of, dtype=np.int64).reshape(-1)
+    n = len(cand)
+    hop, Q, D, Mt, Mg = geometry(nperseg, steps_per_symbol)
+    fs = float(fs)
+    binw = fs / float(nfft)
+    Mz = 79 * Q + 2 * Mg
+    dts = np.arange(-Mt, Mt + 1)
+    q = np.arange(Q)
+    # window index of (dt, symbol, q) into z, and its first input sample relative to nb
+    widx = Mg + dts[:, None, None] + np.arange(79)[None, :, None] * Q + q[None, None, :]
+    sync_k, data_k = np.array(SYNC_SYMBOLS), np.array(DATA_SYMBOLS)
+    df_grid = (np.arange(N_DF) - 2) * binw / 4.0
+    sync_nu = np.array(SYNC_TONES, dtype=np.float64)[None, :] - 3.5 + df_grid[:, None] / TONE_HZ    # [5, 21]
+    R = np.exp(-2j * np.pi * sync_nu[:, :, None] * q[None, None, :] / Q)                             # [5, 21, Q]
+
+    llr = np.zeros((n, 174), dtype=np.float64)
+    fits = np.zeros(n, dtype=FIT_DTYPE)
+    grids = []
+    cache = {}
+    for i in range(n):
+        grids.append(None)
+        slot = int(slot_of[i])
+        if not 0 <= slot < n_slots:
+            fits["status"][i] = STATUS_NOT_ATTEMPTED
+            continue
+        if slot not in cache:
+            cache[slot] = _as_float64(x_all[slot])
+        x = cache[slot]
+        s0 = (int(t_lo) + int(cand[i, 0])) * hop
+        fmix = (int(f_lo) + int(cand[i, 1])) * binw + 3.5 * TONE_HZ
+        nb = s0 - Mg * D
+        # 1. baseband
+        nidx = nb + np.arange(Mz * D, dtype=np.int64)
+        inside = (nidx >= 0) & (nidx < n_samples)
+        xw = np.where(inside, x[np.clip(nidx, 0, n_samples - 1)], 0.0)
+        cyc = fmix * nidx.astype(np.float64) / fs
+        z = (xw * np.exp(-2j * np.pi * (cyc - np.floor(cyc)))).reshape(Mz, D).sum(axis=1)
+        # 2. presence of (dt, symbol)
+        first = nb + (Mg + dts[:, None] + np.arange(79)[None, :] * Q) * D
+        present = (first >= 0) & (first + Q * D <= n_samples)                                        # [nT, 79]
+        if not present[:, sync_k].any():
+            fits["status"][i] = STATUS_NOTHING
+            continue
+        # 3. sync on the Costas symbols
+        W = z[widx]                                                                                  # [nT, 79, Q]
+        corr = np.einsum("dsq,jsq->djs", W[:, sync_k], R)
+        metric = (np.abs(corr) ** 2 * present[:, None, sync_k]).sum(axis=2)                          # [nT, 5]
+        grids[-1] = metric
+        best = int(np.argmax(metric.reshape(-1)))                                                    # the first largest
+        di, j = divmod(best, N_DF)
+        delta = 0.0
+        if 0 < j < N_DF - 1:
+            m_, m0, mp = metric[di, j - 1], metric[di, j], metric[di, j + 1]
+            den = m_ - 2.0 * m0 + mp
+            if den < 0.0:
+                delta = 0.5 * (m_ - mp) / den
+        df = (j - 2 + delta) * binw / 4.0
+        f = fits[i]
+        f["dt_s"], f["df_hz"], f["metric"] = dts[di] * D / fs, df, metric[di, j]
+        f["n_sync"], f["dt_index"], f["df_index"] = int(present[di, sync_k].sum()), dts[di], j
+        # 4. symbol spectra and LLRs
+        E = np.exp(-2j * np.pi * (np.arange(8)[:, None] - 3.5 + df / TONE_HZ) * q[None, :] / Q)       # [8, Q]
+        c = W[di, data_k] @ E.T                                                                      # [58, 8]
+        s = 10.0 * np.log10(1e-12 + np.abs(c) ** 2)
+        L = _llr_of_spectra(s) * present[di, data_k][:, None]
+        L = L.reshape(174)
+        var = np.mean((L - np.mean(L)) ** 2)
+        if not var > 0.0:                                                                            # 0 or NaN
+            f["status"] = STATUS_NOTHING
+            continue
+        llr[i] = L * np.sqrt(24.0 / var)
+        f["status"] = STATUS_VALID
+    return (llr, fits, grids) if details else (llr, fits)
+
+
+def near_tie(metric, rel=1e-5) -> bool:
+    """Whether a metric grid's two largest values differ by less than rel (relative to the largest)."""
+    m = np.sort(np.asarray(metric, dtype=np.float64).reshape(-1))
+    return bool(m[-1] - m[-2] < rel * m[-1])

@@ -161,6 +161,10 @@ struct ft8_ctx {
   std::vector<ft8_ap_hyp> ap_hyps;
   int ap_max_hard = FT8_LDPC_N;
   DevBuf ap_amax, ap_list, ap_count, ap_cand, ap_score, ap_llr, ap_plain, ap_res;
+  // coherent re-demodulation (ft8_set_coherent): the per-slot cap (0: every failed candidate) and the
+  // pass's scratch (CohPass, CohLaunch), sized for the lists of one ft8_decode_batch
+  int coh_max = 0;
+  DevBuf coh_list, coh_count, coh_cand, coh_score, coh_llr, coh_fit, coh_res;
   // the stream of the last entry point that enqueued work, and an event recorded on it after that
   // work (StreamOrder): a call on another stream first waits for it
   hipStream_t last_stream = nullptr;
@@ -724,7 +728,7 @@ SelScratch sel_scratch_at(const ft8_ctx* c, int slot0, const Grid& g, int N, boo
 int check_search_params(ft8_ctx* c, const ft8_params* p, bool limit_first) {
   if (p->steps_per_symbol <= 0 || p->bins_per_tone <= 0) return fail(c, FT8_E_ARG, "bad oversampling factors");
   const bool over = p->max_candidates > kMaxCandidates;
-  if ((p->flags & ~(FT8_FLAG_TOPK | FT8_FLAG_SUBTRACT | FT8_FLAG_AP)) && !(limit_first && over))
+  if ((p->flags & ~(FT8_FLAG_TOPK | FT8_FLAG_SUBTRACT | FT8_FLAG_AP | FT8_FLAG_COHERENT)) && !(limit_first && over))
     return fail(c, FT8_E_ARG, "unknown bits in ft8_params.flags");
   if (over) return fail(c, FT8_E_RANGE, "max_candidates > " + std::to_string(kMaxCandidates) + " is not supported");
   return FT8_OK;
@@ -875,6 +879,109 @@ int ap_pass(ft8_ctx* c, const double* llr, ft8_result* res, const int32_t* cand_
   return FT8_OK;
 }
 
+// ---- coherent re-demodulation -------------------------------------------------------------------
+int sub_q(int nsps);
+
+// the geometry, dtype and LDS checks ft8_coherent_llr and FT8_FLAG_COHERENT share; fills the launch's
+// sample and geometry fields
+int coherent_setup(ft8_ctx* c, const void* x, int dtype, int64_t n_samples, int n_slots, int64_t slot_stride,
+                   const ft8_params* p, CohLaunch* L) {
+  Geo g;
+  std::string why;
+  int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
+  if (rc) return fail(c, rc, why);
+  if (dtype != FT8_F32 && dtype != FT8_I16)
+    return fail(c, FT8_E_UNSUPPORTED, "coherent re-demodulation needs float32 or int16 samples");
+  const int Q = sub_q(g.nperseg);
+  if (Q == 0 || g.hop <= 0 || g.nperseg % g.hop != 0)
+    return fail(c, FT8_E_UNSUPPORTED, "coherent re-demodulation needs nsps with a divisor in [8, 32] and hop | nsps");
+  if (coherent_lds_bytes(g.nperseg, Q) > 64 * 1024)
+    return fail(c, FT8_E_RANGE, "coherent re-demodulation: the decimation's twiddle table does not fit 64 KB of LDS");
+  *L = CohLaunch{};
+  L->x = x;
+  L->dtype = dtype;
+  L->n_samples = n_samples;
+  L->slot_stride = slot_stride;
+  L->n_slots = n_slots;
+  L->fs = rate_of(p);
+  L->nsps = g.nperseg;
+  L->hop = g.hop;
+  L->nfft = g.nfft;
+  L->t_lo = p->t_lo;
+  L->f_lo = p->f_lo;
+  L->Q = Q;
+  return FT8_OK;
+}
+
+// listed candidates per slot of an FT8_FLAG_COHERENT batch
+int coherent_cap(const ft8_ctx* c, int N) { return c->coh_max > 0 ? std::min(c->coh_max, N) : N; }
+
+// the coherent pass's scratch for n_slots lists of M candidates (ft8hip.h states the sizes)
+int ensure_coh_scratch(ft8_ctx* c, size_t n_slots, size_t M) {
+  const size_t n = n_slots * M;
+  int rc;
+  if ((rc = ensure(c, c->coh_list, sizeof(int32_t) * n))) return rc;
+  if ((rc = ensure(c, c->coh_count, sizeof(int32_t) * n_slots))) return rc;
+  if ((rc = ensure(c, c->coh_cand, sizeof(int32_t) * 2 * n))) return rc;
+  if ((rc = ensure(c, c->coh_score, sizeof(double) * n))) return rc;
+  if ((rc = ensure(c, c->coh_llr, sizeof(double) * FT8_LDPC_N * n))) return rc;
+  if ((rc = ensure(c, c->coh_fit, sizeof(ft8_coh_fit) * n))) return rc;
+  return ensure(c, c->coh_res, sizeof(ft8_result) * n);
+}
+
+// The coherent pass over res[n_slots][N] of one chunk (coherent.hip): list, k_coherent, k_bp over the
+// lists, merge.  Like ap_pass, its scratch starts at slot `slot0` of the buffers ensure_coh_scratch sized
+// and `counter` is the k_bp claim counter its launch draws its tickets from.  L: coherent_setup's
+// launch for the chunk's samples.
+int coherent_pass(ft8_ctx* c, CohLaunch L, ft8_result* res, const int32_t* cand_count, const int32_t* cand_in,
+                  const double* score_in, int n_slots, int N, int slot0, int max_iterations, int counter,
+                  hipStream_t s) {
+  const int M = coherent_cap(c, N);
+  const size_t r0 = (size_t)slot0 * M;
+  CohPass A{};
+  A.res = res;
+  A.cand_count = cand_count;
+  A.cand_in = cand_in;
+  A.score_in = score_in;
+  A.n_slots = n_slots;
+  A.N = N;
+  A.M = M;
+  A.list = c->coh_list.as<int32_t>() + r0;
+  A.count = c->coh_count.as<int32_t>() + slot0;
+  A.cand = c->coh_cand.as<int32_t>() + 2 * r0;
+  A.score = c->coh_score.as<double>() + r0;
+  A.fit = c->coh_fit.as<ft8_coh_fit>() + r0;
+  A.res_c = c->coh_res.as<ft8_result>() + r0;
+  hipError_t e = launch_coh_list(A, s);
+  if (e != hipSuccess) return hipfail(c, e, "coherent launch");
+  L.cand = A.cand;
+  L.slot_of = nullptr;
+  L.count = A.count;
+  L.n = n_slots * M;
+  L.M = M;
+  L.llr = c->coh_llr.as<double>() + (size_t)FT8_LDPC_N * r0;
+  L.fit = const_cast<ft8_coh_fit*>(A.fit);  // k_coherent writes what k_coh_merge reads
+  if ((e = launch_coherent(L, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
+  BpLaunch B{};
+  B.cand = A.cand;
+  B.cand_score = A.score;
+  B.cand_count = A.count;
+  B.N = M;
+  B.n_slots = n_slots;
+  B.n_items = n_slots * M;
+  B.mode = 0;
+  B.max_iterations = max_iterations;
+  B.llr_in = L.llr;
+  B.res = const_cast<ft8_result*>(A.res_c);
+  B.work = c->work.as<unsigned long long>() + counter;
+  B.work_base = &c->work_base[counter];
+  wire_bp_stats(c, B);
+  B.grid_waves = c->bp_waves;
+  if ((e = launch_bp(B, s)) != hipSuccess) return hipfail(c, e, "coherent bp launch");
+  if ((e = launch_coh_merge(A, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
+  return FT8_OK;
+}
+
 int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
                 int64_t slot_stride, const ft8_params* p, ft8_result* d_out, int32_t* d_counts, int32_t cap,
                 hipStream_t s) {
@@ -892,9 +999,10 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
   const int n_chunks = (n_slots + csz - 1) / csz;
   const int n_str = (c->n_streams > 0 && n_chunks > 1) ? std::min(c->n_streams, n_chunks) : 0;
   // k_bp claim counters: [0] belongs to ft8_bp / ft8_ap_decode (a caller stream), [1 + k] to chunk k,
-  // [1 + n_chunks + k] to chunk k's a-priori pass
+  // [1 + n_chunks + k] to chunk k's a-priori pass, [1 + 2 n_chunks + k] to its coherent pass
   const bool ap = (p->flags & FT8_FLAG_AP) != 0;
-  if ((rc = ensure_work(c, (ap ? 2 : 1) * n_chunks + 1, s))) return rc;
+  const bool coh = (p->flags & FT8_FLAG_COHERENT) != 0;
+  if ((rc = ensure_work(c, (coh ? 3 : ap ? 2 : 1) * n_chunks + 1, s))) return rc;
   hipError_t e = hipSuccess;
   if (n_str > 0) {
     while ((int)c->streams.size() < n_str) {
@@ -953,7 +1061,15 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     B.warn = sc.warn;
     if ((rc = timed_launch(c, kLlr, cs, "llr launch", [&] { return launch_llr(B, cs); }))) return rc;
     if ((rc = timed_launch(c, kBp, cs, "bp launch", [&] { return launch_bp(B, cs); }))) return rc;
-    // the tie order k_compact applies permutes positions, not records, so AP works on res_all as it is
+    // the tie order k_compact applies permutes positions, not records, so the coherent and AP passes
+    // work on res_all as it is; the coherent pass leaves c->llr alone, so AP sees the STFT LLRs
+    if (coh) {
+      CohLaunch L;
+      if ((rc = coherent_setup(c, xs, dtype, n_samples, ns, slot_stride, p, &L))) return rc;
+      if ((rc = coherent_pass(c, L, B.res, cand_count, cand, cand_score, ns, N, c0, p->max_iterations,
+                              1 + 2 * n_chunks + k, cs)))
+        return rc;
+    }
     if (ap && (rc = ap_pass(c, B.llr_in, B.res, cand_count, cand, cand_score, ns, N, c0, p->max_iterations, nullptr,
                             1 + n_chunks + k, cs)))
       return rc;
@@ -975,7 +1091,7 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     if ((e = hipEventRecord(c->joins[i], c->streams[i])) != hipSuccess) return hipfail(c, e, "join");
     if ((e = hipStreamWaitEvent(s, c->joins[i], 0)) != hipSuccess) return hipfail(c, e, "join wait");
   }
-  c->replay_ok = n_chunks == 1 && !ap;  // a replayed k_bp would overwrite the rescued records
+  c->replay_ok = n_chunks == 1 && !ap && !coh;  // a replayed k_bp would overwrite the rescued records
   return FT8_OK;
 }
 
@@ -1417,6 +1533,36 @@ int ft8_ap_decode(ft8_ctx* c, const double* d_llr, ft8_result* d_res, int32_t n,
   return ap_pass(c, d_llr, d_res, nullptr, nullptr, nullptr, 1, n, 0, max_iterations, d_hard, 0, s);
 }
 
+int ft8_set_coherent(ft8_ctx* c, int32_t max_per_slot) {
+  if (!c || max_per_slot < 0) return fail(c, FT8_E_ARG, "bad argument");
+  c->coh_max = max_per_slot;
+  return FT8_OK;
+}
+
+int ft8_coherent_llr(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
+                     int64_t slot_stride, const ft8_params* p, const int32_t* d_cand, const int32_t* d_slot_of,
+                     int32_t n, double* d_llr_out, ft8_coh_fit* d_fit_out, void* stream) {
+  if (c) c->replay_ok = c->snr_ok = false;
+  if (!c || !p || n < 0 || n_slots < 0 || n_samples < 0 || slot_stride < n_samples ||
+      (n > 0 && (!d_samples || !d_cand || !d_slot_of || !d_llr_out || !d_fit_out)))
+    return fail(c, FT8_E_ARG, "bad argument");
+  if (p->steps_per_symbol <= 0 || p->bins_per_tone <= 0) return fail(c, FT8_E_ARG, "bad oversampling factors");
+  DeviceGuard dg(c->device);
+  CohLaunch L;
+  int rc = coherent_setup(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, &L);
+  if (rc) return rc;
+  if (n == 0) return FT8_OK;
+  L.cand = d_cand;
+  L.slot_of = d_slot_of;
+  L.n = n;
+  L.M = 0;
+  L.llr = d_llr_out;
+  L.fit = d_fit_out;
+  hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = launch_coherent(L, s);
+  return e == hipSuccess ? FT8_OK : hipfail(c, e, "coherent launch");
+}
+
 int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
                      int64_t slot_stride, const ft8_params* p, ft8_result* d_out, int32_t* d_counts,
                      int32_t cap, void* stream) {
@@ -1436,6 +1582,12 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   if (p->flags & FT8_FLAG_AP) {  // also where there is nothing to search
     if (p->flags & FT8_FLAG_SUBTRACT) return fail(c, FT8_E_UNSUPPORTED, "FT8_FLAG_AP with FT8_FLAG_SUBTRACT is not supported");
     if (c->ap_hyps.empty()) return fail(c, FT8_E_ARG, "FT8_FLAG_AP without hypotheses (ft8_set_ap)");
+  }
+  if (p->flags & FT8_FLAG_COHERENT) {  // also where there is nothing to search
+    if (p->flags & FT8_FLAG_SUBTRACT)
+      return fail(c, FT8_E_UNSUPPORTED, "FT8_FLAG_COHERENT with FT8_FLAG_SUBTRACT is not supported");
+    CohLaunch probe;
+    if ((rc = coherent_setup(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, &probe))) return rc;
   }
   const int T = p->t_hi - p->t_lo, F = p->f_hi - p->f_lo;
   const bool f64 = is_f64_dtype(dtype);
@@ -1458,6 +1610,8 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   if ((rc = ensure(c, c->llr, sizeof(double) * FT8_LDPC_N * (size_t)n_slots * N))) return rc;
   if ((rc = ensure_sel_scratch(c, n_slots, gr, N, f64))) return rc;
   if ((p->flags & FT8_FLAG_AP) && (rc = ensure_ap_scratch(c, (size_t)n_slots, (size_t)n_slots * N))) return rc;
+  if ((p->flags & FT8_FLAG_COHERENT) && (rc = ensure_coh_scratch(c, (size_t)n_slots, (size_t)coherent_cap(c, N))))
+    return rc;
   if (!(p->flags & FT8_FLAG_SUBTRACT)) {
     if ((rc = decode_pass(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, d_out, d_counts, cap, s))) return rc;
     remember_snr_batch(c, p, g, n_slots, T, F, cap, f64);

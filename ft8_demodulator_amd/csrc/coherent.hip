@@ -1,0 +1,426 @@
+// coherent.hip -- coherent re-demodulation of candidates from the samples (FT8_FLAG_COHERENT,
+// ft8_coherent_llr; include/ft8hip.h, "coherent re-demodulation"; gfx950).
+//
+// Build-defined: the reference forms its LLRs once, from the dB bins of a one-symbol Hann STFT
+// (ft8_decode.py:151-188).  Here a candidate BP failed on is demodulated again from the samples:
+//   k_coh_list   one wave per slot: the failed candidates (ok == 0) in candidate order, at most M
+//   k_coherent   one 256-lane workgroup per list position (a slot's positions on one XCD):
+//     1. baseband: the samples around the candidate are mixed down to the centre of the 8-tone band
+//        and box-car decimated to Q samples per symbol (D = nsps / Q input samples each) -- the
+//        arithmetic of k_sub_est's phase 2 (subtract.hip): a D-entry twiddle table, two fmas per sample;
+//     2. sync: over start offsets of +-hop/2 (steps of D samples) and tone-0 offsets of +-bin/2 (5
+//        points) the 21 Costas symbols are correlated (coherent within a symbol, power summed over the
+//        symbols that lie inside the slot); first largest wins, the tone-0 offset refined by a parabola;
+//     3. the 58 x 8 tone spectra at the refined point (matched rectangular windows), the reference's
+//        Gray map and max-of-4 LLRs in double, ftx_normalize_logl with NumPy's pairwise sums.
+//   k_bp         unchanged (launch_bp, mode 0 over the compacted lists)
+//   k_coh_merge  one wave per list position: a valid fit whose attempt decoded rewrites its record
+// No atomics; every sample index is range-checked or proven in range in 64-bit arithmetic.
+#include "ft8_internal.h"
+
+namespace ft8 {
+namespace {
+
+constexpr int kCohThreads = 256;
+constexpr int kCohMaxQ = 32;
+constexpr int kCohMaxT = 2 * (kCohMaxQ / 2) + 1;  // start offsets: 2 ceil(Q / (2 sps)) + 1
+constexpr int kCohNF = 5;                         // tone-0 offsets (j - 2) bin / 4
+constexpr int kSymbols = 79, kSync = 21, kData = 58;
+constexpr double kToneHz = 6.25;
+
+// float2 words of the padded baseband rows (-1 .. 81 of Q + 1), rounded up to a 16-B multiple
+__host__ __device__ inline int coh_z_words(int Q) { return ((kSymbols + 4) * (Q + 1) + 1) & ~1; }
+__host__ __device__ inline int coh_rot_words(int Q) { return kCohNF * 8 * (Q + 1); }
+
+template <typename InT>
+__device__ __forceinline__ float coh_sample(const InT* x, int64_t i);
+template <>
+__device__ __forceinline__ float coh_sample<float>(const float* x, int64_t i) { return x[i]; }
+template <>
+__device__ __forceinline__ float coh_sample<int16_t>(const int16_t* x, int64_t i) {
+  return (float)x[i] / 32767.0f;  // read_wave_file scaling, as the STFT applies it
+}
+
+// four consecutive samples in one load (float: 16 B, 4-byte aligned; int16: 8 B, 2-byte aligned)
+constexpr int kCohLd = 8;
+template <typename InT>
+__device__ __forceinline__ float4 coh_load4(const InT* p);
+template <>
+__device__ __forceinline__ float4 coh_load4<float>(const float* p) {
+  float4 v;
+  __builtin_memcpy(&v, p, sizeof(v));
+  return v;
+}
+template <>
+__device__ __forceinline__ float4 coh_load4<int16_t>(const int16_t* p) {
+  short4 v;
+  __builtin_memcpy(&v, p, sizeof(v));
+  return make_float4((float)v.x / 32767.0f, (float)v.y / 32767.0f, (float)v.z / 32767.0f, (float)v.w / 32767.0f);
+}
+
+__device__ __forceinline__ int costas_tone(int i) {  // 3 1 4 0 6 5 2, packed in nibbles
+  return (int)((0x2560413u >> (4 * i)) & 7u);
+}
+__device__ __forceinline__ int gray_map(int j) {     // FT8_Gray_map 0 1 3 2 5 6 4 7
+  return (int)((0x74652310u >> (4 * j)) & 7u);
+}
+
+// exp(-2 pi i cyc) from the exact phase
+__device__ __forceinline__ float2 rot_of(double cyc) {
+  float s, c;
+  sincospif((float)(-2.0 * (cyc - floor(cyc))), &s, &c);
+  return make_float2(c, s);
+}
+
+// blank LLRs and a fit that carries only its status
+__device__ void coh_blank(double* llr, ft8_coh_fit* fit, int status) {
+  for (int i = threadIdx.x; i < FT8_LDPC_N; i += kCohThreads) llr[i] = 0.0;
+  if (threadIdx.x == 0) {
+    ft8_coh_fit f{};
+    f.status = (uint8_t)status;
+    *fit = f;
+  }
+}
+
+template <typename InT>
+__global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a) {
+  FT8_RACE_PROLOGUE();
+  // dynamic LDS: z in rows of Q + 1 (row r + 1 holds z[1 + r Q .. 1 + (r + 1) Q), r = -1 .. 81: the
+  // layout of k_sub_est, whose bank arithmetic it keeps), the D twiddles of phase 1, the rotation
+  // table [5 * 8][Q + 1] of phase 2 (phase 3 rebuilds its first 8 rows for the refined offset)
+  extern __shared__ float4 s_dyn[];
+  float2* s_z = reinterpret_cast<float2*>(s_dyn);
+  __shared__ float s_part[kCohMaxT * kCohNF * 3];
+  __shared__ float s_metric[kCohMaxT * kCohNF];
+  __shared__ float s_pow[kData * 8];
+  __shared__ double s_llr[FT8_LDPC_N + 2];
+  __shared__ double s_sq[FT8_LDPC_N + 2];
+  __shared__ double s_sum[16];
+  __shared__ double s_bc;
+  __shared__ int s_flag, s_best;
+
+  // list position -> (slot, candidate).  Per-slot lists: a slot's positions on one XCD (workgroup id
+  // % 8, as k_sub_est), so its samples are served from that XCD's L2
+  int64_t pos;
+  int slot;
+  if (a.slot_of) {
+    pos = blockIdx.x;
+    if (pos >= a.n) return;
+    slot = a.slot_of[pos];
+  } else {
+    const int w = blockIdx.x, j8 = w / 8;
+    slot = (w % 8) + 8 * (j8 / a.M);
+    const int j = j8 % a.M;
+    if (slot >= a.n_slots || j >= a.count[slot]) return;
+    pos = (int64_t)slot * a.M + j;
+  }
+  double* llr_out = a.llr + pos * FT8_LDPC_N;
+  ft8_coh_fit* fit_out = a.fit + pos;
+  if (slot < 0 || slot >= a.n_slots) {
+    coh_blank(llr_out, fit_out, 3);
+    return;
+  }
+  const InT* x = reinterpret_cast<const InT*>(a.x) + (int64_t)slot * a.slot_stride;
+  const int nsps = a.nsps, Q = a.Q, D = nsps / Q;
+  const int sps = nsps / a.hop;
+  const int Mt = (Q + 2 * sps - 1) / (2 * sps);  // ceil((hop / 2) / D)
+  const int Mg = Mt + 1, nT = 2 * Mt + 1;
+  const int Mz = kSymbols * Q + 2 * Mg;
+  auto z_at = [Q](int m) { const int u = m - 1 + Q; return u + (int)((unsigned)u / (unsigned)Q); };
+  const double fs = a.fs;
+  const double bin = fs / (double)a.nfft;
+  const int64_t s0 = ((int64_t)a.t_lo + a.cand[2 * pos]) * a.hop;
+  const double fmix = (double)((int64_t)a.f_lo + a.cand[2 * pos + 1]) * bin + 3.5 * kToneHz;
+  const int64_t nb = s0 - (int64_t)Mg * D;
+  // symbol k at start offset d - Mt is present when its nsps input samples lie in [0, n_samples)
+  auto present = [&](int d, int k) {
+    const int64_t first = nb + ((int64_t)(1 + d) + (int64_t)k * Q) * D;
+    return first >= 0 && first + nsps <= a.n_samples;
+  };
+
+  // ---- nothing to measure: no Costas symbol inside the slot at any start offset
+  if (threadIdx.x == 0) s_flag = 0;
+  __syncthreads();
+  for (int e = threadIdx.x; e < nT * kSync; e += kCohThreads) {
+    const int d = e / kSync, si = e - d * kSync;
+    if (present(d, (si / 7) * 36 + si % 7)) s_flag = 1;
+  }
+  __syncthreads();
+  if (!s_flag) {
+    coh_blank(llr_out, fit_out, 2);
+    return;
+  }
+
+  // ---- 1. z[m] = w_m sum_i x[nb + m D + i] t_i, t_i = exp(-2 pi i fmix i / fs) from a table of D
+  // exact twiddles, w_m = exp(-2 pi i fmix (nb + m D) / fs); a thread owns z[tid + 256 j].  A window
+  // inside the slot reads its samples four at a time, unchecked; else every sample is tested.
+  float2* s_tw = s_z + coh_z_words(Q);
+  float2* s_R = s_tw + ((D + 1) & ~1);
+  for (int i = threadIdx.x; i < D; i += kCohThreads) s_tw[i] = rot_of(fmix * (double)i / fs);
+  // rotation powers of phase 2, each from its exact phase: row j * 8 + t, entry q
+  for (int e = threadIdx.x; e < coh_rot_words(Q); e += kCohThreads) {
+    const int ft = e / (Q + 1), q = e - ft * (Q + 1);
+    const int t = ft & 7, j = ft >> 3;
+    const double nu = (double)t - 3.5 + ((double)(j - 2) * bin / 4.0) / kToneHz;  // tones relative to fmix
+    s_R[e] = rot_of(nu * (double)q / (double)Q);
+  }
+  __syncthreads();
+  {
+    const bool inside = nb >= 0 && nb + (int64_t)Mz * D <= a.n_samples;  // workgroup-uniform
+#pragma unroll 1
+    for (int m = threadIdx.x; m < Mz; m += kCohThreads) {
+      const int64_t n0 = nb + (int64_t)m * D;
+      const InT* xp = x + n0;
+      float ax = 0.f, ay = 0.f;
+      if (inside && (D & 3) == 0) {
+        // kCohLd loads of four samples are issued before the first is used: one load per trip left a
+        // lane's L2 hits a full latency apart.  The fmas keep their order.  Past D a trip repeats the
+        // last in-range load and does not use it.
+        for (int i0 = 0; i0 < D; i0 += 4 * kCohLd) {
+          float4 v[kCohLd];
+#pragma unroll
+          for (int u = 0; u < kCohLd; ++u) v[u] = coh_load4<InT>(xp + min(i0 + 4 * u, D - 4));
+#pragma unroll
+          for (int u = 0; u < kCohLd; ++u) {
+            const int i = i0 + 4 * u;
+            if (i < D) {
+              const float4 t01 = *reinterpret_cast<const float4*>(s_tw + i);
+              const float4 t23 = *reinterpret_cast<const float4*>(s_tw + i + 2);
+              ax = fmaf(v[u].x, t01.x, ax);
+              ay = fmaf(v[u].x, t01.y, ay);
+              ax = fmaf(v[u].y, t01.z, ax);
+              ay = fmaf(v[u].y, t01.w, ay);
+              ax = fmaf(v[u].z, t23.x, ax);
+              ay = fmaf(v[u].z, t23.y, ay);
+              ax = fmaf(v[u].w, t23.z, ax);
+              ay = fmaf(v[u].w, t23.w, ay);
+            }
+          }
+        }
+      } else {
+        for (int i = 0; i < D; ++i) {
+          const int64_t n = n0 + i;
+          if (n >= 0 && n < a.n_samples) {
+            const float v = coh_sample<InT>(xp, i);
+            const float2 t = s_tw[i];
+            ax = fmaf(v, t.x, ax);
+            ay = fmaf(v, t.y, ay);
+          }
+        }
+      }
+      const float2 w = rot_of(fmix * (double)n0 / fs);
+      s_z[z_at(m)] = make_float2(ax * w.x - ay * w.y, ax * w.y + ay * w.x);
+    }
+  }
+  __syncthreads();
+
+  // ---- 2. sync: item (start offset d, tone-0 offset j, Costas block b) sums its 7 symbols' powers in
+  // symbol order; window element q of symbol k at offset d is z[1 + k Q + d + q]
+  for (int e = threadIdx.x; e < nT * kCohNF * 3; e += kCohThreads) {
+    const int d = e / (kCohNF * 3), r = e - d * (kCohNF * 3);
+    const int j = r / 3, b = r - 3 * j;
+    float sum = 0.f;
+    for (int i = 0; i < 7; ++i) {
+      const int k = 36 * b + i;
+      if (!present(d, k)) continue;
+      const float2* Wp = s_R + (j * 8 + costas_tone(i)) * (Q + 1);
+      const float2* zp = s_z + (k + 1) * (Q + 1);
+      float cx = 0.f, cy = 0.f;
+      for (int q = 0; q < Q; ++q) {
+        const int jj = d + q;  // < 3 Q: the row padding without a division
+        const float2 z = zp[jj + (jj >= Q) + (jj >= 2 * Q)], W = Wp[q];
+        cx = fmaf(z.x, W.x, fmaf(-z.y, W.y, cx));
+        cy = fmaf(z.x, W.y, fmaf(z.y, W.x, cy));
+      }
+      sum += cx * cx + cy * cy;
+    }
+    s_part[e] = sum;
+  }
+  __syncthreads();
+  for (int h = threadIdx.x; h < nT * kCohNF; h += kCohThreads)
+    s_metric[h] = (s_part[3 * h] + s_part[3 * h + 1]) + s_part[3 * h + 2];
+  __syncthreads();
+  if (threadIdx.x == 0) {  // the first largest, start offset outer, tone-0 offset inner
+    int b = 0;
+    for (int h = 1; h < nT * kCohNF; ++h)
+      if (s_metric[h] > s_metric[b]) b = h;
+    s_best = b;
+  }
+  __syncthreads();
+  const int hb = s_best;
+  const int db = hb / kCohNF, jb = hb - db * kCohNF;
+  double delta = 0.0;
+  if (jb > 0 && jb < kCohNF - 1) {
+    const double m_ = s_metric[hb - 1], m0 = s_metric[hb], mp = s_metric[hb + 1];
+    const double den = m_ - 2.0 * m0 + mp;
+    if (den < 0.0) delta = 0.5 * (m_ - mp) / den;
+  }
+  const double df = ((double)(jb - 2) + delta) * bin / 4.0;
+
+  // ---- 3. spectra of the data symbols at (db, df); the rotations replace rows 0 .. 7 of the table
+  for (int e = threadIdx.x; e < 8 * (Q + 1); e += kCohThreads) {
+    const int t = e / (Q + 1), q = e - t * (Q + 1);
+    s_R[e] = rot_of(((double)t - 3.5 + df / kToneHz) * (double)q / (double)Q);
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < kData * 8; e += kCohThreads) {
+    const int kd = e >> 3, t = e & 7;
+    const int k = kd + (kd < 29 ? 7 : 14);
+    const float2* Wp = s_R + t * (Q + 1);
+    const float2* zp = s_z + (k + 1) * (Q + 1);
+    float cx = 0.f, cy = 0.f;
+    for (int q = 0; q < Q; ++q) {
+      const int jj = db + q;
+      const float2 z = zp[jj + (jj >= Q) + (jj >= 2 * Q)], W = Wp[q];
+      cx = fmaf(z.x, W.x, fmaf(-z.y, W.y, cx));
+      cy = fmaf(z.x, W.y, fmaf(z.y, W.x, cy));
+    }
+    s_pow[e] = cx * cx + cy * cy;
+  }
+  __syncthreads();
+  if (threadIdx.x < kData) {  // ft8_extract_symbol in double
+    const int kd = threadIdx.x;
+    const int k = kd + (kd < 29 ? 7 : 14);
+    double l0 = 0.0, l1 = 0.0, l2 = 0.0;
+    if (present(db, k)) {
+      double s2[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s2[j] = 10.0 * log10(1e-12 + (double)s_pow[kd * 8 + gray_map(j)]);
+      auto max4 = [](double p, double q, double r, double s) { return fmax(fmax(p, q), fmax(r, s)); };
+      l0 = max4(s2[4], s2[5], s2[6], s2[7]) - max4(s2[0], s2[1], s2[2], s2[3]);
+      l1 = max4(s2[2], s2[3], s2[6], s2[7]) - max4(s2[0], s2[1], s2[4], s2[5]);
+      l2 = max4(s2[1], s2[3], s2[5], s2[7]) - max4(s2[0], s2[2], s2[4], s2[6]);
+    }
+    s_llr[3 * kd] = l0;
+    s_llr[3 * kd + 1] = l1;
+    s_llr[3 * kd + 2] = l2;
+  }
+  __syncthreads();
+  // ftx_normalize_logl with NumPy's pairwise sums (k_llr's: 8 accumulators, blocks of 80 + 94)
+  auto pairwise174 = [&](const double* v) {
+    const int l = threadIdx.x;
+    if (l < 8) {
+      double r = v[l];
+      for (int i = 8; i < 80; i += 8) r += v[i + l];
+      s_sum[l] = r;
+    } else if (l < 16) {
+      const int j = l - 8;
+      double r = v[80 + j];
+      for (int i = 8; i < 88; i += 8) r += v[80 + i + j];
+      s_sum[l] = r;
+    }
+    __syncthreads();
+    if (l == 0) {
+      const double* p = s_sum;
+      const double s1 = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+      double s2 = ((p[8] + p[9]) + (p[10] + p[11])) + ((p[12] + p[13]) + (p[14] + p[15]));
+      for (int i = 168; i < FT8_LDPC_N; ++i) s2 += v[i];
+      s_bc = 0.0 + (s1 + s2);
+    }
+    __syncthreads();
+    const double tot = s_bc;
+    __syncthreads();
+    return tot;
+  };
+  const double mean = pairwise174(s_llr) / 174.0;
+  for (int i = threadIdx.x; i < FT8_LDPC_N; i += kCohThreads) {
+    const double dd = s_llr[i] - mean;
+    s_sq[i] = dd * dd;
+  }
+  __syncthreads();
+  const double var = pairwise174(s_sq) / 174.0;
+  const bool valid = var > 0.0;  // false for 0 and NaN
+  const double scale = valid ? sqrt(24.0 / var) : 0.0;
+  for (int i = threadIdx.x; i < FT8_LDPC_N; i += kCohThreads) llr_out[i] = valid ? s_llr[i] * scale : 0.0;
+  if (threadIdx.x == 0) {
+    int ns = 0;
+    for (int si = 0; si < kSync; ++si) ns += present(db, (si / 7) * 36 + si % 7) ? 1 : 0;
+    ft8_coh_fit f{};
+    f.dt_s = (float)((double)(db - Mt) * (double)D / fs);
+    f.df_hz = (float)df;
+    f.metric = s_metric[hb];
+    f.n_sync = (uint8_t)ns;
+    f.status = valid ? 0 : 2;
+    f.dt_index = (int8_t)(db - Mt);
+    f.df_index = (uint8_t)jb;
+    *fit_out = f;
+  }
+}
+
+__device__ __forceinline__ int coh_slot_count(const CohPass& a, int slot) {
+  return a.cand_count ? min(a.N, a.cand_count[slot]) : a.N;
+}
+
+// one wave per slot: the first M failed candidates in candidate order (ballot / popcount scan, as k_ap_list)
+__global__ __launch_bounds__(kWave) void k_coh_list(CohPass a) {
+  const int slot = blockIdx.x, lane = threadIdx.x;
+  const int nc = coh_slot_count(a, slot);
+  const int64_t s0 = (int64_t)slot * a.N, l0 = (int64_t)slot * a.M;
+  int base = 0;
+  for (int c0 = 0; c0 < nc && base < a.M; c0 += kWave) {
+    const int c = c0 + lane;
+    const bool take = c < nc && !a.res[s0 + c].ok;
+    const unsigned long long m = __ballot(take);
+    const int at = base + __popcll(m & ((1ull << lane) - 1ull));
+    if (take && at < a.M) {
+      a.list[l0 + at] = c;
+      a.cand[2 * (l0 + at)] = a.cand_in[2 * (s0 + c)];
+      a.cand[2 * (l0 + at) + 1] = a.cand_in[2 * (s0 + c) + 1];
+      a.score[l0 + at] = a.score_in[s0 + c];
+    }
+    base += __popcll(m);
+  }
+  if (lane == 0) a.count[slot] = min(base, a.M);
+}
+
+// one wave per list position: a valid fit whose attempt the tail accepted rewrites its record
+__global__ __launch_bounds__(4 * kWave) void k_coh_merge(CohPass a) {
+  const int lane = threadIdx.x % kWave;
+  const int64_t pos = (int64_t)blockIdx.x * 4 + threadIdx.x / kWave;
+  if (pos >= (int64_t)a.n_slots * a.M) return;
+  const int slot = (int)(pos / a.M), j = (int)(pos % a.M);
+  if (j >= a.count[slot]) return;
+  const ft8_result& r = a.res_c[pos];
+  if (!r.ok || a.fit[pos].status != 0) return;
+  if (lane == 0) {
+    const int64_t src = (int64_t)slot * a.N + a.list[pos];
+    ft8_result w = a.res[src];
+    w.ok = 1;
+    for (int i = 0; i < 10; ++i) w.payload[i] = r.payload[i];
+    w.crc_extracted = r.crc_extracted;
+    w.crc_calculated = r.crc_calculated;
+    w.ldpc_errors = r.ldpc_errors;
+    w.pass_index = (uint8_t)(w.pass_index | 2);
+    a.res[src] = w;
+  }
+}
+
+}  // namespace
+
+size_t coherent_lds_bytes(int nsps, int Q) {
+  const int D = nsps / Q;
+  return sizeof(float2) * ((size_t)coh_z_words(Q) + (size_t)((D + 1) & ~1) + (size_t)coh_rot_words(Q));
+}
+
+hipError_t launch_coherent(const CohLaunch& a, hipStream_t s) {
+  const int64_t grid = a.slot_of ? (int64_t)a.n : (int64_t)((a.n_slots + 7) / 8) * 8 * a.M;
+  if (grid <= 0) return hipSuccess;
+  const size_t lds = coherent_lds_bytes(a.nsps, a.Q);
+  if (a.dtype == FT8_I16) return lds_launch(k_coherent<int16_t>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a);
+  return lds_launch(k_coherent<float>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a);
+}
+
+hipError_t launch_coh_list(const CohPass& a, hipStream_t s) {
+  if (a.n_slots <= 0 || a.M <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_coh_list, dim3(a.n_slots), dim3(kWave), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_coh_merge(const CohPass& a, hipStream_t s) {
+  if (a.n_slots <= 0 || a.M <= 0) return hipSuccess;
+  const unsigned blocks = (unsigned)(((int64_t)a.n_slots * a.M + 3) / 4);
+  hipLaunchKernelGGL(k_coh_merge, dim3(blocks), dim3(4 * kWave), 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace ft8

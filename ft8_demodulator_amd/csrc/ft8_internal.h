@@ -310,6 +310,46 @@ hipError_t launch_ap_amax(const ApLaunch& a, hipStream_t s);
 hipError_t launch_ap_prepare(const ApLaunch& a, hipStream_t s);  // k_ap_list, k_ap_clamp
 hipError_t launch_ap_merge(const ApLaunch& a, hipStream_t s);
 
+// ---- coherent re-demodulation (coherent.hip) ---------------------------------------------------
+// k_coherent over a candidate list (ft8hip.h, "coherent re-demodulation"): either an explicit list
+// (slot_of non-null: n candidates, workgroup = list position) or per-slot lists [n_slots][M] with
+// count[n_slots] entries each (a slot's positions on one XCD).
+struct CohLaunch {
+  const void* x;               // samples [n_slots][slot_stride], F32 or I16
+  int dtype;
+  int64_t n_samples, slot_stride;
+  int n_slots;
+  double fs;
+  int nsps, hop, nfft, t_lo, f_lo;
+  int Q;                       // decimated samples per symbol (nsps % Q == 0)
+  const int32_t* cand;         // [positions][2] = (abs_time, abs_freq)
+  const int32_t* slot_of;      // explicit list: [n]; null: per-slot lists
+  const int32_t* count;        // per-slot lists: [n_slots]
+  int n, M;
+  double* llr;                 // [positions][174]
+  ft8_coh_fit* fit;            // [positions]
+};
+size_t coherent_lds_bytes(int nsps, int Q);   // k_coherent's dynamic LDS
+hipError_t launch_coherent(const CohLaunch& a, hipStream_t s);
+// The pass around it inside ft8_decode_batch: k_coh_list (per slot the first M candidates with ok == 0
+// of res[n_slots][N], in candidate order -> list / cand / score [n_slots][M], count), then k_coherent
+// and launch_bp in mode 0 over those lists (fit, res_c), then k_coh_merge.
+struct CohPass {
+  ft8_result* res;             // in / out: the records plain BP wrote
+  const int32_t* cand_count;   // [n_slots], null: every slot holds N records
+  const int32_t* cand_in;      // [n_slots][N][2]
+  const double* score_in;      // [n_slots][N]
+  int n_slots, N, M;
+  int32_t* list;               // [n_slots][M] original indices of the listed candidates
+  int32_t* count;              // [n_slots]
+  int32_t* cand;               // compacted [n_slots][M][2]
+  double* score;               // compacted
+  const ft8_coh_fit* fit;      // k_coherent's fits of the lists
+  const ft8_result* res_c;     // launch_bp's records of them
+};
+hipError_t launch_coh_list(const CohPass& a, hipStream_t s);
+hipError_t launch_coh_merge(const CohPass& a, hipStream_t s);
+
 // ft8_pack_decodes (bp.hip): one workgroup packs a batch's decodes for the all-gather
 inline __host__ __device__ int64_t pack_header_bytes(int n_slots) { return 8 + ((4 * (int64_t)n_slots + 7) & ~7ll); }
 hipError_t launch_pack(const ft8_result* rec, const int32_t* counts, int n_slots, int cap, int capacity,

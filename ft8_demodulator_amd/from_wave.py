@@ -50,11 +50,13 @@ def read_wave_file(wave_path: str, verbose: bool = False) -> tuple:
     return x, sample_rate
 
 
-def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_errors: int = None, device=None,
-                 verbose: bool = False, **decode_kw) -> tuple:
-    """One file, any PCM width, as one slot through _pipeline.decode_one -> (results, snr_db, patterns).
-    snr_db (with snr, else None): one SNR in 2500 Hz per result.  patterns (with ap, else None): per
-    result the a-priori pattern that rescued it, None for a plain decode."""
+def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_errors: int = None, coherent=None,
+                 device=None, verbose: bool = False, **decode_kw) -> tuple:
+    """One file, any PCM width, as one slot through _pipeline.decode_one -> (results, snr_db, patterns)
+    and, with coherent, a fourth entry.  snr_db (with snr, else None): one SNR in 2500 Hz per result.
+    patterns (with ap, else None): per result the a-priori pattern that rescued it, None for a plain
+    decode.  fits (with coherent): per result (dt_s, df_hz) of the coherent fit that rescued it (one
+    ft8_coherent_llr call for those records), None for any other decode."""
     import torch
     from . import _lib
     from ._pipeline import decode_one
@@ -71,9 +73,31 @@ def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_erro
         x, code = torch.from_numpy(h).to(dev), _lib.FT8_F32
     ap = None if ap is None else tuple(ap)
     results, reports, recs = decode_one(x, code, sample_rate, snr=snr, ap=ap, ap_max_hard_errors=ap_max_hard_errors,
-                                        **decode_kw)
-    return (results, snr_db_or_nan(reports) if snr else None,
-            None if ap is None else [ap[ap_index(r) - 1] if ap_index(r) else None for r in recs])
+                                        coherent=coherent, **decode_kw)
+    out = (results, snr_db_or_nan(reports) if snr else None,
+           None if ap is None else [ap[ap_index(r) - 1] if ap_index(r) else None for r in recs])
+    if coherent is None:
+        return out
+    return out + (_coherent_fits(x, code, sample_rate, recs, decode_kw),)
+
+
+def _coherent_fits(x, code, sample_rate, recs, decode_kw):
+    """(dt_s, df_hz) of every record the coherent pass rescued (the stage call on those candidates), None
+    for the others."""
+    from ._pipeline import make_plan
+    from .coherent import coherent_index
+    from .ldpc_decoder import coherent_llr_batch
+    fits = [None] * len(recs)
+    idx = [i for i, r in enumerate(recs) if coherent_index(r)]
+    if idx:
+        bpt, sps = decode_kw.get("bins_per_tone", 2), decode_kw.get("steps_per_symbol", 2)
+        plan = make_plan(int(x.shape[0]), sample_rate, bpt, sps, decode_kw.get("freq_min"), decode_kw.get("freq_max"),
+                         decode_kw.get("time_min"), decode_kw.get("time_max"))
+        cand = [(int(recs[i]["abs_time"]), int(recs[i]["abs_freq"])) for i in idx]
+        _, f = coherent_llr_batch(x, cand, [0] * len(idx), sample_rate, bpt, sps, plan.t_lo, plan.f_lo, code=code)
+        for i, fi in zip(idx, f):
+            fits[i] = (float(fi["dt_s"]), float(fi["df_hz"]))
+    return fits
 
 
 def decode_ft8_from_wave(wave_path: str, freq_min: float = None, freq_max: float = None, time_min: float = None,
@@ -122,10 +146,11 @@ def decode_ft8_from_wave_ap(wave_path: str, ap, ap_max_hard_errors: int = None, 
     return results, patterns, snr_db
 
 
-def _print_results(results, text: bool = False, snr=None, ap=None):
+def _print_results(results, text: bool = False, snr=None, ap=None, coherent=None):
     """text: one extra `Message:` line per result, the payload unpacked to message text.  snr (one
     value per result): one extra `SNR:` line per result, dB in 2500 Hz.  ap (one pattern or None per
-    result): one extra `AP: <pattern>` line for every a-priori decode."""
+    result): one extra `AP: <pattern>` line for every a-priori decode.  coherent (one (dt_s, df_hz) or
+    None per result): one extra `Coherent:` line for every decode from the coherent LLRs."""
     if not results:
         print("No FT8 messages decoded")
         return
@@ -146,6 +171,8 @@ def _print_results(results, text: bool = False, snr=None, ap=None):
             print(f"Message: {texts.pop(0)}")
         if ap is not None and ap[k] is not None:
             print(f"AP: {ap[k]}")
+        if coherent is not None and coherent[k] is not None:
+            print(f"Coherent: dt {coherent[k][0] * 1e3:+.2f} ms, df {coherent[k][1]:+.2f} Hz")
         print(f"CRC check: {status.crc_calculated}")
         print(f"LDPC errors: {status.ldpc_errors}")
         print("-" * 50)
@@ -192,7 +219,11 @@ def main(argv=None):
                              '"K1ABC ? ?" (repeatable, tried in order; an AP decode is marked with its pattern)')
     parser.add_argument("--ap-max-hard-errors", type=int, default=None,
                         help="most hard decisions of an AP decode that may contradict the received bits (default 36)")
+    parser.add_argument("--coherent", nargs="?", type=int, const=-1, default=None, metavar="N",
+                        help="demodulate the N best-scoring failed candidates again coherently from the samples "
+                             "(default 32, 0: all; such a decode is marked with its fit's time and frequency offset)")
     args = parser.parse_args(argv)
+    coherent = None if args.coherent is None else (True if args.coherent < 0 else args.coherent)
     paths = args.wave_file
     for path in paths:
         if not os.path.exists(path):
@@ -202,11 +233,13 @@ def main(argv=None):
               bins_per_tone=args.bins_per_tone, steps_per_symbol=args.steps_per_symbol,
               max_candidates=args.max_candidates, min_score=args.min_score, max_iterations=args.max_iterations)
     many = len(paths) > 1
-    if args.ap or args.snr:
+    if args.ap or args.snr or coherent is not None:
         # the report comes from the decode's own waterfall, an AP decode's mark from its own record:
         # one file at a time, each decoded once (lazily: a file is printed before the next is decoded)
         if args.correction:
             decode_ft8_from_wave(paths[0], correction=True)  # raises as without the flags
+        if coherent is not None:
+            kw = dict(kw, coherent=coherent)
         decoded = (_decode_file(path, snr=args.snr, ap=args.ap, ap_max_hard_errors=args.ap_max_hard_errors, **kw)
                    for path in paths)
     elif many:
@@ -214,10 +247,10 @@ def main(argv=None):
     else:
         decoded = [(decode_ft8_from_wave(paths[0], correction=args.correction, **kw), None, None)]
     per_file = []
-    for path, (results, snr, patterns) in zip(paths, decoded):
+    for path, (results, snr, patterns, *fits) in zip(paths, decoded):
         if many:
             print(f"\n== {path}")
-        _print_results(results, args.text, snr, patterns)
+        _print_results(results, args.text, snr, patterns, fits[0] if fits else None)
         per_file.append(results)
     return per_file if many else per_file[0]
 

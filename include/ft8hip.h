@@ -84,10 +84,16 @@ typedef struct ft8_params {
  *   FT8_FLAG_AP        ft8_decode_batch retries every candidate BP failed on with the context's
  *                      a-priori hypotheses (ft8_set_ap; "a-priori decoding" below).  Rescued
  *                      candidates come out in candidate order among the plain decodes, with
- *                      pass_index >> 4 = hypothesis index + 1.  Not with FT8_FLAG_SUBTRACT. */
+ *                      pass_index >> 4 = hypothesis index + 1.  Not with FT8_FLAG_SUBTRACT.
+ *   FT8_FLAG_COHERENT  ft8_decode_batch demodulates the best-scoring candidates BP failed on again, coherently
+ *                      from the samples ("coherent re-demodulation" below; ft8_set_coherent caps them per
+ *                      slot), and decodes the new LLRs.  Rescued candidates come out in candidate order
+ *                      among the plain decodes with pass_index bit 1 set.  F32 and I16 samples only; not
+ *                      with FT8_FLAG_SUBTRACT. */
 #define FT8_FLAG_TOPK 1
 #define FT8_FLAG_SUBTRACT 2
 #define FT8_FLAG_AP 4
+#define FT8_FLAG_COHERENT 8
 
 /* One decoded (or attempted) candidate, 40 bytes, 8-byte aligned. */
 typedef struct ft8_result {
@@ -101,7 +107,8 @@ typedef struct ft8_result {
   uint16_t cand_index;     /* position in the reference candidate order */
   uint8_t payload[10];     /* FT8Message.payload (77 bits, [9] & 0xF8) */
   uint8_t ok;              /* 1: LDPC converged and CRC matched (ft8_decode_candidate True) */
-  uint8_t pass_index;      /* low nibble 0: decoded from the slot; 1: decoded after subtraction (FT8_FLAG_SUBTRACT);
+  uint8_t pass_index;      /* low nibble bit 0: 0 decoded from the slot, 1 decoded after subtraction (FT8_FLAG_SUBTRACT);
+                              bit 1: decoded from the coherent LLRs (FT8_FLAG_COHERENT);
                               high nibble 0: plain BP; h + 1: a-priori hypothesis h (FT8_FLAG_AP, ft8_ap_decode) */
 } ft8_result;
 
@@ -374,6 +381,64 @@ int ft8_set_ap(ft8_ctx* ctx, const ft8_ap_hyp* hyps, int32_t n, int32_t max_hard
 int ft8_ap_decode(ft8_ctx* ctx, const double* d_llr, ft8_result* d_res, int32_t n, int32_t max_iterations,
                   int16_t* d_hard, void* stream);
 
+/* ---- coherent re-demodulation: LLRs of a candidate from the samples ----------------------------------
+ * Build-defined, outside reference parity (the reference forms its LLRs once, from the dB bins of a
+ * one-symbol Hann STFT).  ft8_demodulator_amd/coherent.py: coherent_restate is this contract in NumPy.
+ * Geometry: nsps = nperseg, hop = nsps / steps_per_symbol, Q = the largest divisor of nsps in [8, 32],
+ * D = nsps / Q, tone spacing 6.25 Hz, bin = fs / nfft.  For a candidate (abs_time, abs_freq) of a slot
+ * of real float32 samples x (int16: x / 32767 in float32, as the STFT scales it):
+ *   1. baseband   s0 = (t_lo + abs_time) hop, f0 = (f_lo + abs_freq) bin, fmix = f0 + 3.5 * 6.25,
+ *                 Mt = ceil((hop / 2) / D), Mg = Mt + 1, nb = s0 - Mg D,
+ *                 z[m] = sum_{i < D} x[nb + m D + i] exp(-2 pi i fmix (nb + m D + i) / fs), m in [0, 79 Q + 2 Mg);
+ *                 samples outside [0, n_samples) count as 0.
+ *   2. presence   for a start offset dt in [-Mt, Mt] symbol k's window is z[Mg + dt + k Q + q], q < Q; the
+ *                 symbol is present when all of its Q D input samples lie in [0, n_samples).
+ *   3. sync       on the 21 Costas symbols (3 1 4 0 6 5 2 at symbols 0-6, 36-42, 72-78, tone c_k), offsets
+ *                 dt outer and df_j = (j - 2) bin / 4, j = 0 .. 4, inner, both ascending:
+ *                 metric(dt, j) = sum over the present sync symbols k of
+ *                                 |sum_q w_k[q] exp(-2 pi i (c_k - 3.5 + df_j / 6.25) q / Q)|^2;
+ *                 the first largest metric wins; an interior j is refined by the parabola through its
+ *                 two neighbours in j where their second difference is negative.  No sync symbol
+ *                 present at any dt: status 2.
+ *   4. LLRs       at the winning (dt, df), for each of the 58 data symbols (ft8_extract_likelihood's
+ *                 order) c[t] = sum_q w_k[q] exp(-2 pi i (t - 3.5 + df / 6.25) q / Q), t = 0 .. 7,
+ *                 s[t] = 10 log10(1e-12 + |c[t]|^2), three LLRs by ft8_extract_symbol's Gray map and
+ *                 max-of-4 differences; a symbol that is not present gives three zeros; then
+ *                 ftx_normalize_logl (x *= sqrt(24 / var) over all 174).  A variance of 0 or NaN: status 2.
+ * The device accumulates z, the correlations and |c|^2 in float32 and forms s[t], the LLRs and the
+ * normalisation in double; status 2 and 3 leave 174 zeros. */
+typedef struct ft8_coh_fit {
+  float   dt_s;           /* dt D / fs */
+  float   df_hz;          /* the refined tone-0 offset */
+  float   metric;         /* metric(dt, j) of the winning offsets */
+  uint8_t n_sync;         /* sync symbols present at dt */
+  uint8_t status;         /* 0 valid; 2 nothing to measure (no sync symbol present: zeros elsewhere; or the
+                             variance test of step 4); 3 not attempted (slot index out of range; zeros elsewhere) */
+  int8_t  dt_index;       /* dt, in steps of D samples */
+  uint8_t df_index;       /* j */
+} ft8_coh_fit; /* 16 bytes */
+
+/* The stage call: n candidates d_cand[n][2] = (abs_time, abs_freq) of the slots d_slot_of[n] as one list
+ * -> d_llr_out[n][174] (double) and d_fit_out[n], one 256-thread workgroup per candidate.  Samples and
+ * params as for ft8_stft (p gives the sample rate, the oversampling factors, t_lo and f_lo).
+ * FT8_E_UNSUPPORTED for a dtype other than FT8_F32 / FT8_I16 and for a geometry without Q or whose hop
+ * does not divide nsps (fs = 12006.3); FT8_E_RANGE when nsps / Q twiddles do not fit the kernel's 64 KB
+ * of LDS.  Caller-owned buffers, no context scratch: no part in the cross-stream order. */
+int ft8_coherent_llr(ft8_ctx* ctx, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
+                     int64_t slot_stride, const ft8_params* p, const int32_t* d_cand, const int32_t* d_slot_of,
+                     int32_t n, double* d_llr_out, ft8_coh_fit* d_fit_out, void* stream);
+/* FT8_FLAG_COHERENT inside ft8_decode_batch (a context setting, like ft8_set_ap): after plain BP, per slot
+ * the first max_per_slot candidates with ok == 0 in candidate order (0: every one; the selection of
+ * FT8_FLAG_TOPK is sorted by score, so these are the best-scoring failures) are demodulated as above and
+ * their LLRs decoded by the unchanged BP kernel and tail.  A candidate whose fit has status 0 and whose
+ * attempt the tail accepts gets ok = 1, that attempt's payload, crc_extracted, crc_calculated and
+ * ldpc_errors, and pass_index |= 2; score, slot, abs_time, abs_freq and cand_index do not change, and
+ * every other candidate keeps the record plain BP wrote.  The pass runs before the a-priori pass, which
+ * sees the STFT LLRs of the candidates still failed.  FT8_E_UNSUPPORTED as for the stage call, and
+ * together with FT8_FLAG_SUBTRACT.  Scratch (context-owned, grow-only) per listed candidate: 174 * 8
+ * bytes of LLRs and 76 bytes of lists, fits and records.  max_per_slot < 0: FT8_E_ARG.  Default 0. */
+int ft8_set_coherent(ft8_ctx* ctx, int32_t max_per_slot);
+
 /* Per-slot flags of the last selection (copied device->device into d_out[n_slots]):
  * bit 0: an exact score tie reached a heap comparison (the reference raises TypeError there,
  *        ftx_types.py:37-47; here ties are ordered by scan index), bit 1: unused (0), bit 2
@@ -518,8 +583,8 @@ const char* ft8_build_flags(void);
  * (same buffers, same arguments; every stage is idempotent on its inputs), so a kernel's duration
  * can be measured by wall clock over back-to-back launches, without events between stages.  Valid
  * while the caller's buffers of that call are alive and until any other entry point of this
- * context runs (FT8_E_ARG otherwise, and after an FT8_FLAG_SUBTRACT or FT8_FLAG_AP batch, whose
- * stages are not idempotent).  No reference counterpart. */
+ * context runs (FT8_E_ARG otherwise, and after an FT8_FLAG_SUBTRACT, FT8_FLAG_AP or FT8_FLAG_COHERENT
+ * batch, whose stages are not idempotent).  No reference counterpart. */
 int ft8_replay_stage(ft8_ctx* ctx, int32_t stage, int32_t reps, void* stream);
 
 /* ---- per-stage device timing (HIP events on the caller's stream) --------------------------- */

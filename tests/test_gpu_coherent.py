@@ -1,0 +1,300 @@
+"""Coherent re-demodulation on the device (csrc/coherent.hip: ft8_coherent_llr, ft8_set_coherent,
+FT8_FLAG_COHERENT) against the float64 restatement coherent.coherent_restate, and the whole path against
+a construction from the stage call's own LLRs and the oracle's BP: exact, every field."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import ap_cases as A
+import coherent_cases as C
+
+pytestmark = pytest.mark.gpu
+
+ITERS = C.ITERS
+# max |LLR_device - LLR_restate| over the stage test's candidates, measured once on an MI355X against
+# the float64 restatement: 1.65e-5 (12 kHz float32), 1.86e-5 (int16), 1.11e-5 (10 kHz); the LLRs are scaled
+# to a variance of 24.  The bound is 8 x the largest (float32 summation order varies by a small factor
+# from input to input); 1 % of sqrt(24) would be 4.9e-2.
+LLR_MEASURED = 1.86e-5
+LLR_BOUND = 8 * LLR_MEASURED
+
+
+def _L():
+    from ft8_demodulator_amd import _lib
+    return _lib
+
+
+def _check_stage(name, got, ref, fs, D, binw):
+    from ft8_demodulator_amd import coherent
+    llr, fits = got
+    rllr, rfits, grids = ref
+    assert np.array_equal(fits["status"], rfits["status"])
+    assert np.array_equal(fits["n_sync"], rfits["n_sync"])
+    measured = fits["status"] == 0
+    tie = np.array([g is not None and coherent.near_tie(g) for g in grids])
+    cmp_ = measured & ~tie
+    assert int((measured & tie).sum()) * 20 <= int(measured.sum())
+    assert np.array_equal(fits["dt_index"][cmp_], rfits["dt_index"][cmp_])
+    assert np.array_equal(fits["df_index"][cmp_], rfits["df_index"][cmp_])
+    assert np.abs(fits["df_hz"][cmp_].astype(np.float64) - rfits["df_hz"][cmp_]).max() <= 0.01
+    assert np.array_equal(fits["dt_s"][cmp_], (rfits["dt_index"][cmp_] * (D / fs)).astype(np.float32))
+    assert np.allclose(fits["metric"][cmp_], rfits["metric"][cmp_], rtol=1e-4)
+    # status 2 / 3: zeros
+    assert (llr[~measured] == 0.0).all()
+    err = float(np.abs(llr[cmp_] - rllr[cmp_]).max())
+    print(f"{name}: {int(cmp_.sum())} candidates compared, {int((measured & tie).sum())} near ties left out, "
+          f"max |LLR_device - LLR_restate| = {err:.3e} (bound {LLR_BOUND:.3e})")
+    assert err <= LLR_BOUND
+
+
+@pytest.mark.parametrize("key", ["f32", "i16"])
+def test_stage_equals_restatement_12k(gpu, key):
+    """3 slots at 12 kHz, 85 candidates: the 3 x 3 grid points around 9 signals (three of them running past
+    the slot's end), two candidates whose window starts before the slot and two past its end."""
+    from ft8_demodulator_amd.ldpc_decoder import coherent_llr_batch
+    c = C.stage_case_12k()
+    x = np.array(c["x"] if key == "f32" else c["pcm"])
+    got = coherent_llr_batch(x, c["cand"], c["slot_of"], C.FS, 2, 2)
+    assert (c[key][1]["status"] == 2).any() and ((c[key][1]["n_sync"] % 21) != 0).any()
+    _check_stage(key, got, c[key], C.FS, C.NSPS // 32, C.BIN)
+
+
+def test_stage_equals_restatement_10k(gpu):
+    """fs = 10000 at 4 bins per tone and 4 steps per symbol: nsps 1600, D 50 (no float4 path), Mt 4."""
+    from ft8_demodulator_amd.ldpc_decoder import coherent_llr_batch
+    c = C.stage_case_10k()
+    got = coherent_llr_batch(np.array(c["x"]), c["cand"], c["slot_of"], C.FS10, C.BPT10, C.SPS10)
+    _check_stage("10k", got, c["f32"], C.FS10, C.NSPS10 // 32, C.FS10 / C.NFFT10)
+
+
+def test_stage_slot_out_of_range_and_empty(gpu):
+    from ft8_demodulator_amd.ldpc_decoder import coherent_llr_batch
+    c = C.stage_case_12k()
+    llr, fits = coherent_llr_batch(np.array(c["x"]), c["cand"][:3], [0, 3, -1], C.FS)
+    assert fits["status"].tolist() == [0, 3, 3] and (llr[1:] == 0.0).all() and llr[0].any()
+    llr, fits = coherent_llr_batch(np.array(c["x"]), np.zeros((0, 2), np.int32), [], C.FS)
+    assert llr.shape == (0, 174) and len(fits) == 0
+
+
+# ---- FT8_FLAG_COHERENT inside ft8_decode_batch -----------------------------------------------------------
+E2E = dict(max_candidates=20, min_score=2)
+CAP = 4
+AP = ["CQ ? ?"]
+
+
+def _decoder(**kw):
+    from ft8_demodulator_amd._pipeline import SlotDecoder
+    return SlotDecoder(C.FS, max_iterations=ITERS, flags=_L().FT8_FLAG_TOPK, **E2E, **kw)
+
+
+@pytest.fixture(scope="module")
+def e2e(gpu, oracle):
+    """The expectation, from the device's own stage calls: ft8_stft, ft8_sync_select and ft8_llr give every
+    candidate's STFT LLRs, the oracle's BP the plain records; each slot's first CAP failed candidates
+    get the stage call's coherent LLRs, decoded by the oracle again.  -> all records after the coherent
+    pass, after coherent + AP, and the plain ones (read-only)."""
+    from ft8_demodulator_amd import ap
+    from ft8_demodulator_amd._pipeline import make_params, make_plan
+    from ft8_demodulator_amd.ldpc_decoder import coherent_llr_batch
+    _lib, torch = _L(), gpu
+    x = np.array(C.stage_case_12k()["x"])
+    n_slots, n = x.shape
+    ctx = _lib.Context(0)
+    L, st = _lib.lib(), _lib.stream_handle(0)
+    plan = make_plan(n, C.FS)
+    N = E2E["max_candidates"]
+    p = make_params(plan, N, E2E["min_score"], ITERS, _lib.FT8_FLAG_TOPK)
+    d_x = torch.from_numpy(x).cuda()
+    T, F = plan.T, plan.F
+    d_wf = torch.empty(n_slots, T, F, dtype=torch.float32, device="cuda")
+    ctx.check(L.ft8_stft(ctx.handle, _lib.ptr(d_x), _lib.FT8_F32, n, n_slots, n, ctypes.byref(p), _lib.ptr(d_wf), st),
+              "ft8_stft")
+    d_cand = torch.zeros(n_slots, N, 2, dtype=torch.int32, device="cuda")
+    d_score = torch.zeros(n_slots, N, dtype=torch.float64, device="cuda")
+    d_cnt = torch.zeros(n_slots, dtype=torch.int32, device="cuda")
+    ctx.check(L.ft8_sync_select(ctx.handle, _lib.ptr(d_wf), 0, n_slots, T, F, ctypes.byref(p), _lib.ptr(d_cand),
+                                _lib.ptr(d_score), _lib.ptr(d_cnt), None, st), "ft8_sync_select")
+    cand, score, cnt = d_cand.cpu().numpy(), d_score.cpu().numpy(), d_cnt.cpu().numpy()
+    rows = [(s, int(cand[s, i, 0]), int(cand[s, i, 1])) for s in range(n_slots) for i in range(int(cnt[s]))]
+    d_c3 = torch.tensor(rows, dtype=torch.int32, device="cuda")
+    d_llr = torch.empty(len(rows), 174, dtype=torch.float64, device="cuda")
+    ctx.check(L.ft8_llr(ctx.handle, _lib.ptr(d_wf), 0, T, F, 2, 2, _lib.ptr(d_c3), len(rows), 1, _lib.ptr(d_llr), st),
+              "ft8_llr")
+    llr = d_llr.cpu().numpy()
+    rec0 = A.plain_records(llr)
+    k = 0
+    for s in range(n_slots):
+        for i in range(int(cnt[s])):
+            rec0["score"][k], rec0["slot"][k], rec0["cand_index"][k] = score[s, i], s, i
+            rec0["abs_time"][k], rec0["abs_freq"][k] = cand[s, i]
+            k += 1
+    # each slot's first CAP failed candidates, in candidate order
+    listed = [i for s in range(n_slots) for i in np.nonzero((rec0["slot"] == s) & (rec0["ok"] == 0))[0][:CAP]]
+    cl, cf = coherent_llr_batch(x, [(rows[i][1], rows[i][2]) for i in listed], [rows[i][0] for i in listed], C.FS)
+    coh = np.array(rec0, copy=True)
+    for i, v, f in zip(listed, cl, cf):
+        ok, pay, ce, cc, err = C.decode_llr(oracle, v)
+        if ok and f["status"] == 0:
+            coh["ok"][i], coh["pass_index"][i] = 1, 2
+            coh["payload"][i] = np.frombuffer(pay, dtype=np.uint8)
+            coh["crc_extracted"][i], coh["crc_calculated"][i], coh["ldpc_errors"][i] = ce, cc, err
+    both, _ = A.restate(llr, coh, [ap.ap_hypothesis(t) for t in AP], ap.DEFAULT_MAX_HARD_ERRORS)
+    for a in (rec0, coh, both):
+        a.setflags(write=False)
+    return {"x": x, "plain": rec0, "coherent": coh, "both": both, "listed": listed}
+
+
+def _per_slot(rec, s):
+    return rec[(rec["slot"] == s) & (rec["ok"] == 1)]
+
+
+def test_e2e_expectation_shows_every_outcome(e2e):
+    """What the slots were built for, on the expectation alone: plain decodes, rescues, listed candidates
+    that stay failed, and failed candidates beyond the cap."""
+    plain, coh = e2e["plain"], e2e["coherent"]
+    sent = set(C.stage_case_12k()["payloads"])
+    assert int(plain["ok"].sum()) >= 3
+    rescued = coh[coh["pass_index"] == 2]
+    assert len(rescued) >= 2 and all(bytes(r["payload"]) in sent for r in rescued)
+    assert len(e2e["listed"]) == 3 * CAP and len(rescued) < len(e2e["listed"])
+    assert int((plain["ok"] == 0).sum()) > len(e2e["listed"])
+
+
+def test_e2e_records_equal_construction(gpu, e2e):
+    x = gpu.from_numpy(e2e["x"]).cuda()
+    got = _decoder(coherent=CAP).records(x)
+    plain = _decoder().records(x)
+    assert len(got) == len(plain) == 3
+    for s in range(3):
+        A.records_equal(got[s], _per_slot(e2e["coherent"], s))
+        A.records_equal(plain[s], _per_slot(e2e["plain"], s))      # the unflagged decoder: today's path
+        assert (plain[s]["pass_index"] == 0).all()
+
+
+def test_e2e_with_ap(gpu, e2e):
+    """The a-priori pass that follows sees the STFT LLRs of the candidates still failed; rescued records
+    carry no AP index."""
+    from ft8_demodulator_amd import ap, coherent
+    x = gpu.from_numpy(e2e["x"]).cuda()
+    got = _decoder(coherent=CAP, ap=AP).records(x)
+    for s in range(3):
+        A.records_equal(got[s], _per_slot(e2e["both"], s))
+        assert all(ap.ap_index(r) == 0 for r in got[s] if coherent.coherent_index(r))
+
+
+def test_e2e_pipelined_chunks_and_int16(gpu, e2e):
+    """One slot per chunk over two internal streams gives the single chain's records; int16 PCM of the
+    same slots decodes the same payloads at the same candidates."""
+    x = gpu.from_numpy(e2e["x"]).cuda()
+    dec = _decoder(coherent=CAP, context=_L().Context(0))
+    dec.ctx.set_pipeline(1, 2, 4)
+    got = dec.records(x)
+    for s in range(3):
+        A.records_equal(got[s], _per_slot(e2e["coherent"], s))
+    pcm = gpu.from_numpy(np.array(C.stage_case_12k()["pcm"])).cuda()
+    got16 = _decoder(coherent=CAP).records(pcm, code=_L().FT8_I16)
+    assert sum(int((r["pass_index"] == 2).sum()) for r in got16) >= 2
+
+
+def test_gain_on_the_device(gpu):
+    """The 16 slots at -22 dB of the CPU test: with the flag at least 12 transmitted payloads, nothing
+    that was not transmitted; without it none."""
+    x, pays, _ = C.weak_slots()
+    d_x = gpu.from_numpy(np.array(x)).cuda()
+    got = _decoder(coherent=True).records(d_x)
+    found = 0
+    for s, r in enumerate(got):
+        dec = {bytes(v["payload"]) for v in r}
+        assert dec <= {pays[s]}, (s, "a payload that was not transmitted")
+        found += pays[s] in dec
+    print("coherent decodes", found, "of", C.N_WEAK)
+    assert found >= 12
+    assert sum(len(r) for r in _decoder().records(d_x)) == 0
+
+
+def test_messages_reports_and_pack_take_rescued_records(gpu):
+    """ft8_unpack77, ft8_snr_last and ft8_pack_decodes run on a coherent batch unchanged: four weak slots'
+    rescued rows carry a text, a finite report near the transmitted SNR (-18.2 dB in 2500 Hz), and are
+    packed with their pass_index."""
+    from ft8_demodulator_amd import coherent, message
+    _lib = _L()
+    x, pays, _ = C.weak_slots()
+    d_x = gpu.from_numpy(np.array(x[:4])).cuda()
+    dec = _decoder(coherent=True)
+    recs, texts, reps = dec._fetch(d_x, text=True, snr=True)
+    n = 0
+    for s in range(4):
+        want = message.unpack77([pays[s]])[0]
+        for rec, t, r in zip(recs[s], texts[s], reps[s]):
+            assert coherent.coherent_index(rec) == 1 and bytes(rec["payload"]) == pays[s]
+            assert t["status"] == want["status"] and t["text"] == want["text"]
+            assert r["status"] in (0, 1) and -24.0 < r["snr_db"] < -12.0
+            n += 1
+    assert n >= 3
+    out, counts = dec.run(d_x)
+    nbytes = int(_lib.lib().ft8_pack_bytes(4, 16))
+    send = gpu.zeros(nbytes, dtype=gpu.uint8, device="cuda")
+    dec.ctx.check(_lib.lib().ft8_pack_decodes(dec.ctx.handle, _lib.ptr(out), _lib.ptr(counts), 4, dec.cap, 16, 0,
+                                              _lib.ptr(send), None, _lib.stream_handle(0)), "ft8_pack_decodes")
+    raw = send.cpu().numpy()
+    total = int(raw[:8].view(np.int64)[0])
+    packed = raw[nbytes - 16 * 40:].view(_lib.RESULT_DTYPE)[:total]
+    assert total == int(counts.sum()) >= 3 and (packed["pass_index"] == 2).all() and (packed["ok"] == 1).all()
+
+
+def test_errors_and_abi(gpu):
+    _lib = _L()
+    from ft8_demodulator_amd.ldpc_decoder import coherent_llr_batch
+    assert _lib.lib().ft8_abi_version() == 2
+    assert _lib.FT8_FLAG_COHERENT == 8
+    x = np.array(C.stage_case_12k()["x"][:1, :40000])
+    cand, so = [(4, 400)], [0]
+    for bad in (x.astype(np.float64), x.astype(np.complex64), x.astype(np.complex128)):
+        with pytest.raises(NotImplementedError, match="float32 or int16"):
+            coherent_llr_batch(bad, cand, so, C.FS)
+    with pytest.raises(NotImplementedError, match="hop"):
+        coherent_llr_batch(x, cand, so, 12006.3)
+    d_x = gpu.from_numpy(x).cuda()
+    from ft8_demodulator_amd._pipeline import SlotDecoder
+    with pytest.raises(NotImplementedError, match="FT8_FLAG_SUBTRACT"):
+        SlotDecoder(C.FS, flags=_lib.FT8_FLAG_TOPK | _lib.FT8_FLAG_SUBTRACT, coherent=4, **E2E).records(d_x)
+    with pytest.raises(NotImplementedError, match="hop"):
+        SlotDecoder(12006.3, flags=_lib.FT8_FLAG_TOPK, coherent=4, **E2E).records(d_x)
+    with pytest.raises(NotImplementedError, match="float32 or int16"):
+        SlotDecoder(C.FS, flags=_lib.FT8_FLAG_TOPK, coherent=4, **E2E).records(d_x.to(gpu.float64))
+    with pytest.raises(ValueError):
+        SlotDecoder(C.FS, coherent=-1)
+    ctx = _lib.Context(0)
+    assert _lib.lib().ft8_set_coherent(ctx.handle, -1) == _lib.FT8_E_ARG
+    # a coherent batch cannot be replayed
+    dec = _decoder(coherent=CAP, context=ctx)
+    dec.records(d_x)
+    with pytest.raises(ValueError):
+        ctx.replay("bp")
+
+
+def test_from_wave_marks_coherent_decodes(gpu, tmp_path, capsys):
+    """from_wave --coherent on a weak slot as 16-bit PCM: the decode's block carries a `Coherent:` line with
+    the fit's offsets; without the flag the file decodes nothing."""
+    import wave
+    from ft8_demodulator_amd import from_wave
+    x, pays, _ = C.weak_slots()
+    pcm = np.clip(np.round(x[0] / 8.0 * 32767.0), -32767, 32767).astype(np.int16)
+    path = str(tmp_path / "weak.wav")
+    with wave.open(path, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(C.FS)
+        w.writeframes(pcm.tobytes())
+    opts = ["--max-candidates", "20", "--min-score", "5"]
+    res = from_wave.main([path, "--coherent"] + opts)
+    out = capsys.readouterr().out
+    assert [bytes(r[0].payload) for r in res] == [pays[0]] * len(res) and len(res) >= 1
+    assert out.count("Coherent: dt ") == len(res) and " ms, df " in out
+    res = from_wave.main([path] + opts)
+    out = capsys.readouterr().out
+    assert res == [] and "Coherent:" not in out
+    res = from_wave.main([path, "--coherent", "1"] + opts)
+    assert len(res) <= 1
+    capsys.readouterr()
