@@ -109,14 +109,51 @@ hipError_t lds_opt_in(const void* kernel, size_t dyn_bytes) {
 }
 }  // namespace ft8
 
+namespace {
+int ensure(ft8_ctx* c, DevBuf& b, size_t bytes);  // grow-only scratch, below
+}
+// The buffers the two retry passes of ft8_decode_batch have in common (RetryLists, ft8_internal.h): the
+// lists and, per list position, the LLRs k_bp decodes and the records it writes.  ensure: n_slots
+// lists of M positions; at: the scratch of the chunk that starts at slot `slot0`, with the chunk's
+// records and candidates (`in`: everything but M and the list arrays).
+struct RetryView {
+  RetryLists lists;
+  double* llr;
+  ft8_result* res;
+};
+struct RetryScratch {
+  DevBuf list, count, cand, score, llr, res;
+  int M = 0;
+  int ensure(ft8_ctx* c, size_t n_slots, int M_) {
+    const size_t n = n_slots * (size_t)M_;
+    M = M_;
+    int rc;
+    if ((rc = ::ensure(c, list, sizeof(int32_t) * n))) return rc;
+    if ((rc = ::ensure(c, count, sizeof(int32_t) * n_slots))) return rc;
+    if ((rc = ::ensure(c, cand, sizeof(int32_t) * 2 * n))) return rc;
+    if ((rc = ::ensure(c, score, sizeof(double) * n))) return rc;
+    if ((rc = ::ensure(c, llr, sizeof(double) * FT8_LDPC_N * n))) return rc;
+    return ::ensure(c, res, sizeof(ft8_result) * n);
+  }
+  RetryView at(RetryLists in, int slot0) const {
+    const size_t r0 = (size_t)slot0 * M;
+    in.M = M;
+    in.list = list.as<int32_t>() + r0;
+    in.count = count.as<int32_t>() + slot0;
+    in.cand = cand.as<int32_t>() + 2 * r0;
+    in.score = score.as<double>() + r0;
+    return {in, llr.as<double>() + (size_t)FT8_LDPC_N * r0, res.as<ft8_result>() + r0};
+  }
+};
+
 struct ft8_ctx {
   int device = 0;
   std::string err;
   std::vector<PlanEntry> plans;
   std::vector<WinEntry> wins;
   DevBuf wf, scores, smask, cand, cand_score, cand_count, warn, rowsum, res_all, work, stats, llr, tie;
-  // first ticket of the next k_bp launch per claim counter in `work` (8 B each: [0] ft8_bp's, [1 + k]
-  // decode chunk k's); reset with the buffer, which is zeroed whenever it is (re)allocated
+  // first ticket of the next k_bp launch per claim counter in `work` (8 B each, indexed by
+  // bp_counter); reset with the buffer, which is zeroed whenever it is (re)allocated
   std::vector<unsigned long long> work_base;
   // FT8_FLAG_SUBTRACT: residual samples, per-record fits, pass-1 / pass-2 records
   DevBuf residual, sub_est, sub_list, out1, counts1, out2, counts2;
@@ -157,14 +194,16 @@ struct ft8_ctx {
   } snr_batch{};
   DevBuf snr_A, snr_N0;
   // a-priori decoding (ft8_set_ap): the hypotheses, the hard-error limit, and the AP pass's scratch
-  // (ApLaunch), sized for the records of one ft8_decode_batch / ft8_ap_decode
+  // (lists of N; amax and plain per record), sized for one ft8_decode_batch / ft8_ap_decode
   std::vector<ft8_ap_hyp> ap_hyps;
   int ap_max_hard = FT8_LDPC_N;
-  DevBuf ap_amax, ap_list, ap_count, ap_cand, ap_score, ap_llr, ap_plain, ap_res;
+  RetryScratch ap;
+  DevBuf ap_amax, ap_plain;
   // coherent re-demodulation (ft8_set_coherent): the per-slot cap (0: every failed candidate) and the
-  // pass's scratch (CohPass, CohLaunch), sized for the lists of one ft8_decode_batch
+  // pass's scratch (lists of the cap; a fit per position), sized for one ft8_decode_batch
   int coh_max = 0;
-  DevBuf coh_list, coh_count, coh_cand, coh_score, coh_llr, coh_fit, coh_res;
+  RetryScratch coh;
+  DevBuf coh_fit;
   // the stream of the last entry point that enqueued work, and an event recorded on it after that
   // work (StreamOrder): a call on another stream first waits for it
   hipStream_t last_stream = nullptr;
@@ -238,6 +277,16 @@ int ensure_work(ft8_ctx* c, int n_counters, hipStream_t s) {
   if (rc) return rc;
   if (fresh) c->work_base.assign(c->work.cap / sizeof(unsigned long long), 0ull);
   return FT8_OK;
+}
+
+// Claim counter indices: [0] belongs to ft8_bp / ft8_ap_decode (a caller stream, in order); a batch of
+// n_chunks chunks then holds one per chunk for plain BP, for the a-priori pass and for the coherent
+// pass, in that order, so that chunks on different streams never share one.
+enum BpUser { kCallerBp = -1, kChunkBp = 0, kChunkAp = 1, kChunkCoherent = 2 };
+int bp_counter(BpUser u, int k, int n_chunks) { return u == kCallerBp ? 0 : 1 + (int)u * n_chunks + k; }
+// counters of a batch: through its last user's
+int bp_counters(bool ap, bool coh, int n_chunks) {
+  return bp_counter(coh ? kChunkCoherent : ap ? kChunkAp : kChunkBp, n_chunks - 1, n_chunks) + 1;
 }
 
 hipEvent_t get_event(ft8_ctx* c) {
@@ -742,10 +791,35 @@ int subtract_core(ft8_ctx* c, const void* x, int dtype, float* resid, int64_t n_
                   const int32_t* counts, int cap, hipStream_t s);
 int gfsk_tables(ft8_ctx* c, int nsps);
 
-// k_bp's work counters, and its clock counters while timing is on (ft8_set_timing allocates them)
-void wire_bp_stats(const ft8_ctx* c, BpLaunch& B) {
+// the counter half of a k_bp launch: claim counter `counter` (ensure_work) and its host ticket base,
+// the work counters, the clock counters while timing is on (ft8_set_timing allocates them), and the
+// persistent grid's resident waves per SIMD (kernel maximum 4)
+void wire_bp_counters(ft8_ctx* c, BpLaunch& B, int counter, int grid_waves) {
+  B.work = c->work.as<unsigned long long>() + counter;
+  B.work_base = &c->work_base[counter];
   B.stats = c->stats.as<unsigned long long>();
   B.clock = c->timing && c->stats.p ? B.stats + 4 : nullptr;
+  B.grid_waves = grid_waves;
+}
+
+// k_bp in mode 0 over a retry pass's compacted lists: llr_in / plain_out (nullable) / res_out per
+// list position
+hipError_t bp_over_lists(ft8_ctx* c, const RetryLists& l, const double* llr_in, uint8_t* plain_out,
+                         ft8_result* res_out, int max_iterations, int counter, hipStream_t s) {
+  BpLaunch B{};
+  B.cand = l.cand;
+  B.cand_score = l.score;
+  B.cand_count = l.count;
+  B.N = l.M;
+  B.n_slots = l.n_slots;
+  B.n_items = l.n_slots * l.M;
+  B.mode = 0;
+  B.max_iterations = max_iterations;
+  B.llr_in = llr_in;
+  B.plain_out = plain_out;
+  B.res = res_out;
+  wire_bp_counters(c, B, counter, c->bp_waves);
+  return launch_bp(B, s);
 }
 
 // score + select on the scratch `sc`; compact: the score kernel may write only the passing scores
@@ -812,68 +886,42 @@ int do_sync_select(ft8_ctx* c, const void* d_wf, int wf_f64, int n_slots, int T,
 }
 
 // ---- a-priori decoding ---------------------------------------------------------------------------
-// the AP pass's scratch for n_records records in n_slots lists (ft8hip.h states the sizes)
-int ensure_ap_scratch(ft8_ctx* c, size_t n_slots, size_t n_records) {
+// the AP pass's scratch for n_slots lists of N records (ft8hip.h states the sizes)
+int ensure_ap_scratch(ft8_ctx* c, size_t n_slots, int N) {
   int rc;
-  if ((rc = ensure(c, c->ap_amax, sizeof(double) * n_records))) return rc;
-  if ((rc = ensure(c, c->ap_list, sizeof(int32_t) * n_records))) return rc;
-  if ((rc = ensure(c, c->ap_count, sizeof(int32_t) * n_slots))) return rc;
-  if ((rc = ensure(c, c->ap_cand, sizeof(int32_t) * 2 * n_records))) return rc;
-  if ((rc = ensure(c, c->ap_score, sizeof(double) * n_records))) return rc;
-  if ((rc = ensure(c, c->ap_llr, sizeof(double) * FT8_LDPC_N * n_records))) return rc;
-  if ((rc = ensure(c, c->ap_plain, (size_t)FT8_LDPC_N * n_records))) return rc;
-  return ensure(c, c->ap_res, sizeof(ft8_result) * n_records);
+  if ((rc = c->ap.ensure(c, n_slots, N))) return rc;
+  if ((rc = ensure(c, c->ap_amax, sizeof(double) * n_slots * N))) return rc;
+  return ensure(c, c->ap_plain, (size_t)FT8_LDPC_N * n_slots * N);
 }
 
-// The AP pass over res[n_slots][N] and llr[n_slots][N][174], the context's hypotheses one after
-// another (ap.hip).  The pass's scratch starts at slot `slot0` of the buffers ensure_ap_scratch sized
-// (record slot0 * N), so the chunks of a pipelined batch do not share any; `counter` is the k_bp claim
-// counter the pass's launches draw their tickets from.
-int ap_pass(ft8_ctx* c, const double* llr, ft8_result* res, const int32_t* cand_count, const int32_t* cand_in,
-            const double* score_in, int n_slots, int N, int slot0, int max_iterations, int16_t* hard, int counter,
-            hipStream_t s) {
-  const size_t r0 = (size_t)slot0 * N;
+// The AP pass over the records `failed` describes (everything but M, gate and the list arrays) and
+// llr[n_slots][N][174], the context's hypotheses one after another (ap.hip).  The pass's scratch starts
+// at slot `slot0` of the buffers ensure_ap_scratch sized, so the chunks of a pipelined batch do not
+// share any; `counter` is the k_bp claim counter the pass's launches draw their tickets from.
+int ap_pass(ft8_ctx* c, const RetryLists& failed, const double* llr, int slot0, int max_iterations, int16_t* hard,
+            int counter, hipStream_t s) {
+  const RetryView v = c->ap.at(failed, slot0);
+  const size_t r0 = (size_t)slot0 * failed.N;
+  uint8_t* plain = c->ap_plain.as<uint8_t>() + (size_t)FT8_LDPC_N * r0;
   ApLaunch A{};
-  A.llr = llr;
-  A.res = res;
-  A.cand_count = cand_count;
-  A.cand_in = cand_in;
-  A.score_in = score_in;
-  A.n_slots = n_slots;
-  A.N = N;
-  A.max_hard = c->ap_max_hard;
+  A.r = v.lists;
   A.amax = c->ap_amax.as<double>() + r0;
-  A.list = c->ap_list.as<int32_t>() + r0;
-  A.count = c->ap_count.as<int32_t>() + slot0;
-  A.cand = c->ap_cand.as<int32_t>() + 2 * r0;
-  A.score = c->ap_score.as<double>() + r0;
-  A.llr_h = c->ap_llr.as<double>() + (size_t)FT8_LDPC_N * r0;
-  A.plain = c->ap_plain.as<uint8_t>() + (size_t)FT8_LDPC_N * r0;
-  A.res_h = c->ap_res.as<ft8_result>() + r0;
+  A.r.gate = A.amax;
+  A.llr = llr;
+  A.max_hard = c->ap_max_hard;
+  A.llr_h = v.llr;
+  A.plain = plain;
+  A.res_h = v.res;
   A.hard = hard;
   hipError_t e = launch_ap_amax(A, s);
   if (e != hipSuccess) return hipfail(c, e, "ap launch");
-  BpLaunch B{};
-  B.cand = A.cand;
-  B.cand_score = A.score;
-  B.cand_count = A.count;
-  B.N = N;
-  B.n_slots = n_slots;
-  B.n_items = n_slots * N;
-  B.mode = 0;
-  B.max_iterations = max_iterations;
-  B.llr_in = A.llr_h;
-  B.plain_out = const_cast<uint8_t*>(A.plain);  // k_bp writes what k_ap_merge reads
-  B.res = const_cast<ft8_result*>(A.res_h);
-  B.work = c->work.as<unsigned long long>() + counter;
-  B.work_base = &c->work_base[counter];
-  wire_bp_stats(c, B);
-  B.grid_waves = c->bp_waves;
   for (size_t h = 0; h < c->ap_hyps.size(); ++h) {
     A.hyp = c->ap_hyps[h];
     A.h = (int)h;
-    if ((e = launch_ap_prepare(A, s)) != hipSuccess) return hipfail(c, e, "ap launch");
-    if ((e = launch_bp(B, s)) != hipSuccess) return hipfail(c, e, "ap bp launch");
+    if ((e = launch_retry_list(A.r, s)) != hipSuccess) return hipfail(c, e, "ap launch");
+    if ((e = launch_ap_clamp(A, s)) != hipSuccess) return hipfail(c, e, "ap launch");
+    if ((e = bp_over_lists(c, A.r, v.llr, plain, v.res, max_iterations, counter, s)) != hipSuccess)
+      return hipfail(c, e, "ap bp launch");
     if ((e = launch_ap_merge(A, s)) != hipSuccess) return hipfail(c, e, "ap launch");
   }
   return FT8_OK;
@@ -917,67 +965,33 @@ int coherent_setup(ft8_ctx* c, const void* x, int dtype, int64_t n_samples, int 
 int coherent_cap(const ft8_ctx* c, int N) { return c->coh_max > 0 ? std::min(c->coh_max, N) : N; }
 
 // the coherent pass's scratch for n_slots lists of M candidates (ft8hip.h states the sizes)
-int ensure_coh_scratch(ft8_ctx* c, size_t n_slots, size_t M) {
-  const size_t n = n_slots * M;
-  int rc;
-  if ((rc = ensure(c, c->coh_list, sizeof(int32_t) * n))) return rc;
-  if ((rc = ensure(c, c->coh_count, sizeof(int32_t) * n_slots))) return rc;
-  if ((rc = ensure(c, c->coh_cand, sizeof(int32_t) * 2 * n))) return rc;
-  if ((rc = ensure(c, c->coh_score, sizeof(double) * n))) return rc;
-  if ((rc = ensure(c, c->coh_llr, sizeof(double) * FT8_LDPC_N * n))) return rc;
-  if ((rc = ensure(c, c->coh_fit, sizeof(ft8_coh_fit) * n))) return rc;
-  return ensure(c, c->coh_res, sizeof(ft8_result) * n);
+int ensure_coh_scratch(ft8_ctx* c, size_t n_slots, int M) {
+  int rc = c->coh.ensure(c, n_slots, M);
+  return rc ? rc : ensure(c, c->coh_fit, sizeof(ft8_coh_fit) * n_slots * M);
 }
 
-// The coherent pass over res[n_slots][N] of one chunk (coherent.hip): list, k_coherent, k_bp over the
-// lists, merge.  Like ap_pass, its scratch starts at slot `slot0` of the buffers ensure_coh_scratch sized
-// and `counter` is the k_bp claim counter its launch draws its tickets from.  L: coherent_setup's
-// launch for the chunk's samples.
-int coherent_pass(ft8_ctx* c, CohLaunch L, ft8_result* res, const int32_t* cand_count, const int32_t* cand_in,
-                  const double* score_in, int n_slots, int N, int slot0, int max_iterations, int counter,
+// The coherent pass over the records `failed` describes, one chunk's (coherent.hip): list, k_coherent,
+// k_bp over the lists, merge.  Like ap_pass, its scratch starts at slot `slot0` of the buffers
+// ensure_coh_scratch sized and `counter` is the k_bp claim counter its launch draws its tickets from.
+// L: coherent_setup's launch for the chunk's samples.
+int coherent_pass(ft8_ctx* c, CohLaunch L, const RetryLists& failed, int slot0, int max_iterations, int counter,
                   hipStream_t s) {
-  const int M = coherent_cap(c, N);
-  const size_t r0 = (size_t)slot0 * M;
-  CohPass A{};
-  A.res = res;
-  A.cand_count = cand_count;
-  A.cand_in = cand_in;
-  A.score_in = score_in;
-  A.n_slots = n_slots;
-  A.N = N;
-  A.M = M;
-  A.list = c->coh_list.as<int32_t>() + r0;
-  A.count = c->coh_count.as<int32_t>() + slot0;
-  A.cand = c->coh_cand.as<int32_t>() + 2 * r0;
-  A.score = c->coh_score.as<double>() + r0;
-  A.fit = c->coh_fit.as<ft8_coh_fit>() + r0;
-  A.res_c = c->coh_res.as<ft8_result>() + r0;
-  hipError_t e = launch_coh_list(A, s);
+  const RetryView v = c->coh.at(failed, slot0);
+  const RetryLists& l = v.lists;
+  ft8_coh_fit* fit = c->coh_fit.as<ft8_coh_fit>() + (size_t)slot0 * l.M;
+  hipError_t e = launch_retry_list(l, s);
   if (e != hipSuccess) return hipfail(c, e, "coherent launch");
-  L.cand = A.cand;
+  L.cand = l.cand;
   L.slot_of = nullptr;
-  L.count = A.count;
-  L.n = n_slots * M;
-  L.M = M;
-  L.llr = c->coh_llr.as<double>() + (size_t)FT8_LDPC_N * r0;
-  L.fit = const_cast<ft8_coh_fit*>(A.fit);  // k_coherent writes what k_coh_merge reads
+  L.count = l.count;
+  L.n = l.n_slots * l.M;
+  L.M = l.M;
+  L.llr = v.llr;
+  L.fit = fit;
   if ((e = launch_coherent(L, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
-  BpLaunch B{};
-  B.cand = A.cand;
-  B.cand_score = A.score;
-  B.cand_count = A.count;
-  B.N = M;
-  B.n_slots = n_slots;
-  B.n_items = n_slots * M;
-  B.mode = 0;
-  B.max_iterations = max_iterations;
-  B.llr_in = L.llr;
-  B.res = const_cast<ft8_result*>(A.res_c);
-  B.work = c->work.as<unsigned long long>() + counter;
-  B.work_base = &c->work_base[counter];
-  wire_bp_stats(c, B);
-  B.grid_waves = c->bp_waves;
-  if ((e = launch_bp(B, s)) != hipSuccess) return hipfail(c, e, "coherent bp launch");
+  if ((e = bp_over_lists(c, l, v.llr, nullptr, v.res, max_iterations, counter, s)) != hipSuccess)
+    return hipfail(c, e, "coherent bp launch");
+  const CohPass A{l, fit, v.res};
   if ((e = launch_coh_merge(A, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
   return FT8_OK;
 }
@@ -998,11 +1012,9 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
   const int csz = (c->n_streams > 0 && c->chunk_slots > 0) ? c->chunk_slots : n_slots;
   const int n_chunks = (n_slots + csz - 1) / csz;
   const int n_str = (c->n_streams > 0 && n_chunks > 1) ? std::min(c->n_streams, n_chunks) : 0;
-  // k_bp claim counters: [0] belongs to ft8_bp / ft8_ap_decode (a caller stream), [1 + k] to chunk k,
-  // [1 + n_chunks + k] to chunk k's a-priori pass, [1 + 2 n_chunks + k] to its coherent pass
   const bool ap = (p->flags & FT8_FLAG_AP) != 0;
   const bool coh = (p->flags & FT8_FLAG_COHERENT) != 0;
-  if ((rc = ensure_work(c, (coh ? 3 : ap ? 2 : 1) * n_chunks + 1, s))) return rc;
+  if ((rc = ensure_work(c, bp_counters(ap, coh, n_chunks), s))) return rc;
   hipError_t e = hipSuccess;
   if (n_str > 0) {
     while ((int)c->streams.size() < n_str) {
@@ -1053,25 +1065,27 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     B.llr_out = c->llr.as<double>() + (size_t)FT8_LDPC_N * c0 * N;
     B.llr_in = B.llr_out;
     B.res = c->res_all.as<ft8_result>() + (size_t)c0 * N;
-    B.work = c->work.as<unsigned long long>() + 1 + k;
-    B.work_base = &c->work_base[1 + k];
-    wire_bp_stats(c, B);
-    B.grid_waves = c->bp_waves;  // resident waves per SIMD of the persistent grid (kernel maximum 4)
+    wire_bp_counters(c, B, bp_counter(kChunkBp, k, n_chunks), c->bp_waves);
     B.tie = sc.tie;
     B.warn = sc.warn;
     if ((rc = timed_launch(c, kLlr, cs, "llr launch", [&] { return launch_llr(B, cs); }))) return rc;
     if ((rc = timed_launch(c, kBp, cs, "bp launch", [&] { return launch_bp(B, cs); }))) return rc;
     // the tie order k_compact applies permutes positions, not records, so the coherent and AP passes
     // work on res_all as it is; the coherent pass leaves c->llr alone, so AP sees the STFT LLRs
+    RetryLists failed{};
+    failed.res = B.res;
+    failed.cand_count = cand_count;
+    failed.cand_in = cand;
+    failed.score_in = cand_score;
+    failed.n_slots = ns;
+    failed.N = N;
     if (coh) {
       CohLaunch L;
       if ((rc = coherent_setup(c, xs, dtype, n_samples, ns, slot_stride, p, &L))) return rc;
-      if ((rc = coherent_pass(c, L, B.res, cand_count, cand, cand_score, ns, N, c0, p->max_iterations,
-                              1 + 2 * n_chunks + k, cs)))
+      if ((rc = coherent_pass(c, L, failed, c0, p->max_iterations, bp_counter(kChunkCoherent, k, n_chunks), cs)))
         return rc;
     }
-    if (ap && (rc = ap_pass(c, B.llr_in, B.res, cand_count, cand, cand_score, ns, N, c0, p->max_iterations, nullptr,
-                            1 + n_chunks + k, cs)))
+    if (ap && (rc = ap_pass(c, failed, B.llr_in, c0, p->max_iterations, nullptr, bp_counter(kChunkAp, k, n_chunks), cs)))
       return rc;
     CompactLaunch C{};
     C.res = B.res;
@@ -1486,7 +1500,7 @@ int ft8_bp(ft8_ctx* c, const double* d_llr, int32_t n, int32_t max_iterations, u
   if (n <= 0) return FT8_OK;
   DeviceGuard dg(c->device);
   int rc;
-  if ((rc = ensure_work(c, 1, (hipStream_t)stream))) return rc;  // counter [0]: ft8_bp's own
+  if ((rc = ensure_work(c, 1, (hipStream_t)stream))) return rc;
   BpLaunch L{};
   L.mode = 2;
   L.llr_in = d_llr;
@@ -1495,9 +1509,7 @@ int ft8_bp(ft8_ctx* c, const double* d_llr, int32_t n, int32_t max_iterations, u
   L.max_iterations = max_iterations;
   L.plain_out = d_plain;
   L.res = d_res;
-  L.work = c->work.as<unsigned long long>();
-  L.work_base = &c->work_base[0];
-  wire_bp_stats(c, L);
+  wire_bp_counters(c, L, bp_counter(kCallerBp, 0, 0), L.grid_waves);  // BpLaunch's default residency, not the pipeline's
   hipStream_t s = (hipStream_t)stream;
   return timed_launch(c, kBp, s, "bp launch", [&] { return launch_bp(L, s); });
 }
@@ -1523,14 +1535,18 @@ int ft8_ap_decode(ft8_ctx* c, const double* d_llr, ft8_result* d_res, int32_t n,
   DeviceGuard dg(c->device);
   hipStream_t s = (hipStream_t)stream;
   int rc;
-  if ((rc = ensure_work(c, 1, s))) return rc;  // counter [0], as ft8_bp: both run on a caller stream, in order
-  if ((rc = ensure_ap_scratch(c, 1, (size_t)n))) return rc;
+  if ((rc = ensure_work(c, 1, s))) return rc;
+  if ((rc = ensure_ap_scratch(c, 1, n))) return rc;
   if (d_hard) {
     hipError_t e = hipMemsetAsync(d_hard, 0xFF, sizeof(int16_t) * (size_t)n, s);  // -1 throughout
     if (e != hipSuccess) return hipfail(c, e, "memset");
   }
-  // records without slot structure: one list of n
-  return ap_pass(c, d_llr, d_res, nullptr, nullptr, nullptr, 1, n, 0, max_iterations, d_hard, 0, s);
+  // records without slot structure: one list of n, no candidate positions or scores
+  RetryLists failed{};
+  failed.res = d_res;
+  failed.n_slots = 1;
+  failed.N = n;
+  return ap_pass(c, failed, d_llr, 0, max_iterations, d_hard, bp_counter(kCallerBp, 0, 0), s);
 }
 
 int ft8_set_coherent(ft8_ctx* c, int32_t max_per_slot) {
@@ -1609,8 +1625,8 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   if ((rc = ensure(c, c->res_all, sizeof(ft8_result) * (size_t)n_slots * N))) return rc;
   if ((rc = ensure(c, c->llr, sizeof(double) * FT8_LDPC_N * (size_t)n_slots * N))) return rc;
   if ((rc = ensure_sel_scratch(c, n_slots, gr, N, f64))) return rc;
-  if ((p->flags & FT8_FLAG_AP) && (rc = ensure_ap_scratch(c, (size_t)n_slots, (size_t)n_slots * N))) return rc;
-  if ((p->flags & FT8_FLAG_COHERENT) && (rc = ensure_coh_scratch(c, (size_t)n_slots, (size_t)coherent_cap(c, N))))
+  if ((p->flags & FT8_FLAG_AP) && (rc = ensure_ap_scratch(c, (size_t)n_slots, N))) return rc;
+  if ((p->flags & FT8_FLAG_COHERENT) && (rc = ensure_coh_scratch(c, (size_t)n_slots, coherent_cap(c, N))))
     return rc;
   if (!(p->flags & FT8_FLAG_SUBTRACT)) {
     if ((rc = decode_pass(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, d_out, d_counts, cap, s))) return rc;

@@ -3,7 +3,7 @@
 //
 // Build-defined: the reference forms its LLRs once, from the dB bins of a one-symbol Hann STFT
 // (ft8_decode.py:151-188).  Here a candidate BP failed on is demodulated again from the samples:
-//   k_coh_list   one wave per slot: the failed candidates (ok == 0) in candidate order, at most M
+//   k_retry_list (ap.hip; the retry pass of ft8_internal.h) lists each slot's first M failed candidates
 //   k_coherent   one 256-lane workgroup per list position (a slot's positions on one XCD):
 //     1. baseband: the samples around the candidate are mixed down to the centre of the 8-tone band
 //        and box-car decimated to Q samples per symbol (D = nsps / Q input samples each) -- the
@@ -347,52 +347,17 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a) {
   }
 }
 
-__device__ __forceinline__ int coh_slot_count(const CohPass& a, int slot) {
-  return a.cand_count ? min(a.N, a.cand_count[slot]) : a.N;
-}
-
-// one wave per slot: the first M failed candidates in candidate order (ballot / popcount scan, as k_ap_list)
-__global__ __launch_bounds__(kWave) void k_coh_list(CohPass a) {
-  const int slot = blockIdx.x, lane = threadIdx.x;
-  const int nc = coh_slot_count(a, slot);
-  const int64_t s0 = (int64_t)slot * a.N, l0 = (int64_t)slot * a.M;
-  int base = 0;
-  for (int c0 = 0; c0 < nc && base < a.M; c0 += kWave) {
-    const int c = c0 + lane;
-    const bool take = c < nc && !a.res[s0 + c].ok;
-    const unsigned long long m = __ballot(take);
-    const int at = base + __popcll(m & ((1ull << lane) - 1ull));
-    if (take && at < a.M) {
-      a.list[l0 + at] = c;
-      a.cand[2 * (l0 + at)] = a.cand_in[2 * (s0 + c)];
-      a.cand[2 * (l0 + at) + 1] = a.cand_in[2 * (s0 + c) + 1];
-      a.score[l0 + at] = a.score_in[s0 + c];
-    }
-    base += __popcll(m);
-  }
-  if (lane == 0) a.count[slot] = min(base, a.M);
-}
-
 // one wave per list position: a valid fit whose attempt the tail accepted rewrites its record
 __global__ __launch_bounds__(4 * kWave) void k_coh_merge(CohPass a) {
+  const RetryLists& r = a.r;
   const int lane = threadIdx.x % kWave;
   const int64_t pos = (int64_t)blockIdx.x * 4 + threadIdx.x / kWave;
-  if (pos >= (int64_t)a.n_slots * a.M) return;
-  const int slot = (int)(pos / a.M), j = (int)(pos % a.M);
-  if (j >= a.count[slot]) return;
-  const ft8_result& r = a.res_c[pos];
-  if (!r.ok || a.fit[pos].status != 0) return;
-  if (lane == 0) {
-    const int64_t src = (int64_t)slot * a.N + a.list[pos];
-    ft8_result w = a.res[src];
-    w.ok = 1;
-    for (int i = 0; i < 10; ++i) w.payload[i] = r.payload[i];
-    w.crc_extracted = r.crc_extracted;
-    w.crc_calculated = r.crc_calculated;
-    w.ldpc_errors = r.ldpc_errors;
-    w.pass_index = (uint8_t)(w.pass_index | 2);
-    a.res[src] = w;
-  }
+  if (pos >= (int64_t)r.n_slots * r.M) return;
+  const int slot = (int)(pos / r.M), j = (int)(pos % r.M);
+  if (j >= r.count[slot]) return;
+  const ft8_result& got = a.res_c[pos];
+  if (!got.ok || a.fit[pos].status != 0) return;
+  if (lane == 0) retry_accept(r.res + (int64_t)slot * r.N + r.list[pos], got, 2);
 }
 
 }  // namespace
@@ -410,15 +375,9 @@ hipError_t launch_coherent(const CohLaunch& a, hipStream_t s) {
   return lds_launch(k_coherent<float>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a);
 }
 
-hipError_t launch_coh_list(const CohPass& a, hipStream_t s) {
-  if (a.n_slots <= 0 || a.M <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_coh_list, dim3(a.n_slots), dim3(kWave), 0, s, a);
-  return hipGetLastError();
-}
-
 hipError_t launch_coh_merge(const CohPass& a, hipStream_t s) {
-  if (a.n_slots <= 0 || a.M <= 0) return hipSuccess;
-  const unsigned blocks = (unsigned)(((int64_t)a.n_slots * a.M + 3) / 4);
+  if (a.r.n_slots <= 0 || a.r.M <= 0) return hipSuccess;
+  const unsigned blocks = (unsigned)(((int64_t)a.r.n_slots * a.r.M + 3) / 4);
   hipLaunchKernelGGL(k_coh_merge, dim3(blocks), dim3(4 * kWave), 0, s, a);
   return hipGetLastError();
 }

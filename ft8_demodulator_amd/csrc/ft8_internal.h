@@ -282,32 +282,58 @@ struct CompactLaunch {
 };
 hipError_t launch_compact(const CompactLaunch& a, hipStream_t s);
 
-// ---- a-priori decoding (ap.hip) ----------------------------------------------------------------
-// One hypothesis' retry of the failed candidates of res[n_slots][N] (ft8hip.h, "a-priori decoding"):
-// k_ap_amax (once per AP pass) -> per hypothesis: k_ap_list + k_ap_clamp, launch_bp in mode 0 over the
-// compacted lists (cand / score / count below as its candidate lists, llr_h as its LLRs, plain and
-// res_h as its outputs), k_ap_merge.  Every array is [n_slots][N] (x 174 for llr / llr_h / plain).
-struct ApLaunch {
-  const double* llr;           // the LLRs plain BP consumed
-  ft8_result* res;             // in / out: the records plain BP wrote
+// ---- retry pass: the failed candidates of a chunk, tried again (ap.hip, coherent.hip) --------------
+// Both retries of ft8_decode_batch take the records plain BP left with ok == 0: launch_retry_list lists
+// them per slot in candidate order, the pass builds new LLRs for the list positions, launch_bp runs in
+// mode 0 over the compacted lists (cand / score / count as its candidate lists), and the pass's merge
+// kernel lets retry_accept rewrite the record of every attempt it accepts.
+struct RetryLists {
+  ft8_result* res;             // in / out [n_slots][N]: the records plain BP wrote
   const int32_t* cand_count;   // [n_slots], null: every slot holds N records
   const int32_t* cand_in;      // nullable [n_slots][N][2] and [n_slots][N]: the candidates' positions and
   const double* score_in;      // scores (copied to the compacted lists; zeros without them)
-  int n_slots, N;
+  const double* gate;          // nullable [n_slots][N]: only candidates with gate != 0 are listed
+  int n_slots, N, M;           // M <= N: list positions per slot
+  int32_t* list;               // [n_slots][M] original indices of the listed candidates
+  int32_t* count;              // [n_slots] their number
+  int32_t* cand;               // compacted [n_slots][M][2]
+  double* score;               // compacted [n_slots][M]
+};
+__device__ inline int slot_count(const RetryLists& r, int slot) {
+  return r.cand_count ? min(r.N, r.cand_count[slot]) : r.N;
+}
+// k_retry_list, one wave per slot: the first M candidates c < slot_count with !res.ok (and gate != 0),
+// in candidate order; count = min(found, M)
+hipError_t launch_retry_list(const RetryLists& r, hipStream_t s);
+// an accepted attempt `got` rewrites the record it retried; pass_bits: (h + 1) << 4 for AP hypothesis
+// h, 2 for the coherent pass
+__device__ inline void retry_accept(ft8_result* rec, const ft8_result& got, int pass_bits) {
+  ft8_result w = *rec;
+  w.ok = 1;
+  for (int i = 0; i < 10; ++i) w.payload[i] = got.payload[i];
+  w.crc_extracted = got.crc_extracted;
+  w.crc_calculated = got.crc_calculated;
+  w.ldpc_errors = got.ldpc_errors;
+  w.pass_index = (uint8_t)(w.pass_index | pass_bits);
+  *rec = w;
+}
+
+// ---- a-priori decoding (ap.hip) ----------------------------------------------------------------
+// The AP retry (ft8hip.h, "a-priori decoding"): k_ap_amax once (amax is the lists' gate), then per
+// hypothesis the list (M = N), k_ap_clamp -> llr_h, launch_bp -> plain and res_h, k_ap_merge.
+struct ApLaunch {
+  RetryLists r;
+  const double* llr;           // [n_slots][N][174] the LLRs plain BP consumed
   ft8_ap_hyp hyp;              // the hypothesis of this attempt, by value
   int h, max_hard;
-  double* amax;                // a = 1.01 max |L| of every candidate, 0 where it is not to be retried
-  int32_t* list;               // per slot: original indices of the candidates this attempt retries
-  int32_t* count;              // [n_slots] their number
-  int32_t* cand;               // compacted [n_slots][N][2]
-  double* score;               // compacted
+  double* amax;                // [n_slots][N] a = 1.01 max |L| of a candidate, 0 where it is not to be retried
   double* llr_h;               // compacted, clamped LLRs
   const uint8_t* plain;        // launch_bp's hard decisions of the compacted lists
   const ft8_result* res_h;     // launch_bp's records of them
   int16_t* hard;               // nullable [n_slots * N], by original index: hard_h of an accepted attempt
 };
 hipError_t launch_ap_amax(const ApLaunch& a, hipStream_t s);
-hipError_t launch_ap_prepare(const ApLaunch& a, hipStream_t s);  // k_ap_list, k_ap_clamp
+hipError_t launch_ap_clamp(const ApLaunch& a, hipStream_t s);
 hipError_t launch_ap_merge(const ApLaunch& a, hipStream_t s);
 
 // ---- coherent re-demodulation (coherent.hip) ---------------------------------------------------
@@ -331,23 +357,13 @@ struct CohLaunch {
 };
 size_t coherent_lds_bytes(int nsps, int Q);   // k_coherent's dynamic LDS
 hipError_t launch_coherent(const CohLaunch& a, hipStream_t s);
-// The pass around it inside ft8_decode_batch: k_coh_list (per slot the first M candidates with ok == 0
-// of res[n_slots][N], in candidate order -> list / cand / score [n_slots][M], count), then k_coherent
-// and launch_bp in mode 0 over those lists (fit, res_c), then k_coh_merge.
+// The coherent retry inside ft8_decode_batch: the list (M = the per-slot cap), k_coherent -> fit and
+// the LLRs, launch_bp -> res_c, k_coh_merge.
 struct CohPass {
-  ft8_result* res;             // in / out: the records plain BP wrote
-  const int32_t* cand_count;   // [n_slots], null: every slot holds N records
-  const int32_t* cand_in;      // [n_slots][N][2]
-  const double* score_in;      // [n_slots][N]
-  int n_slots, N, M;
-  int32_t* list;               // [n_slots][M] original indices of the listed candidates
-  int32_t* count;              // [n_slots]
-  int32_t* cand;               // compacted [n_slots][M][2]
-  double* score;               // compacted
+  RetryLists r;
   const ft8_coh_fit* fit;      // k_coherent's fits of the lists
   const ft8_result* res_c;     // launch_bp's records of them
 };
-hipError_t launch_coh_list(const CohPass& a, hipStream_t s);
 hipError_t launch_coh_merge(const CohPass& a, hipStream_t s);
 
 // ft8_pack_decodes (bp.hip): one workgroup packs a batch's decodes for the all-gather

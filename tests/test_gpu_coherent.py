@@ -81,19 +81,31 @@ def test_stage_slot_out_of_range_and_empty(gpu):
 E2E = dict(max_candidates=20, min_score=2)
 CAP = 4
 AP = ["CQ ? ?"]
+# more candidates than one wave scans in a round (64): with the cap chosen by _late_cap the list of one
+# slot fills up in the second round
+E2E_LATE = dict(max_candidates=80, min_score=2)
 
 
-def _decoder(**kw):
+def _decoder(search=E2E, **kw):
     from ft8_demodulator_amd._pipeline import SlotDecoder
-    return SlotDecoder(C.FS, max_iterations=ITERS, flags=_L().FT8_FLAG_TOPK, **E2E, **kw)
+    return SlotDecoder(C.FS, max_iterations=ITERS, flags=_L().FT8_FLAG_TOPK, **search, **kw)
 
 
-@pytest.fixture(scope="module")
-def e2e(gpu, oracle):
+def _late_cap(plain):
+    """(slot, cap) from the plain records alone: the slot with the most failed candidates past its first
+    64, and a cap halfway between its failed candidates among the first 64 and all its failed ones."""
+    fails = [(int(((plain["slot"] == s) & (plain["ok"] == 0) & (plain["cand_index"] < 64)).sum()),
+              int(((plain["slot"] == s) & (plain["ok"] == 0)).sum())) for s in range(3)]
+    s = max(range(3), key=lambda i: fails[i][1] - fails[i][0])
+    return s, (fails[s][0] + fails[s][1] + 1) // 2
+
+
+def _expectation(gpu, oracle, search, cap, with_ap):
     """The expectation, from the device's own stage calls: ft8_stft, ft8_sync_select and ft8_llr give every
-    candidate's STFT LLRs, the oracle's BP the plain records; each slot's first CAP failed candidates
-    get the stage call's coherent LLRs, decoded by the oracle again.  -> all records after the coherent
-    pass, after coherent + AP, and the plain ones (read-only)."""
+    candidate's STFT LLRs, the oracle's BP the plain records; each slot's first `cap` (a number, or a
+    function of the plain records that returns (slot, cap)) failed candidates get the stage call's
+    coherent LLRs, decoded by the oracle again.  -> all records after the coherent pass, after
+    coherent + AP (with_ap), and the plain ones (read-only)."""
     from ft8_demodulator_amd import ap
     from ft8_demodulator_amd._pipeline import make_params, make_plan
     from ft8_demodulator_amd.ldpc_decoder import coherent_llr_batch
@@ -103,8 +115,8 @@ def e2e(gpu, oracle):
     ctx = _lib.Context(0)
     L, st = _lib.lib(), _lib.stream_handle(0)
     plan = make_plan(n, C.FS)
-    N = E2E["max_candidates"]
-    p = make_params(plan, N, E2E["min_score"], ITERS, _lib.FT8_FLAG_TOPK)
+    N = search["max_candidates"]
+    p = make_params(plan, N, search["min_score"], ITERS, _lib.FT8_FLAG_TOPK)
     d_x = torch.from_numpy(x).cuda()
     T, F = plan.T, plan.F
     d_wf = torch.empty(n_slots, T, F, dtype=torch.float32, device="cuda")
@@ -129,8 +141,11 @@ def e2e(gpu, oracle):
             rec0["score"][k], rec0["slot"][k], rec0["cand_index"][k] = score[s, i], s, i
             rec0["abs_time"][k], rec0["abs_freq"][k] = cand[s, i]
             k += 1
-    # each slot's first CAP failed candidates, in candidate order
-    listed = [i for s in range(n_slots) for i in np.nonzero((rec0["slot"] == s) & (rec0["ok"] == 0))[0][:CAP]]
+    slot = None
+    if callable(cap):
+        slot, cap = cap(rec0)
+    # each slot's first cap failed candidates, in candidate order
+    listed = [i for s in range(n_slots) for i in np.nonzero((rec0["slot"] == s) & (rec0["ok"] == 0))[0][:cap]]
     cl, cf = coherent_llr_batch(x, [(rows[i][1], rows[i][2]) for i in listed], [rows[i][0] for i in listed], C.FS)
     coh = np.array(rec0, copy=True)
     for i, v, f in zip(listed, cl, cf):
@@ -139,10 +154,20 @@ def e2e(gpu, oracle):
             coh["ok"][i], coh["pass_index"][i] = 1, 2
             coh["payload"][i] = np.frombuffer(pay, dtype=np.uint8)
             coh["crc_extracted"][i], coh["crc_calculated"][i], coh["ldpc_errors"][i] = ce, cc, err
-    both, _ = A.restate(llr, coh, [ap.ap_hypothesis(t) for t in AP], ap.DEFAULT_MAX_HARD_ERRORS)
-    for a in (rec0, coh, both):
+    both = A.restate(llr, coh, [ap.ap_hypothesis(t) for t in AP], ap.DEFAULT_MAX_HARD_ERRORS)[0] if with_ap else None
+    for a in (rec0, coh) + ((both,) if with_ap else ()):
         a.setflags(write=False)
-    return {"x": x, "plain": rec0, "coherent": coh, "both": both, "listed": listed}
+    return {"x": x, "plain": rec0, "coherent": coh, "both": both, "listed": listed, "cap": cap, "slot": slot}
+
+
+@pytest.fixture(scope="module")
+def e2e(gpu, oracle):
+    return _expectation(gpu, oracle, E2E, CAP, True)
+
+
+@pytest.fixture(scope="module")
+def e2e_late(gpu, oracle):
+    return _expectation(gpu, oracle, E2E_LATE, _late_cap, False)
 
 
 def _per_slot(rec, s):
@@ -195,6 +220,33 @@ def test_e2e_pipelined_chunks_and_int16(gpu, e2e):
     pcm = gpu.from_numpy(np.array(C.stage_case_12k()["pcm"])).cuda()
     got16 = _decoder(coherent=CAP).records(pcm, code=_L().FT8_I16)
     assert sum(int((r["pass_index"] == 2).sum()) for r in got16) >= 2
+
+
+def test_late_cap_expectation_fills_the_list_in_the_second_round(e2e_late):
+    """On the expectation alone: one slot selects more than 64 candidates, fewer of its first 64 failed
+    than the cap lists, and more of them all failed than the cap lists."""
+    plain, s, cap = e2e_late["plain"], e2e_late["slot"], e2e_late["cap"]
+    mine = plain[plain["slot"] == s]
+    assert len(mine) > 64 and (mine["cand_index"] == np.arange(len(mine))).all()
+    failed = mine["cand_index"][mine["ok"] == 0]
+    assert int((failed < 64).sum()) < cap < len(failed)
+    listed = [i for i in e2e_late["listed"] if plain["slot"][i] == s]
+    assert len(listed) == cap and plain["cand_index"][listed[-1]] >= 64
+    assert int(plain["ok"].sum()) >= 3 and int((e2e_late["coherent"]["pass_index"] == 2).sum()) >= 1
+
+
+def test_late_cap_records_equal_construction(gpu, e2e_late):
+    """max_candidates 80: the list kernel reaches the cap in its second round of 64, as one chain and as
+    one slot per chunk over two internal streams."""
+    x = gpu.from_numpy(e2e_late["x"]).cuda()
+    one = _decoder(E2E_LATE, coherent=e2e_late["cap"])
+    piped = _decoder(E2E_LATE, coherent=e2e_late["cap"], context=_L().Context(0))
+    piped.ctx.set_pipeline(1, 2, 4)
+    for dec in (one, piped):
+        got = dec.records(x)
+        assert len(got) == 3
+        for s in range(3):
+            A.records_equal(got[s], _per_slot(e2e_late["coherent"], s))
 
 
 def test_gain_on_the_device(gpu):
