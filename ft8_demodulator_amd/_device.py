@@ -163,12 +163,13 @@ def ap_decode(llrs, records, max_iterations):
 
 
 def coherent_llr(samples, cand, slot_of, sample_rate=12000, bins_per_tone=2, steps_per_symbol=2, t_lo=0, f_lo=0,
-                 code=None):
+                 code=None, drift=None):
     """ft8_coherent_llr: samples [n_slots, n_samples] (float32, or int16 PCM; NumPy or a GPU tensor with
     its ft8 dtype `code`), candidates cand [n, 2] = (abs_time, abs_freq) of the slots slot_of [n]
-    -> (LLRs float64 [n, 174], fits coherent.FIT_DTYPE [n])."""
+    -> (LLRs float64 [n, 174], fits coherent.FIT_DTYPE [n]).  drift = (max_rate, n_rates):
+    ft8_coherent_drift_llr -> (LLRs, fits, drifts coherent.DRIFT_DTYPE [n])."""
     from ._pipeline import device_samples
-    from .coherent import FIT_DTYPE
+    from .coherent import DRIFT_DTYPE, FIT_DTYPE
     torch = _lib.require_gpu()
     ctx = _lib.context()
     x = samples
@@ -194,6 +195,14 @@ def coherent_llr(samples, cand, slot_of, sample_rate=12000, bins_per_tone=2, ste
     d_so = torch.from_numpy(np.concatenate([so, np.zeros(1, np.int32)])).to(x.device)
     d_llr = torch.zeros(max(n, 1), 174, dtype=torch.float64, device=x.device)
     d_fit = torch.zeros(max(n, 1) * FIT_DTYPE.itemsize, dtype=torch.uint8, device=x.device)
+    if drift is not None:
+        d_dr = torch.zeros(max(n, 1) * DRIFT_DTYPE.itemsize, dtype=torch.uint8, device=x.device)
+        ctx.check(_lib.lib().ft8_coherent_drift_llr(ctx.handle, _lib.ptr(x), int(code), ns, n_slots, ns, ctypes.byref(p),
+                                                    _lib.ptr(d_c), _lib.ptr(d_so), n, float(drift[0]), int(drift[1]),
+                                                    _lib.ptr(d_llr), _lib.ptr(d_fit), _lib.ptr(d_dr),
+                                                    _lib.stream_handle()), "ft8_coherent_drift_llr")
+        return (d_llr.cpu().numpy()[:n], d_fit.cpu().numpy()[: n * FIT_DTYPE.itemsize].view(FIT_DTYPE).copy(),
+                d_dr.cpu().numpy()[: n * DRIFT_DTYPE.itemsize].view(DRIFT_DTYPE).copy())
     ctx.check(_lib.lib().ft8_coherent_llr(ctx.handle, _lib.ptr(x), int(code), ns, n_slots, ns, ctypes.byref(p),
                                           _lib.ptr(d_c), _lib.ptr(d_so), n, _lib.ptr(d_llr), _lib.ptr(d_fit),
                                           _lib.stream_handle()), "ft8_coherent_llr")

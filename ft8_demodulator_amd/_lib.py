@@ -172,6 +172,9 @@ def lib():
             "ft8_ap_decode": ([vp, vp, vp, i32, i32, vp, vp], ctypes.c_int),
             "ft8_set_coherent": ([vp, i32], ctypes.c_int),
             "ft8_coherent_llr": ([vp, vp, ctypes.c_int, i64, i32, i64, P, vp, vp, i32, vp, vp, vp], ctypes.c_int),
+            "ft8_set_coherent_drift": ([vp, ctypes.c_float, i32], ctypes.c_int),
+            "ft8_coherent_drift_llr": ([vp, vp, ctypes.c_int, i64, i32, i64, P, vp, vp, i32, ctypes.c_float, i32, vp, vp,
+                                        vp, vp], ctypes.c_int),
         }
         stale_ok = os.environ.get("FT8HIP_ALLOW_STALE") == "1"
         for name, (args, res) in sig.items():
@@ -223,7 +226,8 @@ EXPORTED_SYMBOLS = (
     "ft8_build_id", "ft8_build_flags", "ft8_replay_stage", "ft8_set_timing_stages", "ft8_sync_score",
     "ft8_pack_bytes", "ft8_pack_decodes", "ft8_subtract_fits", "ft8_stft_method", "ft8_stft_screen_stats",
     "ft8_unpack77", "ft8_unpack77_host", "ft8_hash_call", "ft8_noise_floor", "ft8_snr", "ft8_snr_last",
-    "ft8_set_ap", "ft8_ap_decode", "ft8_set_coherent", "ft8_coherent_llr")
+    "ft8_set_ap", "ft8_ap_decode", "ft8_set_coherent", "ft8_coherent_llr",
+    "ft8_set_coherent_drift", "ft8_coherent_drift_llr")
 
 
 def limits():
@@ -317,6 +321,12 @@ class Context:
         """ft8_set_coherent: how many failed candidates per slot an FT8_FLAG_COHERENT batch demodulates
         again from the samples (0: every one)."""
         self.check(lib().ft8_set_coherent(self.handle, int(max_per_slot)), "ft8_set_coherent")
+
+    def set_coherent_drift(self, max_rate_hz_per_s: float = 0.0, n_rates: int = 1):
+        """ft8_set_coherent_drift: the drift search of an FT8_FLAG_COHERENT batch, n_rates (odd, <= 33)
+        rates over +-max_rate_hz_per_s (<= 4 Hz/s); (0, 1): off."""
+        self.check(lib().ft8_set_coherent_drift(self.handle, float(max_rate_hz_per_s), int(n_rates)),
+                   "ft8_set_coherent_drift")
 
     def replay(self, stage: str, reps: int = 1, stream=None):
         """ft8_replay_stage: re-launch one kernel of the last ft8_decode_batch `reps` times."""

@@ -227,16 +227,27 @@ class SlotDecoder:
     def __init__(self, sample_rate=12000, bins_per_tone=2, steps_per_symbol=2, max_candidates=20,
                  min_score=10, max_iterations=20, freq_min=None, freq_max=None, time_min=None,
                  time_max=None, device=None, flags=0, max_results_per_slot=None, context=None, ap=None,
-                 ap_max_hard_errors=None, coherent=None):
+                 ap_max_hard_errors=None, coherent=None, coherent_drift=None):
         """ap: a-priori patterns (ap.ap_hypothesis, e.g. ["CQ ? ?", "K1ABC ? ?"], tried in order on every
         candidate BP fails on; at most 8) -- sets FT8_FLAG_AP; None: plain decoding.  ap_max_hard_errors:
         the most hard decisions of an accepted AP decode that may contradict the received LLRs' signs
         (default ap.DEFAULT_MAX_HARD_ERRORS = 36; 174: no limit).
         coherent: True or a count -- sets FT8_FLAG_COHERENT: per slot that many of the best-scoring
         candidates BP fails on (True: 32, 0: every one) are demodulated again coherently from the samples
-        (coherent.py) and decoded from those LLRs; None / False: off."""
+        (coherent.py) and decoded from those LLRs; None / False: off.
+        coherent_drift: True or (max_rate Hz/s, n_rates) -- the coherent pass also searches n_rates (odd,
+        <= 33) linear frequency drift rates over +-max_rate (<= 4; True: 1.0, 9) for every listed
+        candidate (ft8_set_coherent_drift); needs coherent.  None / False: off."""
         from . import ap as _ap
         from . import coherent as _coh
+        if coherent_drift is None or coherent_drift is False:
+            self.coherent_drift = None
+        else:
+            if coherent is None or coherent is False:
+                raise ValueError("coherent_drift needs coherent")
+            a, r = _coh.DEFAULT_DRIFT if coherent_drift is True else coherent_drift
+            _coh.drift_rates(a, r)   # ValueError for what the library refuses
+            self.coherent_drift = (float(a), int(r))
         if coherent is None or coherent is False:
             self.coherent = None
         else:
@@ -315,6 +326,7 @@ class SlotDecoder:
             self.ctx.set_ap(self.ap_hyps, self.ap_max_hard_errors)
         if self.coherent is not None:
             self.ctx.set_coherent(self.coherent)
+            self.ctx.set_coherent_drift(*(self.coherent_drift or (0.0, 1)))
         rc = _lib.lib().ft8_decode_batch(self.ctx.handle, _lib.ptr(x), int(code), n, n_slots, n,
                                          ctypes.byref(p), _lib.ptr(out), _lib.ptr(counts), self.cap,
                                          _lib.stream_handle(torch.device("cuda", self.device)))
@@ -434,7 +446,7 @@ def decode_slots(samples, sample_rate=12000, **kwargs):
 
 def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_candidates=20, min_score=10,
                max_iterations=20, freq_min=None, freq_max=None, time_min=None, time_max=None, *, flags=0, snr=False,
-               ap=None, ap_max_hard_errors=None, coherent=None):
+               ap=None, ap_max_hard_errors=None, coherent=None, coherent_drift=None):
     """One slot, x [N] on the GPU with its ft8 dtype code, through a SlotDecoder of its own:
     -> (decode_ft8_message's 5-tuples, with snr the ft8_snr_rec records aligned with them else None,
     the ft8_result records).  Nothing is launched when the masks leave nothing or max_candidates <= 0."""
@@ -444,7 +456,7 @@ def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_ca
     if not plan.empty and max_candidates > 0:
         dec = SlotDecoder(sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score, max_iterations,
                           freq_min, freq_max, time_min, time_max, device=x.device, flags=flags, ap=ap,
-                          ap_max_hard_errors=ap_max_hard_errors, coherent=coherent)
+                          ap_max_hard_errors=ap_max_hard_errors, coherent=coherent, coherent_drift=coherent_drift)
         recs, _, reps = (v if v is None else v[0] for v in dec._fetch(x.unsqueeze(0), code, snr=snr))
     wf_f64 = code in (_lib.FT8_F64, _lib.FT8_C128)
     return records_to_results(recs, sample_rate, bins_per_tone, wf_f64), reps, recs

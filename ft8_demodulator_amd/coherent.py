@@ -30,6 +30,11 @@ FIT_DTYPE = np.dtype({
 })
 STATUS_VALID, STATUS_NOTHING, STATUS_NOT_ATTEMPTED = 0, 2, 3
 
+# ft8_coh_drift (8 bytes): the winning rate of the drift search
+DRIFT_DTYPE = np.dtype([("rate_hz_per_s", "<f4"), ("rate_index", "<i4")])
+MAX_DRIFT_RATES, MAX_DRIFT_HZ_PER_S = 33, 4.0
+DEFAULT_DRIFT = (1.0, 9)           # SlotDecoder(coherent_drift=True)
+
 
 def sub_q(nsps: int) -> int:
     """Decimated samples per symbol: the largest divisor of nsps in [8, 32], 0 when there is none."""
@@ -55,6 +60,25 @@ def coherent_index(record) -> int:
     return (int(record["pass_index"]) >> 1) & 1
 
 
+def drift_index(record) -> int:
+    """1 when the record was rescued at a drift rate other than 0 (pass_index bit 2), else 0."""
+    return (int(record["pass_index"]) >> 2) & 1
+
+
+def drift_rates(max_rate, n_rates) -> np.ndarray:
+    """The rates r_i = (i - (R - 1) / 2) * 2 A / (R - 1) of the drift search in Hz/s, float64 [R], A being
+    max_rate as the float32 the C-ABI takes ([0.0] where the search is off: R = 1 or A = 0).  ValueError
+    for what ft8_set_coherent_drift answers with FT8_E_ARG: R even or outside [1, 33], A outside [0, 4]."""
+    R, A = int(n_rates), float(np.float32(max_rate))
+    if R != n_rates or R < 1 or R > MAX_DRIFT_RATES or R % 2 == 0:
+        raise ValueError(f"coherent drift: n_rates must be odd and in [1, {MAX_DRIFT_RATES}]")
+    if not 0.0 <= A <= MAX_DRIFT_HZ_PER_S:
+        raise ValueError(f"coherent drift: max_rate must be in [0, {MAX_DRIFT_HZ_PER_S:g}] Hz/s")
+    if R == 1 or A == 0.0:
+        return np.zeros(1)
+    return (np.arange(R) - (R - 1) // 2).astype(np.float64) * (2.0 * A / (R - 1))
+
+
 def _as_float64(x: np.ndarray) -> np.ndarray:
     x = np.asarray(x)
     if x.dtype == np.int16:
@@ -73,10 +97,14 @@ def _llr_of_spectra(s: np.ndarray) -> np.ndarray:
         s2[:, [1, 3, 5, 7]].max(1) - s2[:, [0, 2, 4, 6]].max(1)], axis=1)
 
 
-def coherent_restate(samples, cand, slot_of, fs, nperseg, nfft, steps_per_symbol, t_lo=0, f_lo=0, details=False):
+def coherent_restate(samples, cand, slot_of, fs, nperseg, nfft, steps_per_symbol, t_lo=0, f_lo=0, details=False,
+                     drift=None):
     """samples [n_slots, n_samples] (float32, or int16 PCM), cand [n, 2] = (abs_time, abs_freq), slot_of [n]
     -> (llr float64 [n, 174], fits FIT_DTYPE [n]); with details also the list of every candidate's
-    metric grid [2 Mt + 1, 5] (None where no sync symbol was present)."""
+    metric grid [2 Mt + 1, 5] (None where no sync symbol was present).
+    drift = (max_rate, n_rates): the search over linear drift rates (drift_rates; the header's step 1b)
+    -> (llr, fits, drifts DRIFT_DTYPE [n]) and with details the metric volumes [R, 2 Mt + 1, 5]."""
+    rates = None if drift is None else drift_rates(*drift)
     x_all = np.asarray(samples)
     if x_all.ndim == 1:
         x_all = x_all[None, :]
@@ -99,6 +127,9 @@ def coherent_restate(samples, cand, slot_of, fs, nperseg, nfft, steps_per_symbol
 
     llr = np.zeros((n, 174), dtype=np.float64)
     fits = np.zeros(n, dtype=FIT_DTYPE)
+    drifts = np.zeros(n, dtype=DRIFT_DTYPE)
+    # centre of decimation block m relative to the centre of the nominal signal, squared
+    tau2 = (((np.arange(Mz) - Mg + 0.5) * D - 39.5 * nperseg) / fs) ** 2
     grids = []
     cache = {}
     for i in range(n):
@@ -126,10 +157,24 @@ def coherent_restate(samples, cand, slot_of, fs, nperseg, nfft, steps_per_symbol
             fits["status"][i] = STATUS_NOTHING
             continue
         # 3. sync on the Costas symbols
+        if rates is not None and len(rates) > 1:
+            # 1b. de-chirp by every rate; the first largest metric over (rate, dt, j) chooses z
+            vol, zs = [], []
+            for r in rates:
+                cyc = 0.5 * r * tau2
+                zs.append(z * np.exp(-2j * np.pi * (cyc - np.floor(cyc))))
+                corr = np.einsum("dsq,jsq->djs", zs[-1][widx][:, sync_k], R)
+                vol.append((np.abs(corr) ** 2 * present[:, None, sync_k]).sum(axis=2))
+            vol = np.stack(vol)                                                                      # [R, nT, 5]
+            ri = int(np.argmax(vol.reshape(-1))) // vol[0].size
+            z, metric = zs[ri], vol[ri]
+            drifts[i] = (rates[ri], ri)
+            grids[-1] = vol
         W = z[widx]                                                                                  # [nT, 79, Q]
-        corr = np.einsum("dsq,jsq->djs", W[:, sync_k], R)
-        metric = (np.abs(corr) ** 2 * present[:, None, sync_k]).sum(axis=2)                          # [nT, 5]
-        grids[-1] = metric
+        if rates is None or len(rates) == 1:
+            corr = np.einsum("dsq,jsq->djs", W[:, sync_k], R)
+            metric = (np.abs(corr) ** 2 * present[:, None, sync_k]).sum(axis=2)                      # [nT, 5]
+            grids[-1] = metric if rates is None else metric[None]
         best = int(np.argmax(metric.reshape(-1)))                                                    # the first largest
         di, j = divmod(best, N_DF)
         delta = 0.0
@@ -154,6 +199,8 @@ def coherent_restate(samples, cand, slot_of, fs, nperseg, nfft, steps_per_symbol
             continue
         llr[i] = L * np.sqrt(24.0 / var)
         f["status"] = STATUS_VALID
+    if rates is not None:
+        return (llr, fits, drifts, grids) if details else (llr, fits, drifts)
     return (llr, fits, grids) if details else (llr, fits)
 
 

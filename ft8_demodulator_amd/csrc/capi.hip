@@ -204,6 +204,10 @@ struct ft8_ctx {
   int coh_max = 0;
   RetryScratch coh;
   DevBuf coh_fit;
+  // its drift search (ft8_set_coherent_drift; off: 0, 1) and the winning rate per list position
+  float coh_drift_rate = 0.f;
+  int coh_drift_n = 1;
+  DevBuf coh_drift;
   // the stream of the last entry point that enqueued work, and an event recorded on it after that
   // work (StreamOrder): a call on another stream first waits for it
   hipStream_t last_stream = nullptr;
@@ -961,13 +965,25 @@ int coherent_setup(ft8_ctx* c, const void* x, int dtype, int64_t n_samples, int 
   return FT8_OK;
 }
 
+// the drift search's settings, as ft8_coherent_drift_llr and ft8_set_coherent_drift take them
+int check_coherent_drift(ft8_ctx* c, float max_rate, int n_rates) {
+  if (n_rates < 1 || n_rates > 33 || n_rates % 2 == 0)
+    return fail(c, FT8_E_ARG, "coherent drift: n_rates must be odd and in [1, 33]");
+  if (!(max_rate >= 0.f && max_rate <= 4.f))
+    return fail(c, FT8_E_ARG, "coherent drift: max_rate must be in [0, 4] Hz/s");
+  return FT8_OK;
+}
+
 // listed candidates per slot of an FT8_FLAG_COHERENT batch
 int coherent_cap(const ft8_ctx* c, int N) { return c->coh_max > 0 ? std::min(c->coh_max, N) : N; }
 
 // the coherent pass's scratch for n_slots lists of M candidates (ft8hip.h states the sizes)
 int ensure_coh_scratch(ft8_ctx* c, size_t n_slots, int M) {
   int rc = c->coh.ensure(c, n_slots, M);
-  return rc ? rc : ensure(c, c->coh_fit, sizeof(ft8_coh_fit) * n_slots * M);
+  if (!rc) rc = ensure(c, c->coh_fit, sizeof(ft8_coh_fit) * n_slots * M);
+  if (!rc && coherent_drift_on(CohDrift{c->coh_drift_rate, c->coh_drift_n, nullptr}))
+    rc = ensure(c, c->coh_drift, sizeof(ft8_coh_drift) * n_slots * M);
+  return rc;
 }
 
 // The coherent pass over the records `failed` describes, one chunk's (coherent.hip): list, k_coherent,
@@ -988,10 +1004,12 @@ int coherent_pass(ft8_ctx* c, CohLaunch L, const RetryLists& failed, int slot0, 
   L.M = l.M;
   L.llr = v.llr;
   L.fit = fit;
-  if ((e = launch_coherent(L, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
+  CohDrift G{c->coh_drift_rate, c->coh_drift_n, nullptr};
+  if (coherent_drift_on(G)) G.out = c->coh_drift.as<ft8_coh_drift>() + (size_t)slot0 * l.M;
+  if ((e = launch_coherent(L, G, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
   if ((e = bp_over_lists(c, l, v.llr, nullptr, v.res, max_iterations, counter, s)) != hipSuccess)
     return hipfail(c, e, "coherent bp launch");
-  const CohPass A{l, fit, v.res};
+  const CohPass A{l, fit, v.res, G.out};
   if ((e = launch_coh_merge(A, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
   return FT8_OK;
 }
@@ -1555,17 +1573,36 @@ int ft8_set_coherent(ft8_ctx* c, int32_t max_per_slot) {
   return FT8_OK;
 }
 
+int ft8_set_coherent_drift(ft8_ctx* c, float max_rate_hz_per_s, int32_t n_rates) {
+  if (!c) return FT8_E_ARG;
+  const int rc = check_coherent_drift(c, max_rate_hz_per_s, n_rates);
+  if (rc) return rc;
+  c->coh_drift_rate = max_rate_hz_per_s;
+  c->coh_drift_n = n_rates;
+  return FT8_OK;
+}
+
 int ft8_coherent_llr(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
                      int64_t slot_stride, const ft8_params* p, const int32_t* d_cand, const int32_t* d_slot_of,
                      int32_t n, double* d_llr_out, ft8_coh_fit* d_fit_out, void* stream) {
+  return ft8_coherent_drift_llr(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, d_cand, d_slot_of, n, 0.f, 1,
+                                d_llr_out, d_fit_out, nullptr, stream);
+}
+
+int ft8_coherent_drift_llr(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
+                           int64_t slot_stride, const ft8_params* p, const int32_t* d_cand,
+                           const int32_t* d_slot_of, int32_t n, float max_rate_hz_per_s, int32_t n_rates,
+                           double* d_llr_out, ft8_coh_fit* d_fit_out, ft8_coh_drift* d_drift_out, void* stream) {
   if (c) c->replay_ok = c->snr_ok = false;
   if (!c || !p || n < 0 || n_slots < 0 || n_samples < 0 || slot_stride < n_samples ||
       (n > 0 && (!d_samples || !d_cand || !d_slot_of || !d_llr_out || !d_fit_out)))
     return fail(c, FT8_E_ARG, "bad argument");
   if (p->steps_per_symbol <= 0 || p->bins_per_tone <= 0) return fail(c, FT8_E_ARG, "bad oversampling factors");
+  int rc = check_coherent_drift(c, max_rate_hz_per_s, n_rates);
+  if (rc) return rc;
   DeviceGuard dg(c->device);
   CohLaunch L;
-  int rc = coherent_setup(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, &L);
+  rc = coherent_setup(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, &L);
   if (rc) return rc;
   if (n == 0) return FT8_OK;
   L.cand = d_cand;
@@ -1575,7 +1612,12 @@ int ft8_coherent_llr(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   L.llr = d_llr_out;
   L.fit = d_fit_out;
   hipStream_t s = (hipStream_t)stream;
-  const hipError_t e = launch_coherent(L, s);
+  const CohDrift G{max_rate_hz_per_s, n_rates, d_drift_out};
+  if (!coherent_drift_on(G) && d_drift_out) {  // off: the plain kernel, and zeros in the drift records
+    const hipError_t e = hipMemsetAsync(d_drift_out, 0, sizeof(ft8_coh_drift) * (size_t)n, s);
+    if (e != hipSuccess) return hipfail(c, e, "memset");
+  }
+  const hipError_t e = launch_coherent(L, G, s);
   return e == hipSuccess ? FT8_OK : hipfail(c, e, "coherent launch");
 }
 

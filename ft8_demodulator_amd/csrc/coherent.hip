@@ -8,6 +8,8 @@
 //     1. baseband: the samples around the candidate are mixed down to the centre of the 8-tone band
 //        and box-car decimated to Q samples per symbol (D = nsps / Q input samples each) -- the
 //        arithmetic of k_sub_est's phase 2 (subtract.hip): a D-entry twiddle table, two fmas per sample;
+//    1b. drift (ft8_set_coherent_drift / ft8_coherent_drift_llr only): the baseband is de-chirped in
+//        place by each of n_rates linear drift rates and step 2 repeated; the best rate's copy goes on;
 //     2. sync: over start offsets of +-hop/2 (steps of D samples) and tone-0 offsets of +-bin/2 (5
 //        points) the 21 Costas symbols are correlated (coherent within a symbol, power summed over the
 //        symbols that lie inside the slot); first largest wins, the tone-0 offset refined by a parabola;
@@ -82,9 +84,24 @@ __device__ void coh_blank(double* llr, ft8_coh_fit* fit, int status) {
   }
 }
 
-template <typename InT>
-__global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a) {
+// lane-owned elements of z in the drift search: ceil(max Mz / 256), Mz = 79 Q + 2 (Mt + 1), Mt <= Q / 2
+constexpr int kCohOwn = (kSymbols * kCohMaxQ + 2 * (kCohMaxQ / 2 + 1) + kCohThreads - 1) / kCohThreads;
+
+// Drift: step 1b of the contract, the sync of phase 2 repeated over n_rates de-chirped copies of z.
+// The copies are made in place: z goes from rate i to i + 1 by one complex multiply per element with
+// exp(-i pi (r_{i+1} - r_i) tau_m^2), a factor that is the same for every i (the rates are equidistant)
+// and that each lane keeps in registers for the elements it owns; only the running best and its two
+// tone-0 neighbours are kept, and one more rotation takes z to the winning rate before phase 3.
+// The drift kernels take the search's settings as a second argument (G = CohDrift); without it
+// (G empty) the kernel and its argument are the plain pass's.
+__device__ __forceinline__ CohDrift coh_drift_arg() { return CohDrift{}; }
+__device__ __forceinline__ CohDrift coh_drift_arg(const CohDrift& g) { return g; }
+
+template <typename InT, typename... G>
+__global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a, G... drift) {
   FT8_RACE_PROLOGUE();
+  constexpr bool Drift = sizeof...(G) != 0;
+  [[maybe_unused]] const CohDrift g = coh_drift_arg(drift...);
   // dynamic LDS: z in rows of Q + 1 (row r + 1 holds z[1 + r Q .. 1 + (r + 1) Q), r = -1 .. 81: the
   // layout of k_sub_est, whose bank arithmetic it keeps), the D twiddles of phase 1, the rotation
   // table [5 * 8][Q + 1] of phase 2 (phase 3 rebuilds its first 8 rows for the refined offset)
@@ -98,6 +115,8 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a) {
   __shared__ double s_sum[16];
   __shared__ double s_bc;
   __shared__ int s_flag, s_best;
+  __shared__ float s_win[3];  // Drift: the winning metric between its two tone-0 neighbours
+  __shared__ int s_rate;      // Drift: the winning rate index
 
   // list position -> (slot, candidate).  Per-slot lists: a slot's positions on one XCD (workgroup id
   // % 8, as k_sub_est), so its samples are served from that XCD's L2
@@ -118,6 +137,8 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a) {
   ft8_coh_fit* fit_out = a.fit + pos;
   if (slot < 0 || slot >= a.n_slots) {
     coh_blank(llr_out, fit_out, 3);
+    if constexpr (Drift)
+      if (g.out && threadIdx.x == 0) g.out[pos] = ft8_coh_drift{};
     return;
   }
   const InT* x = reinterpret_cast<const InT*>(a.x) + (int64_t)slot * a.slot_stride;
@@ -148,6 +169,8 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a) {
   __syncthreads();
   if (!s_flag) {
     coh_blank(llr_out, fit_out, 2);
+    if constexpr (Drift)
+      if (g.out && threadIdx.x == 0) g.out[pos] = ft8_coh_drift{};
     return;
   }
 
@@ -216,42 +239,98 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a) {
 
   // ---- 2. sync: item (start offset d, tone-0 offset j, Costas block b) sums its 7 symbols' powers in
   // symbol order; window element q of symbol k at offset d is z[1 + k Q + d + q]
-  for (int e = threadIdx.x; e < nT * kCohNF * 3; e += kCohThreads) {
-    const int d = e / (kCohNF * 3), r = e - d * (kCohNF * 3);
-    const int j = r / 3, b = r - 3 * j;
-    float sum = 0.f;
-    for (int i = 0; i < 7; ++i) {
-      const int k = 36 * b + i;
-      if (!present(d, k)) continue;
-      const float2* Wp = s_R + (j * 8 + costas_tone(i)) * (Q + 1);
-      const float2* zp = s_z + (k + 1) * (Q + 1);
-      float cx = 0.f, cy = 0.f;
-      for (int q = 0; q < Q; ++q) {
-        const int jj = d + q;  // < 3 Q: the row padding without a division
-        const float2 z = zp[jj + (jj >= Q) + (jj >= 2 * Q)], W = Wp[q];
-        cx = fmaf(z.x, W.x, fmaf(-z.y, W.y, cx));
-        cy = fmaf(z.x, W.y, fmaf(z.y, W.x, cy));
+  // Drift (step 1b of the contract): the rates r_i = (i - ic) rstep, i ascending, each searched as
+  // below on z de-chirped in place; tau_m is the centre of decimation block m relative to the centre of
+  // the nominal signal.  A lane owns z[tid + 256 u], as in phase 1.
+  const int R = Drift ? g.n_rates : 1, ic = (R - 1) / 2;
+  const double rstep = Drift ? 2.0 * (double)g.max_rate / (double)(R - 1) : 0.0;
+  auto tau2 = [&](int m) {
+    const double t = (((double)(m - Mg) + 0.5) * (double)D - 39.5 * (double)nsps) / fs;
+    return t * t;
+  };
+  int zi[kCohOwn];     // the element's word in s_z, -1 past Mz
+  float2 wr[kCohOwn];  // exp(-i pi rstep tau^2) from its exact phase
+  auto rotate = [&](auto factor) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < kCohOwn; ++u)
+      if (zi[u] >= 0) {
+        const float2 z = s_z[zi[u]], w = factor(u);
+        s_z[zi[u]] = make_float2(z.x * w.x - z.y * w.y, z.x * w.y + z.y * w.x);
       }
-      sum += cx * cx + cy * cy;
+  };
+  // by dr Hz/s, the factor from its exact phase
+  auto rotate_exact = [&](double dr) __attribute__((always_inline)) {
+    rotate([&](int u) { return rot_of(0.5 * dr * tau2(threadIdx.x + u * kCohThreads)); });
+  };
+  if constexpr (Drift) {
+#pragma unroll
+    for (int u = 0; u < kCohOwn; ++u) {
+      const int m = threadIdx.x + u * kCohThreads;
+      zi[u] = m < Mz ? z_at(m) : -1;
+      wr[u] = rot_of(0.5 * rstep * tau2(m));
     }
-    s_part[e] = sum;
+    rotate_exact((double)(-ic) * rstep);
+    __syncthreads();
   }
+  int ri = 0;
+  do {  // one trip without Drift
+    if constexpr (Drift)
+      if (ri > 0) {
+        rotate([&](int u) { return wr[u]; });
+        __syncthreads();
+      }
+    for (int e = threadIdx.x; e < nT * kCohNF * 3; e += kCohThreads) {
+      const int d = e / (kCohNF * 3), r = e - d * (kCohNF * 3);
+      const int j = r / 3, b = r - 3 * j;
+      float sum = 0.f;
+      for (int i = 0; i < 7; ++i) {
+        const int k = 36 * b + i;
+        if (!present(d, k)) continue;
+        const float2* Wp = s_R + (j * 8 + costas_tone(i)) * (Q + 1);
+        const float2* zp = s_z + (k + 1) * (Q + 1);
+        float cx = 0.f, cy = 0.f;
+        for (int q = 0; q < Q; ++q) {
+          const int jj = d + q;  // < 3 Q: the row padding without a division
+          const float2 z = zp[jj + (jj >= Q) + (jj >= 2 * Q)], W = Wp[q];
+          cx = fmaf(z.x, W.x, fmaf(-z.y, W.y, cx));
+          cy = fmaf(z.x, W.y, fmaf(z.y, W.x, cy));
+        }
+        sum += cx * cx + cy * cy;
+      }
+      s_part[e] = sum;
+    }
+    __syncthreads();
+    for (int h = threadIdx.x; h < nT * kCohNF; h += kCohThreads)
+      s_metric[h] = (s_part[3 * h] + s_part[3 * h + 1]) + s_part[3 * h + 2];
+    __syncthreads();
+    if (threadIdx.x == 0) {  // the first largest, start offset outer, tone-0 offset inner
+      int b = 0;
+      for (int h = 1; h < nT * kCohNF; ++h)
+        if (s_metric[h] > s_metric[b]) b = h;
+      if constexpr (!Drift) {
+        s_best = b;
+      } else if (ri == 0 || s_metric[b] > s_win[1]) {  // ... and the rate outermost
+        s_win[0] = b > 0 ? s_metric[b - 1] : 0.f;
+        s_win[1] = s_metric[b];
+        s_win[2] = b + 1 < nT * kCohNF ? s_metric[b + 1] : 0.f;
+        s_best = b;
+        s_rate = ri;
+      }
+    }
+    // Drift: thread 0 reads s_metric before it arrives at the next trip's barriers, and until then the
+    // others write only s_z and s_part
+  } while (Drift && ++ri < R);
   __syncthreads();
-  for (int h = threadIdx.x; h < nT * kCohNF; h += kCohThreads)
-    s_metric[h] = (s_part[3 * h] + s_part[3 * h + 1]) + s_part[3 * h + 2];
-  __syncthreads();
-  if (threadIdx.x == 0) {  // the first largest, start offset outer, tone-0 offset inner
-    int b = 0;
-    for (int h = 1; h < nT * kCohNF; ++h)
-      if (s_metric[h] > s_metric[b]) b = h;
-    s_best = b;
+  if constexpr (Drift) {
+    // z stands at rate R - 1; phase 3's barrier after its table orders this before the spectra
+    if (s_rate != R - 1) rotate_exact((double)(s_rate - (R - 1)) * rstep);
   }
-  __syncthreads();
   const int hb = s_best;
   const int db = hb / kCohNF, jb = hb - db * kCohNF;
   double delta = 0.0;
   if (jb > 0 && jb < kCohNF - 1) {
-    const double m_ = s_metric[hb - 1], m0 = s_metric[hb], mp = s_metric[hb + 1];
+    const double m_ = Drift ? s_win[0] : s_metric[hb - 1], m0 = Drift ? s_win[1] : s_metric[hb],
+                 mp = Drift ? s_win[2] : s_metric[hb + 1];
     const double den = m_ - 2.0 * m0 + mp;
     if (den < 0.0) delta = 0.5 * (m_ - mp) / den;
   }
@@ -338,12 +417,19 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a) {
     ft8_coh_fit f{};
     f.dt_s = (float)((double)(db - Mt) * (double)D / fs);
     f.df_hz = (float)df;
-    f.metric = s_metric[hb];
+    f.metric = Drift ? s_win[1] : s_metric[hb];
     f.n_sync = (uint8_t)ns;
     f.status = valid ? 0 : 2;
     f.dt_index = (int8_t)(db - Mt);
     f.df_index = (uint8_t)jb;
     *fit_out = f;
+    if constexpr (Drift)
+      if (g.out) {
+        ft8_coh_drift w;
+        w.rate_hz_per_s = (float)((double)(s_rate - ic) * rstep);
+        w.rate_index = s_rate;
+        g.out[pos] = w;
+      }
   }
 }
 
@@ -357,7 +443,9 @@ __global__ __launch_bounds__(4 * kWave) void k_coh_merge(CohPass a) {
   if (j >= r.count[slot]) return;
   const ft8_result& got = a.res_c[pos];
   if (!got.ok || a.fit[pos].status != 0) return;
-  if (lane == 0) retry_accept(r.res + (int64_t)slot * r.N + r.list[pos], got, 2);
+  // a.drift (null without the drift search): a rescue at a rate other than 0 also sets bit 2
+  const int bits = a.drift && a.drift[pos].rate_hz_per_s != 0.f ? 6 : 2;
+  if (lane == 0) retry_accept(r.res + (int64_t)slot * r.N + r.list[pos], got, bits);
 }
 
 }  // namespace
@@ -367,10 +455,15 @@ size_t coherent_lds_bytes(int nsps, int Q) {
   return sizeof(float2) * ((size_t)coh_z_words(Q) + (size_t)((D + 1) & ~1) + (size_t)coh_rot_words(Q));
 }
 
-hipError_t launch_coherent(const CohLaunch& a, hipStream_t s) {
+hipError_t launch_coherent(const CohLaunch& a, const CohDrift& g, hipStream_t s) {
   const int64_t grid = a.slot_of ? (int64_t)a.n : (int64_t)((a.n_slots + 7) / 8) * 8 * a.M;
   if (grid <= 0) return hipSuccess;
   const size_t lds = coherent_lds_bytes(a.nsps, a.Q);
+  if (coherent_drift_on(g)) {
+    if (a.dtype == FT8_I16)
+      return lds_launch(k_coherent<int16_t, CohDrift>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a, g);
+    return lds_launch(k_coherent<float, CohDrift>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a, g);
+  }
   if (a.dtype == FT8_I16) return lds_launch(k_coherent<int16_t>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a);
   return lds_launch(k_coherent<float>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a);
 }

@@ -306,7 +306,7 @@ __device__ inline int slot_count(const RetryLists& r, int slot) {
 // in candidate order; count = min(found, M)
 hipError_t launch_retry_list(const RetryLists& r, hipStream_t s);
 // an accepted attempt `got` rewrites the record it retried; pass_bits: (h + 1) << 4 for AP hypothesis
-// h, 2 for the coherent pass
+// h, 2 for the coherent pass (6 at a drift rate other than 0)
 __device__ inline void retry_accept(ft8_result* rec, const ft8_result& got, int pass_bits) {
   ft8_result w = *rec;
   w.ok = 1;
@@ -355,14 +355,23 @@ struct CohLaunch {
   double* llr;                 // [positions][174]
   ft8_coh_fit* fit;            // [positions]
 };
+// the drift search (ft8hip.h, step 1b): on when n_rates > 1 and max_rate > 0.  Its kernels are
+// instantiations of their own and take this as a second argument; k_coherent's argument stays CohLaunch.
+struct CohDrift {
+  float max_rate;              // Hz/s
+  int n_rates;                 // odd, <= 33
+  ft8_coh_drift* out;          // nullable [positions]
+};
+inline bool coherent_drift_on(const CohDrift& g) { return g.n_rates > 1 && g.max_rate > 0.f; }
 size_t coherent_lds_bytes(int nsps, int Q);   // k_coherent's dynamic LDS
-hipError_t launch_coherent(const CohLaunch& a, hipStream_t s);
+hipError_t launch_coherent(const CohLaunch& a, const CohDrift& g, hipStream_t s);
 // The coherent retry inside ft8_decode_batch: the list (M = the per-slot cap), k_coherent -> fit and
 // the LLRs, launch_bp -> res_c, k_coh_merge.
 struct CohPass {
   RetryLists r;
   const ft8_coh_fit* fit;      // k_coherent's fits of the lists
   const ft8_result* res_c;     // launch_bp's records of them
+  const ft8_coh_drift* drift;  // null without the drift search: the winning rates of the lists
 };
 hipError_t launch_coh_merge(const CohPass& a, hipStream_t s);
 

@@ -51,12 +51,13 @@ def read_wave_file(wave_path: str, verbose: bool = False) -> tuple:
 
 
 def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_errors: int = None, coherent=None,
-                 device=None, verbose: bool = False, **decode_kw) -> tuple:
+                 coherent_drift=None, device=None, verbose: bool = False, **decode_kw) -> tuple:
     """One file, any PCM width, as one slot through _pipeline.decode_one -> (results, snr_db, patterns)
     and, with coherent, a fourth entry.  snr_db (with snr, else None): one SNR in 2500 Hz per result.
     patterns (with ap, else None): per result the a-priori pattern that rescued it, None for a plain
     decode.  fits (with coherent): per result (dt_s, df_hz) of the coherent fit that rescued it (one
-    ft8_coherent_llr call for those records), None for any other decode."""
+    ft8_coherent_llr call for those records), None for any other decode; with coherent_drift
+    (True or (max_rate, n_rates)) the fit is (dt_s, df_hz, rate_hz_per_s)."""
     import torch
     from . import _lib
     from ._pipeline import decode_one
@@ -73,19 +74,19 @@ def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_erro
         x, code = torch.from_numpy(h).to(dev), _lib.FT8_F32
     ap = None if ap is None else tuple(ap)
     results, reports, recs = decode_one(x, code, sample_rate, snr=snr, ap=ap, ap_max_hard_errors=ap_max_hard_errors,
-                                        coherent=coherent, **decode_kw)
+                                        coherent=coherent, coherent_drift=coherent_drift, **decode_kw)
     out = (results, snr_db_or_nan(reports) if snr else None,
            None if ap is None else [ap[ap_index(r) - 1] if ap_index(r) else None for r in recs])
     if coherent is None:
         return out
-    return out + (_coherent_fits(x, code, sample_rate, recs, decode_kw),)
+    return out + (_coherent_fits(x, code, sample_rate, recs, decode_kw, coherent_drift),)
 
 
-def _coherent_fits(x, code, sample_rate, recs, decode_kw):
+def _coherent_fits(x, code, sample_rate, recs, decode_kw, drift=None):
     """(dt_s, df_hz) of every record the coherent pass rescued (the stage call on those candidates), None
-    for the others."""
+    for the others; with the drift search (True or (max_rate, n_rates)) also the winning rate in Hz/s."""
     from ._pipeline import make_plan
-    from .coherent import coherent_index
+    from .coherent import DEFAULT_DRIFT, coherent_index
     from .ldpc_decoder import coherent_llr_batch
     fits = [None] * len(recs)
     idx = [i for i, r in enumerate(recs) if coherent_index(r)]
@@ -94,9 +95,15 @@ def _coherent_fits(x, code, sample_rate, recs, decode_kw):
         plan = make_plan(int(x.shape[0]), sample_rate, bpt, sps, decode_kw.get("freq_min"), decode_kw.get("freq_max"),
                          decode_kw.get("time_min"), decode_kw.get("time_max"))
         cand = [(int(recs[i]["abs_time"]), int(recs[i]["abs_freq"])) for i in idx]
-        _, f = coherent_llr_batch(x, cand, [0] * len(idx), sample_rate, bpt, sps, plan.t_lo, plan.f_lo, code=code)
-        for i, fi in zip(idx, f):
-            fits[i] = (float(fi["dt_s"]), float(fi["df_hz"]))
+        if drift is None or drift is False:
+            _, f = coherent_llr_batch(x, cand, [0] * len(idx), sample_rate, bpt, sps, plan.t_lo, plan.f_lo, code=code)
+            for i, fi in zip(idx, f):
+                fits[i] = (float(fi["dt_s"]), float(fi["df_hz"]))
+        else:
+            _, f, g = coherent_llr_batch(x, cand, [0] * len(idx), sample_rate, bpt, sps, plan.t_lo, plan.f_lo, code=code,
+                                         drift=DEFAULT_DRIFT if drift is True else drift)
+            for i, fi, gi in zip(idx, f, g):
+                fits[i] = (float(fi["dt_s"]), float(fi["df_hz"]), float(gi["rate_hz_per_s"]))
     return fits
 
 
@@ -150,7 +157,8 @@ def _print_results(results, text: bool = False, snr=None, ap=None, coherent=None
     """text: one extra `Message:` line per result, the payload unpacked to message text.  snr (one
     value per result): one extra `SNR:` line per result, dB in 2500 Hz.  ap (one pattern or None per
     result): one extra `AP: <pattern>` line for every a-priori decode.  coherent (one (dt_s, df_hz) or
-    None per result): one extra `Coherent:` line for every decode from the coherent LLRs."""
+    None per result): one extra `Coherent:` line for every decode from the coherent LLRs; a third entry
+    (the drift search's rate, Hz/s) ends the line with `, drift +0.50 Hz/s`."""
     if not results:
         print("No FT8 messages decoded")
         return
@@ -172,7 +180,8 @@ def _print_results(results, text: bool = False, snr=None, ap=None, coherent=None
         if ap is not None and ap[k] is not None:
             print(f"AP: {ap[k]}")
         if coherent is not None and coherent[k] is not None:
-            print(f"Coherent: dt {coherent[k][0] * 1e3:+.2f} ms, df {coherent[k][1]:+.2f} Hz")
+            drift = f", drift {coherent[k][2]:+.2f} Hz/s" if len(coherent[k]) > 2 else ""
+            print(f"Coherent: dt {coherent[k][0] * 1e3:+.2f} ms, df {coherent[k][1]:+.2f} Hz{drift}")
         print(f"CRC check: {status.crc_calculated}")
         print(f"LDPC errors: {status.ldpc_errors}")
         print("-" * 50)
@@ -196,6 +205,13 @@ def _decode_many(paths, correction, kw):
         for i, r in zip(idx, res):
             out[i] = r
     return out
+
+
+def _drift_arg(text: str):
+    """--coherent-drift MAX[:N] -> (MAX Hz/s, N rates); N defaults to 9."""
+    from .coherent import DEFAULT_DRIFT
+    a, _, n = text.partition(":")
+    return float(a), int(n) if n else DEFAULT_DRIFT[1]
 
 
 def main(argv=None):
@@ -222,8 +238,14 @@ def main(argv=None):
     parser.add_argument("--coherent", nargs="?", type=int, const=-1, default=None, metavar="N",
                         help="demodulate the N best-scoring failed candidates again coherently from the samples "
                              "(default 32, 0: all; such a decode is marked with its fit's time and frequency offset)")
+    parser.add_argument("--coherent-drift", nargs="?", type=_drift_arg, const=True, default=None, metavar="MAX[:N]",
+                        help="with --coherent: also search N (odd, at most 33) linear frequency drift rates over "
+                             "+-MAX Hz/s (at most 4) for each of those candidates (default 1.0:9; the decode's "
+                             "mark then carries the rate)")
     args = parser.parse_args(argv)
     coherent = None if args.coherent is None else (True if args.coherent < 0 else args.coherent)
+    if args.coherent_drift is not None and coherent is None:
+        parser.error("--coherent-drift needs --coherent")
     paths = args.wave_file
     for path in paths:
         if not os.path.exists(path):
@@ -240,6 +262,8 @@ def main(argv=None):
             decode_ft8_from_wave(paths[0], correction=True)  # raises as without the flags
         if coherent is not None:
             kw = dict(kw, coherent=coherent)
+        if args.coherent_drift is not None:
+            kw = dict(kw, coherent_drift=args.coherent_drift)
         decoded = (_decode_file(path, snr=args.snr, ap=args.ap, ap_max_hard_errors=args.ap_max_hard_errors, **kw)
                    for path in paths)
     elif many:

@@ -132,8 +132,10 @@ def _pulse(nsps: int, bt: float = 2.0, device=None) -> torch.Tensor:
     return 0.5 * (torch.special.erf(k * bt * (t + 0.5)) - torch.special.erf(k * bt * (t - 0.5)))
 
 
-def gfsk_waveforms(tones: torch.Tensor, fs: int, f0: torch.Tensor) -> torch.Tensor:
-    """tones [B, 79] (int), f0 [B] Hz -> real unit-amplitude waveforms [B, 79*nsps] float64."""
+def gfsk_waveforms(tones: torch.Tensor, fs: int, f0: torch.Tensor, drift_hz_per_s=None) -> torch.Tensor:
+    """tones [B, 79] (int), f0 [B] Hz -> real unit-amplitude waveforms [B, 79*nsps] float64.
+    drift_hz_per_s (a scalar or [B], Hz/s; None: no drift): a linear frequency drift r, added to the
+    instantaneous frequency about the waveform's centre: f(t) = f0 + tone + r (t - t_c)."""
     B, nsym = tones.shape
     dev = tones.device
     nsps = int(0.16 * fs)
@@ -152,6 +154,11 @@ def gfsk_waveforms(tones: torch.Tensor, fs: int, f0: torch.Tensor) -> torch.Tens
     dphi = dphi_peak * blocks.reshape(B, -1) + (2.0 * math.pi / fs) * f0.to(torch.float64)[:, None]
     n = nsym * nsps
     steps = dphi[:, nsps:nsps + n - 1]
+    if drift_hz_per_s is not None:
+        r = torch.as_tensor(drift_hz_per_s, dtype=torch.float64, device=dev).expand(B)
+        # the step from sample k to k + 1 carries the frequency at its middle
+        t = (torch.arange(n - 1, dtype=torch.float64, device=dev) + 0.5 - 0.5 * n) / fs
+        steps = steps + (2.0 * math.pi / fs) * r[:, None] * t[None, :]
     phi = torch.cat([torch.zeros(B, 1, dtype=torch.float64, device=dev), torch.cumsum(steps, 1)], 1)
     sig = torch.sin(torch.remainder(phi, 2.0 * math.pi))
     nramp = nsps // 8
@@ -172,13 +179,20 @@ class SlotTruth:
 
 def make_slots(n_slots: int, n_signals: int, fs: int = 12000, snr_db=(-24.0, -10.0),
                f0_range=(200.0, 2800.0), start_range=(0.0, 2.0), seed: int = 0,
-               device="cpu", slot_s: float = 15.0, noise: bool = True, seeds=None):
+               device="cpu", slot_s: float = 15.0, noise: bool = True, seeds=None, drift_hz_per_s=None):
     """-> (samples float32 [n_slots, int(slot_s*fs)], list[SlotTruth]).
 
     Slot b uses np.random.default_rng(seeds[b] if seeds else seed + b) for its parameters and a
     torch generator with the same seed for its noise, so slots are reproducible individually.
+    drift_hz_per_s (a scalar or one value per signal of a slot, Hz/s; None: no drift, and no other
+    output changes): every signal's linear frequency drift (gfsk_waveforms); it draws nothing from the
+    generators.  CPU synthesis only: the device's transmit chain has no drift.
     """
     N = int(slot_s * fs)
+    if drift_hz_per_s is not None:
+        if torch.device(device).type == "cuda":
+            raise NotImplementedError("make_slots: drift_hz_per_s is synthesised on the CPU only")
+        drift_hz_per_s = np.array(np.broadcast_to(np.asarray(drift_hz_per_s, dtype=np.float64), (n_signals,)))
     if torch.device(device).type == "cuda":
         return _make_slots_gpu(n_slots, n_signals, fs, snr_db, f0_range, start_range, seed, device, N, noise, seeds)
     out = torch.empty(n_slots, N, dtype=torch.float32, device=device)
@@ -198,7 +212,8 @@ def make_slots(n_slots: int, n_signals: int, fs: int = 12000, snr_db=(-24.0, -10
                else torch.zeros(N, dtype=torch.float64, device=device))
         if n_signals:
             tones = torch.as_tensor(np.stack([itones(p) for p in pays]), device=device)
-            wav = gfsk_waveforms(tones, fs, torch.as_tensor(f0, device=device))
+            wav = gfsk_waveforms(tones, fs, torch.as_tensor(f0, device=device),
+                                 None if drift_hz_per_s is None else torch.as_tensor(drift_hz_per_s, device=device))
             amp = torch.as_tensor(np.sqrt(2.0 * 10.0 ** (snr / 10.0)), device=device)
             wav *= amp[:, None]
             n = 79 * nsps

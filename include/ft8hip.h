@@ -89,7 +89,8 @@ typedef struct ft8_params {
  *                      from the samples ("coherent re-demodulation" below; ft8_set_coherent caps them per
  *                      slot), and decodes the new LLRs.  Rescued candidates come out in candidate order
  *                      among the plain decodes with pass_index bit 1 set.  F32 and I16 samples only; not
- *                      with FT8_FLAG_SUBTRACT. */
+ *                      with FT8_FLAG_SUBTRACT.  ft8_set_coherent_drift adds a search over linear
+ *                      frequency drift to it (off by default). */
 #define FT8_FLAG_TOPK 1
 #define FT8_FLAG_SUBTRACT 2
 #define FT8_FLAG_AP 4
@@ -109,6 +110,7 @@ typedef struct ft8_result {
   uint8_t ok;              /* 1: LDPC converged and CRC matched (ft8_decode_candidate True) */
   uint8_t pass_index;      /* low nibble bit 0: 0 decoded from the slot, 1 decoded after subtraction (FT8_FLAG_SUBTRACT);
                               bit 1: decoded from the coherent LLRs (FT8_FLAG_COHERENT);
+                              bit 2: ... at a drift rate other than 0 (ft8_set_coherent_drift);
                               high nibble 0: plain BP; h + 1: a-priori hypothesis h (FT8_FLAG_AP, ft8_ap_decode) */
 } ft8_result;
 
@@ -438,6 +440,39 @@ int ft8_coherent_llr(ft8_ctx* ctx, const void* d_samples, int dtype, int64_t n_s
  * together with FT8_FLAG_SUBTRACT.  Scratch (context-owned, grow-only) per listed candidate: 174 * 8
  * bytes of LLRs and 76 bytes of lists, fits and records.  max_per_slot < 0: FT8_E_ARG.  Default 0. */
 int ft8_set_coherent(ft8_ctx* ctx, int32_t max_per_slot);
+
+/* ---- coherent re-demodulation with a search over linear frequency drift ----------------------------
+ * Opt-in and build-defined like the pass itself; coherent.py: coherent_restate(drift=...) restates it.
+ * A signal whose frequency runs as f(t) = f_c + r (t - t_c) about its centre t_c (r in Hz/s) smears over
+ * the tone filters of steps 3 and 4 above.  With n_rates = R (odd, 1 <= R <= 33) and max_rate = A
+ * (0 <= A <= 4.0 Hz/s) one step is added between steps 1 and 2:
+ *   1b. de-chirp  rates r_i = (i - (R - 1) / 2) * 2 A / (R - 1), i = 0 .. R - 1;
+ *                 z_i[m] = z[m] exp(-i pi r_i tau_m^2), tau_m = ((m - Mg + 0.5) D - 39.5 nsps) / fs: the
+ *                 centre of decimation block m relative to the centre of the nominal signal (the phase
+ *                 formed in double, reduced mod 1 cycle before it is rounded to float32).
+ *   3.  sync      metric(i, dt, j) is step 3's metric on z_i; i outer, then dt, then j, all ascending;
+ *                 the first largest wins.  The parabola in j is applied at the winning (i, dt); the rate
+ *                 is not refined.
+ *   4.  LLRs      unchanged, on z_i of the winning rate, so df_hz is the offset at the signal's centre.
+ * R = 1 or A = 0: off, exactly the pass above.  The device rotates z in place from one rate to the next
+ * (float32, one factor per element, the same for every step) and once more to the winner. */
+typedef struct ft8_coh_drift {
+  float   rate_hz_per_s;  /* r_i of the winning rate */
+  int32_t rate_index;     /* i */
+} ft8_coh_drift; /* 8 bytes */
+
+/* ft8_coherent_llr with the drift search: d_drift_out[n] (may be NULL) receives the winning rates, zeros
+ * where no sync was made (status 3, and status 2 for want of a sync symbol).  n_rates = 1 or max_rate = 0 writes exactly the bytes of ft8_coherent_llr and zeros
+ * in the drift records.  FT8_E_ARG for an even n_rates, n_rates outside [1, 33], max_rate outside [0, 4]. */
+int ft8_coherent_drift_llr(ft8_ctx* ctx, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
+                           int64_t slot_stride, const ft8_params* p, const int32_t* d_cand,
+                           const int32_t* d_slot_of, int32_t n, float max_rate_hz_per_s, int32_t n_rates,
+                           double* d_llr_out, ft8_coh_fit* d_fit_out, ft8_coh_drift* d_drift_out, void* stream);
+/* The drift search inside FT8_FLAG_COHERENT (a context setting like ft8_set_coherent; default off: 0, 1).
+ * A record rescued at a winning rate other than 0 gets pass_index |= 4 on top of |= 2; the rate itself is
+ * not carried in ft8_result (the stage call gives it).  The pass's scratch grows by 8 bytes per listed
+ * candidate.  Errors as for the stage call. */
+int ft8_set_coherent_drift(ft8_ctx* ctx, float max_rate_hz_per_s, int32_t n_rates);
 
 /* Per-slot flags of the last selection (copied device->device into d_out[n_slots]):
  * bit 0: an exact score tie reached a heap comparison (the reference raises TypeError there,

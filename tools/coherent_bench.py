@@ -12,6 +12,10 @@
           whose transmitted message is decoded -- plain, coherent, coherent + AP "CQ ? ?" (top-K
           selection, K = 40, min_score 2)
   noise   256 noise-only slots at K = 300: decodes (false by construction) with coherent = 32 and 0
+  drift   (--drift, or --legs drift) the drift search (ft8_set_coherent_drift): the fraction of one-signal slots
+          decoded over the drift rate at two SNRs -- plain, coherent, coherent with the search (top-K,
+          K = 40, min_score 2); decodes on the noise-only slots with the search on; k_coherent ms per launch
+          at 1, 9, 17 and 33 rates for M = 8 and 32; the step with coherent = 8 and 32, search off and (1.0, 9)
 
 Prints one JSON line and writes it to --out.  Needs a GPU; there is no CPU fallback.
 """
@@ -150,9 +154,118 @@ def leg_noise(torch, dev, args):
     return out
 
 
+DRIFT_RATES = (0.0, 0.25, -0.25, 0.5, -0.5, 0.75, -0.75, 1.0, -1.0, 1.5, -1.5)   # Hz/s
+DRIFT_KERNEL_RATES = (1, 9, 17, 33)
+DRIFT_STEP = (1.0, 9)
+
+
+def _timed_launches(torch, launch, steps, warmup):
+    for _ in range(warmup):
+        launch()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
+    ev[0].record()
+    for i in range(steps):
+        launch()
+        ev[i + 1].record()
+    torch.cuda.synchronize()
+    ms = np.array([ev[i].elapsed_time(ev[i + 1]) for i in range(steps)])
+    return {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max())}
+
+
+def leg_drift(torch, dev, args):
+    from ft8_demodulator_amd import SlotDecoder, _lib, coherent, synth
+    from ft8_demodulator_amd._pipeline import make_params, make_plan
+    search = (float(args.drift_search.split(":")[0]), int(args.drift_search.split(":")[1]))
+    kw = dict(max_candidates=40, min_score=2, max_iterations=20, flags=_lib.FT8_FLAG_TOPK)
+    decs = (("plain", SlotDecoder(FS, 2, 2, device=dev, context=_lib.Context(dev.index), **kw)),
+            ("coherent", SlotDecoder(FS, 2, 2, device=dev, context=_lib.Context(dev.index), coherent=True, **kw)),
+            ("coherent_drift", SlotDecoder(FS, 2, 2, device=dev, context=_lib.Context(dev.index), coherent=True,
+                                           coherent_drift=search, **kw)))
+    # ---- decode fractions: one signal per slot (synthesised on the CPU: the device's chain has no drift)
+    table = []
+    for k, snr in enumerate(args.drift_snrs):
+        for r in DRIFT_RATES:
+            x, truth = synth.make_slots(args.sweep_slots, 1, fs=FS, snr_db=float(snr),
+                                        seeds=[args.seed + 1000 * k + s for s in range(args.sweep_slots)],
+                                        drift_hz_per_s=r)
+            x = x.to(dev)
+            row = {"snr_db_full_band": float(snr), "snr_db_2500": float(snr + 10.0 * np.log10(FS / 2.0 / 2500.0)),
+                   "rate_hz_per_s": r}
+            for name, dec in decs:
+                recs = dec.records(x)
+                pay = [bytes(t.payloads[0]) for t in truth]
+                hit = sum(any(bytes(v["payload"]) == pay[s] for v in recs[s]) for s in range(len(recs)))
+                false = sum(sum(bytes(v["payload"]) != pay[s] for v in recs[s]) for s in range(len(recs)))
+                row[name] = {"decoded": hit, "fraction": hit / len(recs), "false": false}
+            table.append(row)
+    # ---- noise-only slots, the search on
+    g = torch.Generator(device=dev)
+    g.manual_seed(args.seed)
+    xn = torch.randn(args.slots, N, generator=g, device=dev, dtype=torch.float32)
+    recs = SlotDecoder(FS, 2, 2, device=dev, coherent=32, coherent_drift=search, **CFG3).records(xn)
+    noise = {"slots": args.slots, "search": search, "decodes": sum(len(s) for s in recs),
+             "drift_decodes": sum(int(sum(coherent.drift_index(r) for r in s)) for s in recs)}
+    # ---- k_coherent per launch over the number of rates, candidates listed as the in-batch launch lists them
+    x = crowded(args, dev)
+    S, K = args.slots, CFG3["max_candidates"]
+    ctx, L, st = _lib.Context(dev.index), _lib.lib(), _lib.stream_handle(dev)
+    plan = make_plan(N, FS)
+    p = make_params(plan, K, CFG3["min_score"], 20, _lib.FT8_FLAG_TOPK)
+    d_wf = torch.empty(S, plan.T, plan.F, dtype=torch.float32, device=dev)
+    ctx.check(L.ft8_stft(ctx.handle, _lib.ptr(x), _lib.FT8_F32, N, S, N, ctypes.byref(p), _lib.ptr(d_wf), st), "stft")
+    d_cand = torch.zeros(S, K, 2, dtype=torch.int32, device=dev)
+    d_score = torch.zeros(S, K, dtype=torch.float64, device=dev)
+    d_cnt = torch.zeros(S, dtype=torch.int32, device=dev)
+    ctx.check(L.ft8_sync_select(ctx.handle, _lib.ptr(d_wf), 0, S, plan.T, plan.F, ctypes.byref(p), _lib.ptr(d_cand),
+                                _lib.ptr(d_score), _lib.ptr(d_cnt), None, st), "select")
+    cand, cnt = d_cand.cpu().numpy(), d_cnt.cpu().numpy()
+    del d_wf
+    kernel = {}
+    for M in (8, 32):
+        w = np.arange(((S + 7) // 8) * 8 * M)
+        slot, j = (w % 8) + 8 * ((w // 8) // M), (w // 8) % M
+        keep = (slot < S) & (j < np.minimum(cnt[np.minimum(slot, S - 1)], M))
+        slot, j = slot[keep], j[keep]
+        n = len(slot)
+        d_c = torch.from_numpy(np.ascontiguousarray(cand[slot, j])).to(dev)
+        d_so = torch.from_numpy(slot.astype(np.int32)).to(dev)
+        d_llr = torch.empty(n, 174, dtype=torch.float64, device=dev)
+        d_fit = torch.empty(n * coherent.FIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_dr = torch.empty(n * coherent.DRIFT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        for R in DRIFT_KERNEL_RATES:
+            def launch():
+                ctx.check(L.ft8_coherent_drift_llr(ctx.handle, _lib.ptr(x), _lib.FT8_F32, N, S, N, ctypes.byref(p),
+                                                   _lib.ptr(d_c), _lib.ptr(d_so), n, 1.0, R, _lib.ptr(d_llr),
+                                                   _lib.ptr(d_fit), _lib.ptr(d_dr), st), "coherent drift")
+            kernel[f"M_{M}_R_{R}"] = dict(_timed_launches(torch, launch, args.steps, args.warmup), candidates=int(n))
+    # ---- the flagged step, search off and on, alternating on the crowded batch
+    names, sd = [], []
+    for m in (8, 32):
+        for d in (None, DRIFT_STEP):
+            names.append(f"coherent_{m}" + ("_drift" if d else ""))
+            sd.append(SlotDecoder(FS, 2, 2, device=dev, context=_lib.Context(dev.index), coherent=m, coherent_drift=d,
+                                  **CFG3))
+    times = timed_steps(torch, sd, x, args.steps, args.warmup)
+    step = {"search": DRIFT_STEP}
+    for name, dec, t in zip(names, sd, times):
+        recs = dec.records(x)
+        step[name] = dict(t, decodes=sum(len(s) for s in recs),
+                          rescued=sum(int(sum(coherent.coherent_index(r) for r in s)) for s in recs),
+                          rescued_drifting=sum(int(sum(coherent.drift_index(r) for r in s)) for s in recs),
+                          distinct_messages=sum(len({bytes(r["payload"]) for r in s}) for s in recs))
+    return {"search": search, "slots_per_cell": args.sweep_slots, "selection": "top-K, K = 40, min_score 2",
+            "table": table, "noise": noise, "kernel": kernel, "step": step}
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    p.add_argument("--legs", default="step,kernel,sweep,noise", help="comma-separated subset of step,kernel,sweep,noise")
+    p.add_argument("--legs", default="step,kernel,sweep,noise",
+                   help="comma-separated subset of step,kernel,sweep,noise,drift")
+    p.add_argument("--drift", action="store_true", help="the drift search's measurements only (--legs drift)")
+    p.add_argument("--drift-search", default="2.0:17", metavar="MAX:N",
+                   help="the search of the drift leg's decode fractions and noise slots")
+    p.add_argument("--drift-snrs", type=float, nargs=2, default=(-21.8, -13.8), metavar="DB",
+                   help="the two full-band SNRs of the drift leg's table (default: -18 and -10 dB in 2500 Hz)")
     p.add_argument("--slots", type=int, default=256)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
@@ -169,8 +282,8 @@ def main():
     dev = torch.device("cuda", 0)
     res = {"box": socket.gethostname(), "gpu": torch.cuda.get_device_name(0),
            "build_id": _lib.lib().ft8_build_id().decode()}
-    legs = {"step": leg_step, "kernel": leg_kernel, "sweep": leg_sweep, "noise": leg_noise}
-    for name in args.legs.split(","):
+    legs = {"step": leg_step, "kernel": leg_kernel, "sweep": leg_sweep, "noise": leg_noise, "drift": leg_drift}
+    for name in (["drift"] if args.drift else args.legs.split(",")):
         res[name] = legs[name](torch, dev, args)
     line = json.dumps(res)
     out = args.out if os.path.isabs(args.out) else os.path.join(ROOT, args.out)
