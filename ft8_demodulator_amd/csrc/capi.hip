@@ -931,37 +931,40 @@ int ap_pass(ft8_ctx* c, const RetryLists& failed, const double* llr, int slot0, 
   return FT8_OK;
 }
 
-// ---- coherent re-demodulation -------------------------------------------------------------------
-int sub_q(int nsps);
+// ---- the baseband front end of the subtraction and the coherent pass (baseband.h) ---------------
+// decimated samples per symbol: 32 when nsps allows, else the largest divisor of nsps in [8, 32]
+int sub_q(int nsps) {
+  for (int q = 32; q >= 8; --q)
+    if (nsps % q == 0) return q;
+  return 0;
+}
 
-// the geometry, dtype and LDS checks ft8_coherent_llr and FT8_FLAG_COHERENT share; fills the launch's
-// sample and geometry fields
-int coherent_setup(ft8_ctx* c, const void* x, int dtype, int64_t n_samples, int n_slots, int64_t slot_stride,
-                   const ft8_params* p, CohLaunch* L) {
+// the geometry and dtype checks both share (`who` opens their messages); fills the launch's samples
+// and geometry
+int baseband_setup(ft8_ctx* c, const void* x, int dtype, int64_t n_samples, int n_slots, int64_t slot_stride,
+                   const ft8_params* p, const char* who, Baseband* B) {
   Geo g;
   std::string why;
   int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
   if (rc) return fail(c, rc, why);
   if (dtype != FT8_F32 && dtype != FT8_I16)
-    return fail(c, FT8_E_UNSUPPORTED, "coherent re-demodulation needs float32 or int16 samples");
+    return fail(c, FT8_E_UNSUPPORTED, std::string(who) + " needs float32 or int16 samples");
   const int Q = sub_q(g.nperseg);
   if (Q == 0 || g.hop <= 0 || g.nperseg % g.hop != 0)
-    return fail(c, FT8_E_UNSUPPORTED, "coherent re-demodulation needs nsps with a divisor in [8, 32] and hop | nsps");
-  if (coherent_lds_bytes(g.nperseg, Q) > 64 * 1024)
-    return fail(c, FT8_E_RANGE, "coherent re-demodulation: the decimation's twiddle table does not fit 64 KB of LDS");
+    return fail(c, FT8_E_UNSUPPORTED, std::string(who) + " needs nsps with a divisor in [8, 32] and hop | nsps");
+  *B = Baseband{x, dtype, n_samples, slot_stride, n_slots, rate_of(p), g.nperseg, g.hop, g.nfft, p->t_lo, p->f_lo, Q};
+  return FT8_OK;
+}
+
+// ---- coherent re-demodulation -------------------------------------------------------------------
+// the checks ft8_coherent_llr and FT8_FLAG_COHERENT share; fills the launch's baseband
+int coherent_setup(ft8_ctx* c, const void* x, int dtype, int64_t n_samples, int n_slots, int64_t slot_stride,
+                   const ft8_params* p, CohLaunch* L) {
   *L = CohLaunch{};
-  L->x = x;
-  L->dtype = dtype;
-  L->n_samples = n_samples;
-  L->slot_stride = slot_stride;
-  L->n_slots = n_slots;
-  L->fs = rate_of(p);
-  L->nsps = g.nperseg;
-  L->hop = g.hop;
-  L->nfft = g.nfft;
-  L->t_lo = p->t_lo;
-  L->f_lo = p->f_lo;
-  L->Q = Q;
+  const int rc = baseband_setup(c, x, dtype, n_samples, n_slots, slot_stride, p, "coherent re-demodulation", &L->b);
+  if (rc) return rc;
+  if (coherent_lds_bytes(L->b.nsps, L->b.Q) > 64 * 1024)
+    return fail(c, FT8_E_RANGE, "coherent re-demodulation: the decimation's twiddle table does not fit 64 KB of LDS");
   return FT8_OK;
 }
 
@@ -1153,43 +1156,20 @@ int gfsk_tables(ft8_ctx* c, int nsps) {
   return FT8_OK;
 }
 
-// decimated samples per symbol of the subtraction's fine sync: 32 when nsps allows, else the
-// largest divisor of nsps in [8, 32]
-int sub_q(int nsps) {
-  for (int q = 32; q >= 8; --q)
-    if (nsps % q == 0) return q;
-  return 0;
-}
-
 int subtract_core(ft8_ctx* c, const void* x, int dtype, float* resid, int64_t n_samples, int n_slots,
                   int64_t x_stride, int64_t r_stride, const ft8_params* p, const ft8_result* res,
                   const int32_t* counts, int cap, hipStream_t s) {
-  Geo g;
-  std::string why;
-  int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
-  if (rc) return fail(c, rc, why);
-  if (dtype != FT8_F32 && dtype != FT8_I16) return fail(c, FT8_E_UNSUPPORTED, "subtraction needs float32 or int16 samples");
+  // FT8_FLAG_SUBTRACT, the one caller whose strides can differ, has passed the geometry and dtype checks
   if (x_stride != r_stride) return fail(c, FT8_E_ARG, "residual and sample strides differ");
+  SubLaunch L{};
+  int rc = baseband_setup(c, x, dtype, n_samples, n_slots, x_stride, p, "subtraction", &L.b);
+  if (rc) return rc;
+  L.b.fs = (double)(int)rate_of(p);  // SubLaunch.fs was an int: a fractional rate stays truncated here, bit for bit
   c->sub_slots = c->sub_cap = -1;  // no valid fits until this subtraction has been launched
-  const int Q = sub_q(g.nperseg);
-  if (Q == 0 || g.nperseg % g.hop != 0)
-    return fail(c, FT8_E_UNSUPPORTED, "subtraction needs nsps with a divisor in [8, 32] and hop | nsps");
-  if ((rc = gfsk_tables(c, g.nperseg))) return rc;
+  if ((rc = gfsk_tables(c, L.b.nsps))) return rc;
   if ((rc = ensure(c, c->sub_est, sub_est_bytes() * (size_t)n_slots * (size_t)(cap > 0 ? cap : 1)))) return rc;
   if ((rc = ensure(c, c->sub_list, sizeof(int32_t) * (size_t)n_slots * (size_t)(cap + 1)))) return rc;
-  SubLaunch L{};
-  L.x = x;
-  L.dtype = dtype;
   L.residual = resid;
-  L.n_samples = n_samples;
-  L.slot_stride = x_stride;
-  L.n_slots = n_slots;
-  L.fs = rate_of(p);
-  L.nsps = g.nperseg;
-  L.hop = g.hop;
-  L.nfft = g.nfft;
-  L.t_lo = p->t_lo;
-  L.f_lo = p->f_lo;
   L.res = res;
   L.counts = counts;
   L.cap = cap;
@@ -1197,7 +1177,6 @@ int subtract_core(ft8_ctx* c, const void* x, int dtype, float* resid, int64_t n_
   L.Pf = c->gfsk_Pf.as<const float>();
   L.est = c->sub_est.p;
   L.list = c->sub_list.as<int32_t>();
-  L.Q = Q;
   if ((rc = timed_launch(c, kSubEst, s, "subtract launch", [&] { return launch_sub_est(L, s); }))) return rc;
   if ((rc = timed_launch(c, kSubApply, s, "subtract launch", [&] { return launch_sub_apply(L, s); }))) return rc;
   c->sub_slots = n_slots;

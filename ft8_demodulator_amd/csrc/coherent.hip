@@ -6,8 +6,8 @@
 //   k_retry_list (ap.hip; the retry pass of ft8_internal.h) lists each slot's first M failed candidates
 //   k_coherent   one 256-lane workgroup per list position (a slot's positions on one XCD):
 //     1. baseband: the samples around the candidate are mixed down to the centre of the 8-tone band
-//        and box-car decimated to Q samples per symbol (D = nsps / Q input samples each) -- the
-//        arithmetic of k_sub_est's phase 2 (subtract.hip): a D-entry twiddle table, two fmas per sample;
+//        and box-car decimated to Q samples per symbol (D = nsps / Q input samples each): the front
+//        end it shares with k_sub_est (baseband.h);
 //    1b. drift (ft8_set_coherent_drift / ft8_coherent_drift_llr only): the baseband is de-chirped in
 //        place by each of n_rates linear drift rates and step 2 repeated; the best rate's copy goes on;
 //     2. sync: over start offsets of +-hop/2 (steps of D samples) and tone-0 offsets of +-bin/2 (5
@@ -18,60 +18,24 @@
 //   k_bp         unchanged (launch_bp, mode 0 over the compacted lists)
 //   k_coh_merge  one wave per list position: a valid fit whose attempt decoded rewrites its record
 // No atomics; every sample index is range-checked or proven in range in 64-bit arithmetic.
-#include "ft8_internal.h"
+#include "baseband.h"
 
 namespace ft8 {
 namespace {
 
-constexpr int kCohThreads = 256;
-constexpr int kCohMaxQ = 32;
-constexpr int kCohMaxT = 2 * (kCohMaxQ / 2) + 1;  // start offsets: 2 ceil(Q / (2 sps)) + 1
-constexpr int kCohNF = 5;                         // tone-0 offsets (j - 2) bin / 4
-constexpr int kSymbols = 79, kSync = 21, kData = 58;
+constexpr int kCohThreads = kBbThreads;
+constexpr int kCohMaxT = 2 * (kBbMaxQ / 2) + 1;  // start offsets: 2 ceil(Q / (2 sps)) + 1
+constexpr int kCohNF = 5;                        // tone-0 offsets (j - 2) bin / 4
+constexpr int kSymbols = kBbSymbols, kSync = 21, kData = 58;
 constexpr double kToneHz = 6.25;
 
-// float2 words of the padded baseband rows (-1 .. 81 of Q + 1), rounded up to a 16-B multiple
-__host__ __device__ inline int coh_z_words(int Q) { return ((kSymbols + 4) * (Q + 1) + 1) & ~1; }
 __host__ __device__ inline int coh_rot_words(int Q) { return kCohNF * 8 * (Q + 1); }
-
-template <typename InT>
-__device__ __forceinline__ float coh_sample(const InT* x, int64_t i);
-template <>
-__device__ __forceinline__ float coh_sample<float>(const float* x, int64_t i) { return x[i]; }
-template <>
-__device__ __forceinline__ float coh_sample<int16_t>(const int16_t* x, int64_t i) {
-  return (float)x[i] / 32767.0f;  // read_wave_file scaling, as the STFT applies it
-}
-
-// four consecutive samples in one load (float: 16 B, 4-byte aligned; int16: 8 B, 2-byte aligned)
-constexpr int kCohLd = 8;
-template <typename InT>
-__device__ __forceinline__ float4 coh_load4(const InT* p);
-template <>
-__device__ __forceinline__ float4 coh_load4<float>(const float* p) {
-  float4 v;
-  __builtin_memcpy(&v, p, sizeof(v));
-  return v;
-}
-template <>
-__device__ __forceinline__ float4 coh_load4<int16_t>(const int16_t* p) {
-  short4 v;
-  __builtin_memcpy(&v, p, sizeof(v));
-  return make_float4((float)v.x / 32767.0f, (float)v.y / 32767.0f, (float)v.z / 32767.0f, (float)v.w / 32767.0f);
-}
 
 __device__ __forceinline__ int costas_tone(int i) {  // 3 1 4 0 6 5 2, packed in nibbles
   return (int)((0x2560413u >> (4 * i)) & 7u);
 }
 __device__ __forceinline__ int gray_map(int j) {     // FT8_Gray_map 0 1 3 2 5 6 4 7
   return (int)((0x74652310u >> (4 * j)) & 7u);
-}
-
-// exp(-2 pi i cyc) from the exact phase
-__device__ __forceinline__ float2 rot_of(double cyc) {
-  float s, c;
-  sincospif((float)(-2.0 * (cyc - floor(cyc))), &s, &c);
-  return make_float2(c, s);
 }
 
 // blank LLRs and a fit that carries only its status
@@ -85,7 +49,7 @@ __device__ void coh_blank(double* llr, ft8_coh_fit* fit, int status) {
 }
 
 // lane-owned elements of z in the drift search: ceil(max Mz / 256), Mz = 79 Q + 2 (Mt + 1), Mt <= Q / 2
-constexpr int kCohOwn = (kSymbols * kCohMaxQ + 2 * (kCohMaxQ / 2 + 1) + kCohThreads - 1) / kCohThreads;
+constexpr int kCohOwn = (kSymbols * kBbMaxQ + 2 * (kBbMaxQ / 2 + 1) + kCohThreads - 1) / kCohThreads;
 
 // Drift: step 1b of the contract, the sync of phase 2 repeated over n_rates de-chirped copies of z.
 // The copies are made in place: z goes from rate i to i + 1 by one complex multiply per element with
@@ -102,9 +66,8 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a, G... drif
   FT8_RACE_PROLOGUE();
   constexpr bool Drift = sizeof...(G) != 0;
   [[maybe_unused]] const CohDrift g = coh_drift_arg(drift...);
-  // dynamic LDS: z in rows of Q + 1 (row r + 1 holds z[1 + r Q .. 1 + (r + 1) Q), r = -1 .. 81: the
-  // layout of k_sub_est, whose bank arithmetic it keeps), the D twiddles of phase 1, the rotation
-  // table [5 * 8][Q + 1] of phase 2 (phase 3 rebuilds its first 8 rows for the refined offset)
+  // dynamic LDS: z and the D twiddles of phase 1 (baseband.h's layout), then the rotation table
+  // [5 * 8][Q + 1] of phase 2 (phase 3 rebuilds its first 8 rows for the refined offset)
   extern __shared__ float4 s_dyn[];
   float2* s_z = reinterpret_cast<float2*>(s_dyn);
   __shared__ float s_part[kCohMaxT * kCohNF * 3];
@@ -130,33 +93,30 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a, G... drif
     const int w = blockIdx.x, j8 = w / 8;
     slot = (w % 8) + 8 * (j8 / a.M);
     const int j = j8 % a.M;
-    if (slot >= a.n_slots || j >= a.count[slot]) return;
+    if (slot >= a.b.n_slots || j >= a.count[slot]) return;
     pos = (int64_t)slot * a.M + j;
   }
   double* llr_out = a.llr + pos * FT8_LDPC_N;
   ft8_coh_fit* fit_out = a.fit + pos;
-  if (slot < 0 || slot >= a.n_slots) {
+  if (slot < 0 || slot >= a.b.n_slots) {
     coh_blank(llr_out, fit_out, 3);
     if constexpr (Drift)
       if (g.out && threadIdx.x == 0) g.out[pos] = ft8_coh_drift{};
     return;
   }
-  const InT* x = reinterpret_cast<const InT*>(a.x) + (int64_t)slot * a.slot_stride;
-  const int nsps = a.nsps, Q = a.Q, D = nsps / Q;
-  const int sps = nsps / a.hop;
-  const int Mt = (Q + 2 * sps - 1) / (2 * sps);  // ceil((hop / 2) / D)
-  const int Mg = Mt + 1, nT = 2 * Mt + 1;
-  const int Mz = kSymbols * Q + 2 * Mg;
-  auto z_at = [Q](int m) { const int u = m - 1 + Q; return u + (int)((unsigned)u / (unsigned)Q); };
-  const double fs = a.fs;
-  const double bin = fs / (double)a.nfft;
-  const int64_t s0 = ((int64_t)a.t_lo + a.cand[2 * pos]) * a.hop;
-  const double fmix = (double)((int64_t)a.f_lo + a.cand[2 * pos + 1]) * bin + 3.5 * kToneHz;
-  const int64_t nb = s0 - (int64_t)Mg * D;
+  const Baseband& bb = a.b;
+  const InT* x = reinterpret_cast<const InT*>(bb.x) + (int64_t)slot * bb.slot_stride;
+  const BbGeom geo = bb_geom(bb.nsps, bb.hop, bb.Q);
+  const int nsps = bb.nsps, Q = geo.Q, D = geo.D, Mt = geo.Mt, Mg = geo.Mg, Mz = geo.Mz, nT = geo.nT;
+  const double fs = bb.fs;
+  const double bin = fs / (double)bb.nfft;
+  const int64_t s0 = ((int64_t)bb.t_lo + a.cand[2 * pos]) * bb.hop;
+  const double fmix = (double)((int64_t)bb.f_lo + a.cand[2 * pos + 1]) * bin + 3.5 * kToneHz;
+  const int64_t nb = bb_nb(geo, s0);
   // symbol k at start offset d - Mt is present when its nsps input samples lie in [0, n_samples)
   auto present = [&](int d, int k) {
     const int64_t first = nb + ((int64_t)(1 + d) + (int64_t)k * Q) * D;
-    return first >= 0 && first + nsps <= a.n_samples;
+    return first >= 0 && first + nsps <= bb.n_samples;
   };
 
   // ---- nothing to measure: no Costas symbol inside the slot at any start offset
@@ -174,67 +134,19 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a, G... drif
     return;
   }
 
-  // ---- 1. z[m] = w_m sum_i x[nb + m D + i] t_i, t_i = exp(-2 pi i fmix i / fs) from a table of D
-  // exact twiddles, w_m = exp(-2 pi i fmix (nb + m D) / fs); a thread owns z[tid + 256 j].  A window
-  // inside the slot reads its samples four at a time, unchecked; else every sample is tested.
-  float2* s_tw = s_z + coh_z_words(Q);
-  float2* s_R = s_tw + ((D + 1) & ~1);
-  for (int i = threadIdx.x; i < D; i += kCohThreads) s_tw[i] = rot_of(fmix * (double)i / fs);
+  // ---- 1. the mixed-down, decimated baseband z (baseband.h)
+  float2* s_tw = s_z + bb_z_words(Q);
+  float2* s_R = s_z + bb_tail_at(Q, D);
+  bb_twiddles(s_tw, D, fmix, fs);
   // rotation powers of phase 2, each from its exact phase: row j * 8 + t, entry q
   for (int e = threadIdx.x; e < coh_rot_words(Q); e += kCohThreads) {
     const int ft = e / (Q + 1), q = e - ft * (Q + 1);
     const int t = ft & 7, j = ft >> 3;
     const double nu = (double)t - 3.5 + ((double)(j - 2) * bin / 4.0) / kToneHz;  // tones relative to fmix
-    s_R[e] = rot_of(nu * (double)q / (double)Q);
+    s_R[e] = bb_rot(nu * (double)q / (double)Q);
   }
   __syncthreads();
-  {
-    const bool inside = nb >= 0 && nb + (int64_t)Mz * D <= a.n_samples;  // workgroup-uniform
-#pragma unroll 1
-    for (int m = threadIdx.x; m < Mz; m += kCohThreads) {
-      const int64_t n0 = nb + (int64_t)m * D;
-      const InT* xp = x + n0;
-      float ax = 0.f, ay = 0.f;
-      if (inside && (D & 3) == 0) {
-        // kCohLd loads of four samples are issued before the first is used: one load per trip left a
-        // lane's L2 hits a full latency apart.  The fmas keep their order.  Past D a trip repeats the
-        // last in-range load and does not use it.
-        for (int i0 = 0; i0 < D; i0 += 4 * kCohLd) {
-          float4 v[kCohLd];
-#pragma unroll
-          for (int u = 0; u < kCohLd; ++u) v[u] = coh_load4<InT>(xp + min(i0 + 4 * u, D - 4));
-#pragma unroll
-          for (int u = 0; u < kCohLd; ++u) {
-            const int i = i0 + 4 * u;
-            if (i < D) {
-              const float4 t01 = *reinterpret_cast<const float4*>(s_tw + i);
-              const float4 t23 = *reinterpret_cast<const float4*>(s_tw + i + 2);
-              ax = fmaf(v[u].x, t01.x, ax);
-              ay = fmaf(v[u].x, t01.y, ay);
-              ax = fmaf(v[u].y, t01.z, ax);
-              ay = fmaf(v[u].y, t01.w, ay);
-              ax = fmaf(v[u].z, t23.x, ax);
-              ay = fmaf(v[u].z, t23.y, ay);
-              ax = fmaf(v[u].w, t23.z, ax);
-              ay = fmaf(v[u].w, t23.w, ay);
-            }
-          }
-        }
-      } else {
-        for (int i = 0; i < D; ++i) {
-          const int64_t n = n0 + i;
-          if (n >= 0 && n < a.n_samples) {
-            const float v = coh_sample<InT>(xp, i);
-            const float2 t = s_tw[i];
-            ax = fmaf(v, t.x, ax);
-            ay = fmaf(v, t.y, ay);
-          }
-        }
-      }
-      const float2 w = rot_of(fmix * (double)n0 / fs);
-      s_z[z_at(m)] = make_float2(ax * w.x - ay * w.y, ax * w.y + ay * w.x);
-    }
-  }
+  bb_mix_down<InT, kBbLd>(x, bb.n_samples, nb, geo, fmix, fs, s_tw, s_z);
   __syncthreads();
 
   // ---- 2. sync: item (start offset d, tone-0 offset j, Costas block b) sums its 7 symbols' powers in
@@ -260,14 +172,14 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a, G... drif
   };
   // by dr Hz/s, the factor from its exact phase
   auto rotate_exact = [&](double dr) __attribute__((always_inline)) {
-    rotate([&](int u) { return rot_of(0.5 * dr * tau2(threadIdx.x + u * kCohThreads)); });
+    rotate([&](int u) { return bb_rot(0.5 * dr * tau2(threadIdx.x + u * kCohThreads)); });
   };
   if constexpr (Drift) {
 #pragma unroll
     for (int u = 0; u < kCohOwn; ++u) {
       const int m = threadIdx.x + u * kCohThreads;
-      zi[u] = m < Mz ? z_at(m) : -1;
-      wr[u] = rot_of(0.5 * rstep * tau2(m));
+      zi[u] = m < Mz ? bb_z_at(Q, m) : -1;
+      wr[u] = bb_rot(0.5 * rstep * tau2(m));
     }
     rotate_exact((double)(-ic) * rstep);
     __syncthreads();
@@ -339,7 +251,7 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a, G... drif
   // ---- 3. spectra of the data symbols at (db, df); the rotations replace rows 0 .. 7 of the table
   for (int e = threadIdx.x; e < 8 * (Q + 1); e += kCohThreads) {
     const int t = e / (Q + 1), q = e - t * (Q + 1);
-    s_R[e] = rot_of(((double)t - 3.5 + df / kToneHz) * (double)q / (double)Q);
+    s_R[e] = bb_rot(((double)t - 3.5 + df / kToneHz) * (double)q / (double)Q);
   }
   __syncthreads();
   for (int e = threadIdx.x; e < kData * 8; e += kCohThreads) {
@@ -451,20 +363,20 @@ __global__ __launch_bounds__(4 * kWave) void k_coh_merge(CohPass a) {
 }  // namespace
 
 size_t coherent_lds_bytes(int nsps, int Q) {
-  const int D = nsps / Q;
-  return sizeof(float2) * ((size_t)coh_z_words(Q) + (size_t)((D + 1) & ~1) + (size_t)coh_rot_words(Q));
+  return sizeof(float2) * ((size_t)bb_tail_at(Q, nsps / Q) + (size_t)coh_rot_words(Q));
 }
 
 hipError_t launch_coherent(const CohLaunch& a, const CohDrift& g, hipStream_t s) {
-  const int64_t grid = a.slot_of ? (int64_t)a.n : (int64_t)((a.n_slots + 7) / 8) * 8 * a.M;
+  const int64_t grid = a.slot_of ? (int64_t)a.n : (int64_t)((a.b.n_slots + 7) / 8) * 8 * a.M;
   if (grid <= 0) return hipSuccess;
-  const size_t lds = coherent_lds_bytes(a.nsps, a.Q);
+  if (!bb_valid(a.b)) return hipErrorInvalidValue;
+  const size_t lds = coherent_lds_bytes(a.b.nsps, a.b.Q);
   if (coherent_drift_on(g)) {
-    if (a.dtype == FT8_I16)
+    if (a.b.dtype == FT8_I16)
       return lds_launch(k_coherent<int16_t, CohDrift>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a, g);
     return lds_launch(k_coherent<float, CohDrift>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a, g);
   }
-  if (a.dtype == FT8_I16) return lds_launch(k_coherent<int16_t>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a);
+  if (a.b.dtype == FT8_I16) return lds_launch(k_coherent<int16_t>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a);
   return lds_launch(k_coherent<float>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a);
 }
 

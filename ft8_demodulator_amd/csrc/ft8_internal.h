@@ -282,6 +282,17 @@ struct CompactLaunch {
 };
 hipError_t launch_compact(const CompactLaunch& a, hipStream_t s);
 
+// ---- the samples and geometry k_sub_est and k_coherent mix down from (baseband.h; capi.hip baseband_setup)
+struct Baseband {
+  const void* x;               // samples [n_slots][slot_stride], F32 or I16
+  int dtype;
+  int64_t n_samples, slot_stride;
+  int n_slots;
+  double fs;
+  int nsps, hop, nfft, t_lo, f_lo;
+  int Q;                       // decimated samples per symbol (nsps % Q == 0)
+};
+
 // ---- retry pass: the failed candidates of a chunk, tried again (ap.hip, coherent.hip) --------------
 // Both retries of ft8_decode_batch take the records plain BP left with ok == 0: launch_retry_list lists
 // them per slot in candidate order, the pass builds new LLRs for the list positions, launch_bp runs in
@@ -341,13 +352,7 @@ hipError_t launch_ap_merge(const ApLaunch& a, hipStream_t s);
 // (slot_of non-null: n candidates, workgroup = list position) or per-slot lists [n_slots][M] with
 // count[n_slots] entries each (a slot's positions on one XCD).
 struct CohLaunch {
-  const void* x;               // samples [n_slots][slot_stride], F32 or I16
-  int dtype;
-  int64_t n_samples, slot_stride;
-  int n_slots;
-  double fs;
-  int nsps, hop, nfft, t_lo, f_lo;
-  int Q;                       // decimated samples per symbol (nsps % Q == 0)
+  Baseband b;
   const int32_t* cand;         // [positions][2] = (abs_time, abs_freq)
   const int32_t* slot_of;      // explicit list: [n]; null: per-slot lists
   const int32_t* count;        // per-slot lists: [n_slots]
@@ -412,19 +417,14 @@ hipError_t launch_encode(const uint8_t* msg, int msg_bytes, int n, uint8_t* a91,
 hipError_t launch_synth(const SynthLaunch& a, hipStream_t s);
 
 struct SubLaunch {
-  const void* x;               // samples [n_slots][slot_stride], F32 or I16
-  int dtype;
+  Baseband b;
   float* residual;             // [n_slots][slot_stride]
-  int64_t n_samples, slot_stride;
-  int n_slots;
-  int fs, nsps, hop, nfft, t_lo, f_lo;
   const ft8_result* res;       // [n_slots][cap] decoded records
   const int32_t* counts;       // [n_slots]
   int cap;
   const double* P;             // cumulative GFSK pulse [3 nsps + 1] (double)
   const float* Pf;             // the same in float
   void* est;                   // scratch [n_slots * cap] SubEst records
-  int Q;                       // decimated samples per symbol (nsps % Q == 0)
   int32_t* list;               // scratch [n_slots][cap + 1]: the records to fit (ok, first of their
                                // payload in the slot), in record order, then their count
 };

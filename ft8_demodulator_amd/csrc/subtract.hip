@@ -21,37 +21,26 @@
 //            summed in record order (deterministic).
 // k_merge    one wave per slot: pass-2 records with a payload not decoded in pass 1 are appended.
 #include <algorithm>
-#include <type_traits>
 
+#include "baseband.h"
 #include "tx_device.h"
 
 namespace ft8 {
 namespace {
 
-constexpr int kSubThreads = 256;
+constexpr int kSubThreads = kBbThreads;
 constexpr int kSubRecStride = 32;               // k_sub_est workgroups per slot (a crowded slot: ~21 fits)
 constexpr int kSubRestStride = 8;               // ... and per slot in the rest launch (fits >= 32)
 constexpr int kSubWaves = kSubThreads / kWave;
-constexpr int kMaxQ = 32;
 constexpr int kMaxHyp = 1024;
-constexpr int kMaxT = kMaxQ + 3;                // start offsets searched: 2 ceil(Q / (2 sps)) + 1
+constexpr int kMaxT = kBbMaxQ + 3;              // start offsets searched: 2 ceil(Q / (2 sps)) + 1
 constexpr int kMf = 2;                         // tone-0 search: 2 kMf + 1 points over +-bin/2
-// float2 words of k_sub_est's padded baseband rows (-1 .. 81 of Q + 1), rounded up to a 16-B multiple;
-// the decimation's twiddle table [D] follows them
-__host__ __device__ inline int z_words(int Q) { return ((tx::kSymbols + 4) * (Q + 1) + 1) & ~1; }
+__host__ __device__ inline int sub_rot_words(int Q) { return (2 * kMf + 1) * 8 * (Q + 1); }
 
 // the fitted signal of one record: the public ft8_sub_fit (include/ft8hip.h, ft8_subtract_fits)
 using SubEst = ft8_sub_fit;
 static_assert(sizeof(((SubEst*)nullptr)->amp) / sizeof(float[2]) == tx::kSymbols, "one amplitude per symbol");
-
-template <typename InT>
-__device__ __forceinline__ float ld_sample(const InT* x, int64_t i);
-template <>
-__device__ __forceinline__ float ld_sample<float>(const float* x, int64_t i) { return x[i]; }
-template <>
-__device__ __forceinline__ float ld_sample<int16_t>(const int16_t* x, int64_t i) {
-  return (float)x[i] / 32767.0f;  // read_wave_file scaling, as the STFT applies it
-}
+static_assert(tx::kSymbols == kBbSymbols, "baseband.h's rows hold tx_device.h's symbols");
 
 __device__ __forceinline__ float ramp_f(int n, int L, int nsps) { return tx::gfsk_ramp<float>(n, L, nsps, 0); }
 // k_sub_list: one wave per slot lists the records worth a fit -- ok, and the first record of the
@@ -93,12 +82,8 @@ __global__ __launch_bounds__(kWave) void k_sub_list(SubLaunch a) {
 template <typename InT, bool REST>
 __global__ __launch_bounds__(kSubThreads) void k_sub_est(SubLaunch a) {
   FT8_RACE_PROLOGUE();
-  // dynamic LDS: the decimated baseband z (phases 2-3), then the float pulse table (phase 4).  z is
-  // stored in rows of Q + 1 (one pad): row r + 1 holds z[1 + r Q .. 1 + (r + 1) Q), r = -1 .. 81,
-  // so symbol k's window starts a row (z_at below) and the lanes' reads (one symbol per lane) are
-  // 2 (Q + 1) dwords apart -- distinct banks for even Q.  Unpadded, the lanes of a ds_read_b64
-  // were 2 Q dwords apart: at Q = 32 one bank for all 32 lanes of a group (32-way conflicts; 169 M
-  // conflict cycles per 334-slot launch, r4_v30_sub_pmc.json)
+  // dynamic LDS: the decimated baseband z in baseband.h's padded rows (phases 2-3), then the float
+  // pulse table (phase 4)
   extern __shared__ float4 s_dyn[];
   float2* s_z = reinterpret_cast<float2*>(s_dyn);
   float4* s_D = s_dyn;  // phase 4: the pulse table's symbol-relative differences (see k_sub_apply)
@@ -118,7 +103,7 @@ __global__ __launch_bounds__(kSubThreads) void k_sub_est(SubLaunch a) {
   constexpr int kStride = REST ? kSubRestStride : kSubRecStride;
   const int slot = (w % 8) + 8 * (j8 / kStride);
   const int rec0 = j8 % kStride;
-  if (slot >= a.n_slots) return;
+  if (slot >= a.b.n_slots) return;
   const int32_t* list = a.list + (int64_t)slot * (a.cap + 1);
   const int nfit = list[a.cap];
   for (int i = rec0 + (REST ? kSubRecStride : 0); i < nfit; i += kStride) {
@@ -142,95 +127,38 @@ __global__ __launch_bounds__(kSubThreads) void k_sub_est(SubLaunch a) {
   }
   __syncthreads();
 
-  const InT* x = reinterpret_cast<const InT*>(a.x) + (int64_t)slot * a.slot_stride;
-  const int nsps = a.nsps, Q = a.Q, D = nsps / Q, L = tx::kSymbols * nsps;
-  const int Mt = (Q + 2 * (nsps / a.hop) - 1) / (2 * (nsps / a.hop));  // ceil((hop / 2) / D)
-  const int Mg = Mt + 1;
-  const int Mz = tx::kSymbols * Q + 2 * Mg;
-  // z[m] -> its padded position (m >= 0; Mg - Mt = 1 is the first window's start)
-  auto z_at = [Q](int m) { const int u = m - 1 + Q; return u + (int)((unsigned)u / (unsigned)Q); };
-  const double fs = (double)a.fs;
-  const int64_t s0 = (int64_t)(a.t_lo + r.abs_time) * a.hop;
-  const double ftone = (double)(a.f_lo + r.abs_freq) * fs / (double)a.nfft;
+  const Baseband& bb = a.b;
+  const InT* x = reinterpret_cast<const InT*>(bb.x) + (int64_t)slot * bb.slot_stride;
+  const BbGeom geo = bb_geom(bb.nsps, bb.hop, bb.Q);
+  const int nsps = bb.nsps, Q = geo.Q, D = geo.D, Mt = geo.Mt, nT = geo.nT, L = tx::kSymbols * nsps;
+  const double fs = bb.fs;
+  const int64_t s0 = (int64_t)(bb.t_lo + r.abs_time) * bb.hop;
+  const double ftone = (double)(bb.f_lo + r.abs_freq) * fs / (double)bb.nfft;
   const double fmix = ftone + 3.5 * 6.25;
 
-  // ---- 2. mixed-down, box-car decimated baseband z[m], samples [nb + m D, nb + (m + 1) D):
-  // z[m] = w_m sum_i x[nb + m D + i] t_i with t_i = exp(-2 pi i fmix i / fs) (a table of D twiddles
-  // in LDS, each from the exact phase) and w_m = exp(-2 pi i fmix (nb + m D) / fs).  A thread owns
-  // z[tid + 256 j]: two fmas per sample.  (Round 4 rotated a per-z phasor by one complex multiply
-  // per sample, ~20 VALU per sample with its per-sample range tests.)  Records whose window lies
-  // inside the slot (all but the slot's edges) read float32 samples four at a time, unchecked.
-  {
-    constexpr int kZ = (tx::kSymbols * kMaxQ + 2 * (kMaxQ / 2 + 2) + kSubThreads - 1) / kSubThreads;
-    const int64_t nb = s0 - (int64_t)Mg * D;
-    float2* s_tw = s_z + z_words(Q);
-    for (int i = threadIdx.x; i < D; i += kSubThreads) {
-      const double cyc = fmix * (double)i / fs;
-      float sn, cs;
-      sincospif((float)(-2.0 * (cyc - floor(cyc))), &sn, &cs);
-      s_tw[i] = make_float2(cs, sn);
-    }
-    __syncthreads();
-    const bool inside = nb >= 0 && nb + (int64_t)Mz * D <= a.n_samples;  // workgroup-uniform
-#pragma unroll 1
-    for (int j = 0; j < kZ; ++j) {
-      const int m = threadIdx.x + j * kSubThreads;
-      if (m >= Mz) break;
-      const int64_t n0 = nb + (int64_t)m * D;
-      const InT* xp = x + n0;
-      float ax = 0.f, ay = 0.f;
-      if (std::is_same<InT, float>::value && inside && (D & 3) == 0) {
-        for (int i = 0; i < D; i += 4) {
-          float4 v;
-          __builtin_memcpy(&v, xp + i, sizeof(v));  // 4-byte aligned
-          const float4 t01 = *reinterpret_cast<const float4*>(s_tw + i);
-          const float4 t23 = *reinterpret_cast<const float4*>(s_tw + i + 2);
-          ax = fmaf(v.x, t01.x, ax);
-          ay = fmaf(v.x, t01.y, ay);
-          ax = fmaf(v.y, t01.z, ax);
-          ay = fmaf(v.y, t01.w, ay);
-          ax = fmaf(v.z, t23.x, ax);
-          ay = fmaf(v.z, t23.y, ay);
-          ax = fmaf(v.w, t23.z, ax);
-          ay = fmaf(v.w, t23.w, ay);
-        }
-      } else {
-        for (int i = 0; i < D; ++i) {
-          const int64_t n = n0 + i;
-          if (n >= 0 && n < a.n_samples) {
-            const float v = ld_sample<InT>(xp, i);
-            const float2 t = s_tw[i];
-            ax = fmaf(v, t.x, ax);
-            ay = fmaf(v, t.y, ay);
-          }
-        }
-      }
-      const double cyc = fmix * (double)n0 / fs;
-      float ws, wc;
-      sincospif((float)(-2.0 * (cyc - floor(cyc))), &ws, &wc);
-      s_z[z_at(m)] = make_float2(ax * wc - ay * ws, ax * ws + ay * wc);
-    }
-  }
+  // ---- 2. the mixed-down, decimated baseband z (baseband.h), all its loads issued ahead as in
+  // k_coherent
+  float2* s_tw = s_z + bb_z_words(Q);
+  bb_twiddles(s_tw, D, fmix, fs);
+  __syncthreads();
+  bb_mix_down<InT, kBbLd>(x, bb.n_samples, bb_nb(geo, s0), geo, fmix, fs, s_tw, s_z);
   __syncthreads();
 
   // ---- 3. fine sync over (start, tone-0) hypotheses
-  const double bin = fs / (double)a.nfft;
+  const double bin = fs / (double)bb.nfft;
   const int Mf = kMf;
   const double fstep = 0.5 * bin / kMf;
-  const int nT = 2 * Mt + 1, nF = 2 * Mf + 1;
+  const int nF = 2 * Mf + 1;
   const int H = min(nT * nF, kMaxHyp);
   // per-(tone-0 offset, tone) rotation of one decimated sample and its powers w^q, q <= Q, each from
   // its exact phase (one LDS read and four fmas per sample of a coherent window; round 4 advanced
   // w^q by a complex multiply per sample)
-  float2* s_W = s_z + z_words(Q) + ((D + 1) & ~1);  // after the twiddles of phase 2: [nF * 8][Q + 1]
-  for (int e = threadIdx.x; e < nF * 8 * (Q + 1); e += kSubThreads) {
+  float2* s_W = s_z + bb_tail_at(Q, D);  // after the twiddles of phase 2: [nF * 8][Q + 1]
+  for (int e = threadIdx.x; e < sub_rot_words(Q); e += kSubThreads) {
     const int ft = e / (Q + 1), q = e - ft * (Q + 1);
     const int t = ft & 7, dfi = ft / 8 - Mf;
     const double nu = (double)t * 6.25 + dfi * fstep - 3.5 * 6.25;  // Hz relative to fmix
-    const double cyc = nu * (double)D * (double)q / fs;
-    float s_, c_;
-    sincospif((float)(-2.0 * (cyc - floor(cyc))), &s_, &c_);
-    s_W[e] = make_float2(c_, s_);
+    s_W[e] = bb_rot(nu * (double)D * (double)q / fs);
   }
   __syncthreads();
   // sliding windows: a wave owns one tone-0 offset at a time and a lane one symbol (k, k + 64);
@@ -325,7 +253,7 @@ __global__ __launch_bounds__(kSubThreads) void k_sub_est(SubLaunch a) {
       float ax = 0.f, ay = 0.f, rr = 0.f;
       const float ph = s_ph0[k];
       const int64_t nsym = start + (int64_t)k * nsps;
-      const bool inside = nsym >= 0 && nsym + nsps <= a.n_samples;
+      const bool inside = nsym >= 0 && nsym + nsps <= a.b.n_samples;
       const float E0 = (float)s_E[k], E1 = (float)s_E[k + 1], E2 = (float)s_E[k + 2];
       // the amplitude ramp is 1 except in the first and last symbols (wave-uniform): those take
       // a plain loop with the ramp, every other symbol the batched loads with rp = 1
@@ -333,13 +261,13 @@ __global__ __launch_bounds__(kSubThreads) void k_sub_est(SubLaunch a) {
 #pragma unroll 1
         for (int i = lane; i < nsps; i += kWave) {
           const int64_t n = nsym + i;
-          if (!(n >= 0 && n < a.n_samples)) continue;
+          if (!(n >= 0 && n < a.b.n_samples)) continue;
           const float rp = ramp_f(k * nsps + i, L, nsps);
           const float4 dd = s_D[i];
           const float cyc = ph + (float)i * f0r + sr * (E0 * dd.x + E1 * dd.y + E2 * dd.z);
           const float fr = __builtin_amdgcn_fractf(cyc);
           const float sn = __builtin_amdgcn_sinf(fr), cs = __builtin_amdgcn_cosf(fr);
-          const float vr = ld_sample<InT>(x, n) * rp;
+          const float vr = bb_sample<InT>(x, n) * rp;
           ax += vr * cs;
           ay -= vr * sn;
           rr += rp * rp;
@@ -348,7 +276,7 @@ __global__ __launch_bounds__(kSubThreads) void k_sub_est(SubLaunch a) {
         // rp = 1: vr = v * 1, and sum rp^2 is the number of samples the symbol has in the slot (a sum
         // of 1.0s is exact in any order, so it is that count, not a per-sample add); inside the
         // slot (wave-uniform, all but the slot's edges) the samples are read without range tests
-        const int64_t lo_n = max<int64_t>(nsym, 0), hi_n = min<int64_t>(nsym + nsps, a.n_samples);
+        const int64_t lo_n = max<int64_t>(nsym, 0), hi_n = min<int64_t>(nsym + nsps, a.b.n_samples);
         rr = (lane == 0 && hi_n > lo_n) ? (float)(hi_n - lo_n) : 0.f;
         for (int i0 = lane; i0 < nsps; i0 += kPf * kWave) {
           float v[kPf];
@@ -358,7 +286,7 @@ __global__ __launch_bounds__(kSubThreads) void k_sub_est(SubLaunch a) {
             const int i = i0 + u * kWave;
             const int64_t n = nsym + i;
             v[u] = 0.f;
-            if (i < nsps && (inside || (n >= 0 && n < a.n_samples))) v[u] = ld_sample<InT>(xp, u * kWave);
+            if (i < nsps && (inside || (n >= 0 && n < a.b.n_samples))) v[u] = bb_sample<InT>(xp, u * kWave);
           }
 #pragma unroll
           for (int u = 0; u < kPf; ++u) {
@@ -443,13 +371,13 @@ __global__ __launch_bounds__(kApThreads) void k_sub_apply(SubLaunch a) {
   extern __shared__ float4 s_D[];
   const int slot = blockIdx.y;
   const int64_t t0 = (int64_t)blockIdx.x * kApTile;
-  const int nsps = a.nsps, L = tx::kSymbols * nsps, nramp = nsps / 8;
+  const int nsps = a.b.nsps, L = tx::kSymbols * nsps, nramp = nsps / 8;
   float* s_R = reinterpret_cast<float*>(s_D + nsps);
-  const float fsf = (float)a.fs, inv_nsps = 1.0f / (float)nsps, sr = 6.25f / fsf;
+  const float fsf = (float)a.b.fs, inv_nsps = 1.0f / (float)nsps, sr = 6.25f / fsf;
   const int cnt = min(a.counts[slot], a.cap);
   const SubEst* est = reinterpret_cast<const SubEst*>(a.est) + (int64_t)slot * a.cap;
   // samples t0 + tid + 512 kk with kk < nv exist (16 except in a slot's last tile)
-  const int64_t rem = a.n_samples - (t0 + (int64_t)threadIdx.x);
+  const int64_t rem = a.b.n_samples - (t0 + (int64_t)threadIdx.x);
   const int nv = rem <= 0 ? 0 : (int)min<int64_t>(kApPer, (rem + kApThreads - 1) / kApThreads);
   float acc[kApPer];
 #pragma unroll
@@ -497,7 +425,7 @@ __global__ __launch_bounds__(kApThreads) void k_sub_apply(SubLaunch a) {
       if (threadIdx.x < nb) {
         const SubEst* e = est + j0 + s_list[b0 + threadIdx.x];
         s_start[threadIdx.x] = e->start;
-        s_f0r[threadIdx.x] = (float)(e->f0 / (double)a.fs);
+        s_f0r[threadIdx.x] = (float)(e->f0 / (double)a.b.fs);
       }
       __syncthreads();
       for (int f = 0; f < nb; ++f) {
@@ -555,12 +483,12 @@ __global__ __launch_bounds__(kApThreads) void k_sub_apply(SubLaunch a) {
       }
     }
   }
-  const InT* x = reinterpret_cast<const InT*>(a.x) + (int64_t)slot * a.slot_stride;
-  float* out = a.residual + (int64_t)slot * a.slot_stride;
+  const InT* x = reinterpret_cast<const InT*>(a.b.x) + (int64_t)slot * a.b.slot_stride;
+  float* out = a.residual + (int64_t)slot * a.b.slot_stride;
 #pragma unroll
   for (int kk = 0; kk < kApPer; ++kk) {
     const int64_t nabs = t0 + threadIdx.x + (int64_t)kk * kApThreads;
-    if (nabs < a.n_samples) out[nabs] = ld_sample<InT>(x, nabs) - acc[kk];
+    if (nabs < a.b.n_samples) out[nabs] = bb_sample<InT>(x, nabs) - acc[kk];
   }
 }
 
@@ -610,22 +538,21 @@ size_t sub_est_bytes() { return sizeof(SubEst); }
 // lds_launch, which raises it once per kernel and device and again only when a launch needs more
 // (it was a host-side call per launch)
 hipError_t launch_sub_est(const SubLaunch& a, hipStream_t s) {
-  if (a.n_slots <= 0 || a.n_samples <= 0) return hipSuccess;
-  if (a.Q <= 0 || a.Q > kMaxQ || a.nsps % a.Q != 0 || a.hop <= 0 || a.nsps % a.hop != 0) return hipErrorInvalidValue;
+  if (a.b.n_slots <= 0 || a.b.n_samples <= 0) return hipSuccess;
+  if (!bb_valid(a.b)) return hipErrorInvalidValue;
   if (a.cap > 0) {
-    hipLaunchKernelGGL(k_sub_list, dim3(a.n_slots), dim3(kWave), 0, s, a);
-    const unsigned grid = (unsigned)(((a.n_slots + 7) / 8) * 8 * (int64_t)kSubRecStride);
+    hipLaunchKernelGGL(k_sub_list, dim3(a.b.n_slots), dim3(kWave), 0, s, a);
+    const unsigned grid = (unsigned)(((a.b.n_slots + 7) / 8) * 8 * (int64_t)kSubRecStride);
     // the rest launch: 8 workgroups per slot that exit at once unless the slot holds more than
     // kSubRecStride fits
-    const unsigned grid_rest = (unsigned)(((a.n_slots + 7) / 8) * 8 * (int64_t)kSubRestStride);
+    const unsigned grid_rest = (unsigned)(((a.b.n_slots + 7) / 8) * 8 * (int64_t)kSubRestStride);
     // padded z rows -1 .. 81, the decimation's twiddles and the fine sync's rotation powers (phases
     // 2-3), then the pulse table (phase 4)
-    const int D = a.nsps / a.Q;
-    const size_t mz = (size_t)z_words(a.Q) + (size_t)((D + 1) & ~1) + (size_t)(2 * kMf + 1) * 8 * (a.Q + 1);
-    const size_t lds = std::max(mz * sizeof(float2), (size_t)a.nsps * sizeof(float4));
+    const size_t mz = (size_t)bb_tail_at(a.b.Q, a.b.nsps / a.b.Q) + (size_t)sub_rot_words(a.b.Q);
+    const size_t lds = std::max(mz * sizeof(float2), (size_t)a.b.nsps * sizeof(float4));
     const bool rest = a.cap > kSubRecStride;
     hipError_t e;
-    if (a.dtype == FT8_I16) {
+    if (a.b.dtype == FT8_I16) {
       e = lds_launch(k_sub_est<int16_t, false>, dim3(grid), dim3(kSubThreads), lds, s, a);
       if (e == hipSuccess && rest) e = lds_launch(k_sub_est<int16_t, true>, dim3(grid_rest), dim3(kSubThreads), lds, s, a);
     } else {
@@ -638,10 +565,10 @@ hipError_t launch_sub_est(const SubLaunch& a, hipStream_t s) {
 }
 
 hipError_t launch_sub_apply(const SubLaunch& a, hipStream_t s) {
-  if (a.n_slots <= 0 || a.n_samples <= 0) return hipSuccess;
-  dim3 g2((unsigned)((a.n_samples + kApTile - 1) / kApTile), (unsigned)a.n_slots);
-  const size_t lds2 = (size_t)a.nsps * sizeof(float4) + (size_t)(a.nsps / 8) * sizeof(float);
-  if (a.dtype == FT8_I16) return lds_launch(k_sub_apply<int16_t>, g2, dim3(kApThreads), lds2, s, a);
+  if (a.b.n_slots <= 0 || a.b.n_samples <= 0) return hipSuccess;
+  dim3 g2((unsigned)((a.b.n_samples + kApTile - 1) / kApTile), (unsigned)a.b.n_slots);
+  const size_t lds2 = (size_t)a.b.nsps * sizeof(float4) + (size_t)(a.b.nsps / 8) * sizeof(float);
+  if (a.b.dtype == FT8_I16) return lds_launch(k_sub_apply<int16_t>, g2, dim3(kApThreads), lds2, s, a);
   return lds_launch(k_sub_apply<float>, g2, dim3(kApThreads), lds2, s, a);
 }
 

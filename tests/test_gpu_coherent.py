@@ -68,6 +68,25 @@ def test_stage_equals_restatement_10k(gpu):
     _check_stage("10k", got, c["f32"], C.FS10, C.NSPS10 // 32, C.FS10 / C.NFFT10)
 
 
+@pytest.mark.parametrize("key", ["f32", "i16"])
+def test_stage_at_the_slot_edges(gpu, key):
+    """The stage case's measured candidates whose baseband window starts before the slot or ends past it
+    (the range-checked loop of bb_mix_down; csrc/baseband.h), alone, against the restatement."""
+    from ft8_demodulator_amd.ldpc_decoder import coherent_llr_batch
+    c = C.stage_case_12k()
+    x = np.array(c["x"] if key == "f32" else c["pcm"])
+    Q, sps = 32, C.NSPS // C.HOP
+    D, Mg = C.NSPS // Q, (Q + 2 * sps - 1) // (2 * sps) + 1
+    nb = c["cand"][:, 0].astype(np.int64) * C.HOP - Mg * D
+    rllr, rfits, grids = c[key]
+    measured = rfits["status"] == 0
+    head, tail = measured & (nb < 0), measured & (nb + (79 * Q + 2 * Mg) * D > x.shape[1])
+    assert head.any() and tail.any() and (measured & ~head & ~tail).any()
+    sel = np.flatnonzero(head | tail)
+    got = coherent_llr_batch(x, c["cand"][sel], c["slot_of"][sel], C.FS, 2, 2)
+    _check_stage(key + " edges", got, (rllr[sel], rfits[sel], [grids[i] for i in sel]), C.FS, D, C.BIN)
+
+
 def test_stage_slot_out_of_range_and_empty(gpu):
     from ft8_demodulator_amd.ldpc_decoder import coherent_llr_batch
     c = C.stage_case_12k()

@@ -88,3 +88,118 @@ def test_subtract_pass2_matches_oracle(gpu, oracle):
     assert n_fits >= 3 * N_SLOTS
     assert n_start_off <= max(1, n_fits // 20)
     print(f"subtract oracle: {n_fits} fits, {n_start_off} with start +-1")
+
+
+# ---- the paths of the baseband front end (csrc/baseband.h) that a crowded slot does not take ----------
+# one slot each; the tolerances are the test's above
+
+def _device_fits(x, fs, bpt, sps):
+    """Top-k decode of the slots x (float32 or int16 PCM on the device) and ft8_subtract on its records
+    -> (records per slot, plan, fits [n_slots, cap])."""
+    import torch
+    from ft8_demodulator_amd import SlotDecoder, _lib
+    from ft8_demodulator_amd._pipeline import make_params
+
+    n_slots, n = x.shape
+    dec = SlotDecoder(fs, bpt, sps, 40, MIN_SCORE, ITERS, flags=_lib.FT8_FLAG_TOPK)
+    out, counts = dec.run(x)
+    recs = dec.records(x)
+    plan = dec.plan(n)
+    p = make_params(plan, 40, MIN_SCORE, ITERS, _lib.FT8_FLAG_TOPK)
+    ctx, L, st = dec.ctx, _lib.lib(), _lib.stream_handle()
+    code = _lib.FT8_I16 if x.dtype == torch.int16 else _lib.FT8_F32
+    resid = torch.empty(x.shape, dtype=torch.float32, device="cuda")
+    ctx.check(L.ft8_subtract(ctx.handle, _lib.ptr(x), code, _lib.ptr(resid), n, n_slots, n, ctypes.byref(p),
+                             _lib.ptr(out), _lib.ptr(counts), dec.cap, st), "ft8_subtract")
+    fits_d = torch.empty(n_slots * dec.cap * _lib.SUB_FIT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    ctx.check(L.ft8_subtract_fits(ctx.handle, _lib.ptr(fits_d), n_slots, dec.cap, st), "ft8_subtract_fits")
+    torch.cuda.synchronize()
+    return recs, plan, fits_d.cpu().numpy().view(_lib.SUB_FIT_DTYPE).reshape(n_slots, dec.cap)
+
+
+def _check_fits(gfit, ofit):
+    """Every device fit of one slot against the oracle's fit of the same record -> the number compared."""
+    n_fits = 0
+    for j, of in enumerate(ofit):
+        g = gfit[j]
+        assert int(g["active"]) == (of is not None), j
+        if of is None:
+            continue
+        n_fits += 1
+        assert list(g["tones"][:79]) == list(of["tones"])
+        assert abs(int(g["start"]) - of["start"]) <= 1, (j, int(g["start"]), of["start"])
+        assert abs(float(g["f0"]) - of["f0"]) <= 1e-3, (j, float(g["f0"]), of["f0"])
+        if int(g["start"]) == of["start"]:
+            ga = g["amp"][:, 0] + 1j * g["amp"][:, 1]
+            assert np.max(np.abs(ga - of["amp"])) <= 2e-3 * np.max(np.abs(of["amp"])), j
+    return n_fits
+
+
+def _window(plan, rec):
+    """[first, last) input sample of the baseband k_sub_est decimates for a record."""
+    Q = 32
+    assert plan.nperseg % Q == 0
+    D, sps = plan.nperseg // Q, plan.nperseg // plan.hop
+    Mg = (Q + 2 * sps - 1) // (2 * sps) + 1
+    nb = (plan.t_lo + int(rec["abs_time"])) * plan.hop - Mg * D
+    return nb, nb + (79 * Q + 2 * Mg) * D
+
+
+EDGE_STARTS = (200, 12000, 27900)     # samples: within Mg D = 540 of the slot's head, inside, of its end
+EDGE_F0 = (700.0, 1500.0, 2300.0)
+
+
+def _edge_slot():
+    """One 12 kHz slot of unit noise and three signals at -4 dB -> (float32 [1, 180000], payloads)."""
+    import torch
+    from ft8_demodulator_amd import synth
+    noise, _ = synth.make_slots(1, 0, fs=12000, seeds=[8100])
+    rng = np.random.default_rng(8100)
+    pays = [synth.random_payload(rng) for _ in EDGE_STARTS]
+    tones = torch.as_tensor(np.stack([synth.itones(p) for p in pays]))
+    wav = synth.gfsk_waveforms(tones, 12000, torch.tensor(EDGE_F0, dtype=torch.float64))
+    wav *= np.sqrt(2.0 * 10.0 ** (-4.0 / 10.0))
+    x = noise[0].to(torch.float64)
+    for i, s in enumerate(EDGE_STARTS):
+        x[s:s + wav.shape[1]] += wav[i]
+    return x.to(torch.float32).numpy()[None], pays
+
+
+@pytest.mark.parametrize("key", ["f32", "i16"])
+def test_fits_at_the_slot_edges_match_oracle(gpu, oracle, key):
+    """A signal whose baseband window starts before the slot, one whose window ends past it (both take
+    the range-checked loop of bb_mix_down) and one inside (the vector loads), as float32 and as int16 PCM."""
+    import torch
+    from oracle import subtract as OS
+    x, pays = _edge_slot()
+    if key == "i16":
+        pcm = np.clip(np.round(x / 8.0 * 32767.0), -32767, 32767).astype(np.int16)
+        xd, xs = torch.from_numpy(pcm).cuda(), pcm.astype(np.float64) / 32767.0
+    else:
+        xd, xs = torch.from_numpy(x).cuda(), x
+    n = x.shape[1]
+    recs, plan, gfit = _device_fits(xd, 12000, 2, 2)
+    r = recs[0]
+    assert {bytes(q["payload"]) for q in r} == set(pays)                  # all three decode
+    ofit = OS.fits(xs[0], r, 12000, plan.nperseg, plan.hop, plan.nfft, plan.t_lo, plan.f_lo)
+    where = {}
+    for q, of in zip(r, ofit):
+        if of is not None:
+            lo, hi = _window(plan, q)
+            where[pays.index(bytes(q["payload"]))] = (lo < 0, hi > n)
+    assert where == {0: (True, False), 1: (False, False), 2: (False, True)}, where
+    assert _check_fits(gfit[0], ofit) == 3
+
+
+def test_fits_at_10k_match_oracle(gpu, oracle):
+    """fs = 10000 at 4 bins per tone and 4 steps per symbol: nsps 1600, Q 32, D 50 -- no window of
+    bb_mix_down takes the four-sample loads."""
+    from ft8_demodulator_amd import synth
+    from oracle import subtract as OS
+    x, truth = synth.make_slots(1, 2, fs=10000, snr_db=-5.0, f0_range=(300.0, 2500.0), seeds=[8200])
+    recs, plan, gfit = _device_fits(x.cuda(), 10000, 4, 4)
+    assert plan.nperseg == 1600 and (plan.nperseg // 32) % 4 != 0
+    r = recs[0]
+    assert {bytes(q["payload"]) for q in r} == {bytes(p) for p in truth[0].payloads}
+    ofit = OS.fits(x[0].numpy(), r, 10000, plan.nperseg, plan.hop, plan.nfft, plan.t_lo, plan.f_lo)
+    assert _check_fits(gfit[0], ofit) == 2
