@@ -164,8 +164,10 @@ def fit_record(x, rec, fs, nsps, hop, nfft, t_lo, f_lo, P=None):
             "metric": metric}
 
 
-def fits(x, records, fs, nsps, hop, nfft, t_lo, f_lo):
-    """Fits of a slot's records in record order; None for a failed record or a repeated payload."""
+def fits(x, records, fs, nsps, hop, nfft, t_lo, f_lo, cache=None):
+    """Fits of a slot's records in record order; None for a failed record or a repeated payload (one
+    an earlier ok record of the slot carries: a failed record shadows nothing).  cache: a dict the
+    caller keeps for these samples and this geometry; lists that share a record share its fit."""
     P = pulse_table(nsps)
     seen, out = set(), []
     for r in records:
@@ -174,7 +176,13 @@ def fits(x, records, fs, nsps, hop, nfft, t_lo, f_lo):
             out.append(None)
             continue
         seen.add(pay)
-        out.append(fit_record(x, r, fs, nsps, hop, nfft, t_lo, f_lo, P))
+        key = (pay, int(r["abs_time"]), int(r["abs_freq"]))
+        fit = cache.get(key) if cache is not None else None
+        if fit is None:
+            fit = fit_record(x, r, fs, nsps, hop, nfft, t_lo, f_lo, P)
+            if cache is not None:
+                cache[key] = fit
+        out.append(fit)
     return out
 
 
@@ -209,6 +217,17 @@ def residual(x, fit_list, nsps, fs):
         n, s = waveform(f, nsps, fs, len(x), P)
         acc[n] += s
     return x.astype(np.float64) - acc
+
+
+def merge(recs1, recs2):
+    """The records of an FT8_FLAG_SUBTRACT batch for one slot (csrc/subtract.hip k_merge): the pass-1
+    rows as they are, then the ok pass-2 rows whose payload no pass-1 row carries, in pass-2 order,
+    with pass_index 1.  recs1, recs2: structured ft8_result arrays -> one such array."""
+    seen = {bytes(r["payload"]) for r in recs1}
+    new = np.array([j for j, r in enumerate(recs2) if r["ok"] and bytes(r["payload"]) not in seen], dtype=np.int64)
+    tail = recs2[new].copy()
+    tail["pass_index"] = 1
+    return np.concatenate([recs1, tail])
 
 
 def decode_topk(x, fs, N, min_score, max_iterations, bpt=2, sps=2):

@@ -50,10 +50,16 @@ def test_subtract_pass2_matches_oracle(gpu, oracle):
     xs = x.cpu().numpy()
     gres = resid.cpu().numpy()
     recs2 = SlotDecoder(12000, 2, 2, K, MIN_SCORE, ITERS, flags=_lib.FT8_FLAG_TOPK).records(resid)
-    one_call = SlotDecoder(12000, 2, 2, K, MIN_SCORE, ITERS,
-                           flags=_lib.FT8_FLAG_TOPK | _lib.FT8_FLAG_SUBTRACT).records(x)
+    one = SlotDecoder(12000, 2, 2, K, MIN_SCORE, ITERS, flags=_lib.FT8_FLAG_TOPK | _lib.FT8_FLAG_SUBTRACT)
+    one_call = one.records(x)
+    # the one-call batch's raw output: every row of the buffer and the counts as k_merge wrote them
+    out_m, counts_m = one.run(x)
+    torch.cuda.synchronize()
+    counts_m = counts_m.cpu().numpy()
+    raw_m = out_m[:N_SLOTS * one.cap * _lib.RESULT_DTYPE.itemsize].cpu().numpy().view(_lib.RESULT_DTYPE)
+    raw_m = raw_m.reshape(N_SLOTS, one.cap)
 
-    n_fits = n_start_off = 0
+    n_fits = n_start_off = n_new = 0
     for s in range(N_SLOTS):
         r1 = recs[s]
         p1 = {bytes(r["payload"]) for r in r1}
@@ -85,9 +91,23 @@ def test_subtract_pass2_matches_oracle(gpu, oracle):
         new_o = {pay for pay, _, _ in OS.decode_topk(ores.astype(np.float32), 12000, K, MIN_SCORE, ITERS)} - o1
         assert new_g == new_o, s
         assert {bytes(r["payload"]) for r in one_call[s] if r["pass_index"] == 1} == new_g, s
+        # the merge, row for row (oracle/subtract.py merge): the pass-1 rows byte for byte, then the ok
+        # pass-2 rows decoded from the device residual whose payload no pass-1 row carries, in pass-2
+        # order, byte for byte but for pass_index 1; the count is that of both
+        want = OS.merge(r1, recs2[s])
+        c1 = len(r1)
+        assert c1 > 0 and np.all(r1["pass_index"] == 0) and np.all(recs2[s]["pass_index"] == 0)
+        assert int(counts_m[s]) == len(want) <= one.cap, (s, int(counts_m[s]), len(want))
+        got = raw_m[s, :len(want)]
+        assert got[:c1].tobytes() == r1.tobytes(), s
+        assert list(got[c1:]["pass_index"]) == [1] * (len(want) - c1), s
+        assert got[c1:].tobytes() == want[c1:].tobytes(), s
+        assert len(one_call[s]) == len(want) and one_call[s].tobytes() == want.tobytes(), s
+        n_new += len(want) - c1
     assert n_fits >= 3 * N_SLOTS
     assert n_start_off <= max(1, n_fits // 20)
-    print(f"subtract oracle: {n_fits} fits, {n_start_off} with start +-1")
+    assert n_new >= 1                                                 # the merge appended something
+    print(f"subtract oracle: {n_fits} fits, {n_start_off} with start +-1, {n_new} rows appended by the merge")
 
 
 # ---- the paths of the baseband front end (csrc/baseband.h) that a crowded slot does not take ----------
@@ -118,21 +138,10 @@ def _device_fits(x, fs, bpt, sps):
 
 
 def _check_fits(gfit, ofit):
-    """Every device fit of one slot against the oracle's fit of the same record -> the number compared."""
-    n_fits = 0
-    for j, of in enumerate(ofit):
-        g = gfit[j]
-        assert int(g["active"]) == (of is not None), j
-        if of is None:
-            continue
-        n_fits += 1
-        assert list(g["tones"][:79]) == list(of["tones"])
-        assert abs(int(g["start"]) - of["start"]) <= 1, (j, int(g["start"]), of["start"])
-        assert abs(float(g["f0"]) - of["f0"]) <= 1e-3, (j, float(g["f0"]), of["f0"])
-        if int(g["start"]) == of["start"]:
-            ga = g["amp"][:, 0] + 1j * g["amp"][:, 1]
-            assert np.max(np.abs(ga - of["amp"])) <= 2e-3 * np.max(np.abs(of["amp"])), j
-    return n_fits
+    """Every device fit of one slot against the oracle's fit of the same record -> the number compared
+    (the comparison and its tolerances: subtract_cases.check_fits, shared with test_gpu_subtract_lists.py)."""
+    from subtract_cases import check_fits
+    return check_fits(gfit, ofit)[0]
 
 
 def _window(plan, rec):
