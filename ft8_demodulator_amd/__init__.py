@@ -25,4 +25,4 @@ from ._pipeline import SlotDecoder, decode_slots  # noqa: E402,F401
 from .message import CallsignTable, hash_call, pack77, pack_telemetry, unpack77  # noqa: E402,F401
 from .snr import snr_reference  # noqa: E402,F401
 from .ap import ap_hypothesis, ap_index  # noqa: E402,F401
-from .coherent import coherent_index, coherent_restate, drift_index  # noqa: E402,F401
+from .coherent import coherent_index, coherent_restate, drift_index, multisymbol_index  # noqa: E402,F401

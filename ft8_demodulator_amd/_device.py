@@ -163,13 +163,15 @@ def ap_decode(llrs, records, max_iterations):
 
 
 def coherent_llr(samples, cand, slot_of, sample_rate=12000, bins_per_tone=2, steps_per_symbol=2, t_lo=0, f_lo=0,
-                 code=None, drift=None):
+                 code=None, drift=None, nsym=1):
     """ft8_coherent_llr: samples [n_slots, n_samples] (float32, or int16 PCM; NumPy or a GPU tensor with
     its ft8 dtype `code`), candidates cand [n, 2] = (abs_time, abs_freq) of the slots slot_of [n]
     -> (LLRs float64 [n, 174], fits coherent.FIT_DTYPE [n]).  drift = (max_rate, n_rates):
-    ft8_coherent_drift_llr -> (LLRs, fits, drifts coherent.DRIFT_DTYPE [n])."""
+    ft8_coherent_drift_llr -> (LLRs, fits, drifts coherent.DRIFT_DTYPE [n]).  nsym = S > 1:
+    ft8_coherent_nsym_llr -> LLRs [n, S, 174], and the validity bytes uint8 [n] come last."""
     from ._pipeline import device_samples
-    from .coherent import DRIFT_DTYPE, FIT_DTYPE
+    from .coherent import DRIFT_DTYPE, FIT_DTYPE, check_nsym
+    S = check_nsym(nsym)
     torch = _lib.require_gpu()
     ctx = _lib.context()
     x = samples
@@ -195,6 +197,19 @@ def coherent_llr(samples, cand, slot_of, sample_rate=12000, bins_per_tone=2, ste
     d_so = torch.from_numpy(np.concatenate([so, np.zeros(1, np.int32)])).to(x.device)
     d_llr = torch.zeros(max(n, 1), 174, dtype=torch.float64, device=x.device)
     d_fit = torch.zeros(max(n, 1) * FIT_DTYPE.itemsize, dtype=torch.uint8, device=x.device)
+    if S > 1:
+        d_llr = torch.zeros(max(n, 1), S, 174, dtype=torch.float64, device=x.device)
+        d_dr = torch.zeros(max(n, 1) * DRIFT_DTYPE.itemsize, dtype=torch.uint8, device=x.device)
+        d_v = torch.zeros(max(n, 1), dtype=torch.uint8, device=x.device)
+        a, r = (0.0, 1) if drift is None else (float(drift[0]), int(drift[1]))
+        ctx.check(_lib.lib().ft8_coherent_nsym_llr(ctx.handle, _lib.ptr(x), int(code), ns, n_slots, ns, ctypes.byref(p),
+                                                   _lib.ptr(d_c), _lib.ptr(d_so), n, a, r, _lib.ptr(d_llr),
+                                                   _lib.ptr(d_fit), _lib.ptr(d_dr), S, _lib.ptr(d_v),
+                                                   _lib.stream_handle()), "ft8_coherent_nsym_llr")
+        out = (d_llr.cpu().numpy()[:n], d_fit.cpu().numpy()[: n * FIT_DTYPE.itemsize].view(FIT_DTYPE).copy())
+        if drift is not None:
+            out += (d_dr.cpu().numpy()[: n * DRIFT_DTYPE.itemsize].view(DRIFT_DTYPE).copy(),)
+        return out + (d_v.cpu().numpy()[:n].copy(),)
     if drift is not None:
         d_dr = torch.zeros(max(n, 1) * DRIFT_DTYPE.itemsize, dtype=torch.uint8, device=x.device)
         ctx.check(_lib.lib().ft8_coherent_drift_llr(ctx.handle, _lib.ptr(x), int(code), ns, n_slots, ns, ctypes.byref(p),

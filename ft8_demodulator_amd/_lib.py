@@ -175,6 +175,9 @@ def lib():
             "ft8_set_coherent_drift": ([vp, ctypes.c_float, i32], ctypes.c_int),
             "ft8_coherent_drift_llr": ([vp, vp, ctypes.c_int, i64, i32, i64, P, vp, vp, i32, ctypes.c_float, i32, vp, vp,
                                         vp, vp], ctypes.c_int),
+            "ft8_set_coherent_nsym": ([vp, i32], ctypes.c_int),
+            "ft8_coherent_nsym_llr": ([vp, vp, ctypes.c_int, i64, i32, i64, P, vp, vp, i32, ctypes.c_float, i32, vp, vp,
+                                       vp, i32, vp, vp], ctypes.c_int),
         }
         stale_ok = os.environ.get("FT8HIP_ALLOW_STALE") == "1"
         for name, (args, res) in sig.items():
@@ -227,7 +230,7 @@ EXPORTED_SYMBOLS = (
     "ft8_pack_bytes", "ft8_pack_decodes", "ft8_subtract_fits", "ft8_stft_method", "ft8_stft_screen_stats",
     "ft8_unpack77", "ft8_unpack77_host", "ft8_hash_call", "ft8_noise_floor", "ft8_snr", "ft8_snr_last",
     "ft8_set_ap", "ft8_ap_decode", "ft8_set_coherent", "ft8_coherent_llr",
-    "ft8_set_coherent_drift", "ft8_coherent_drift_llr")
+    "ft8_set_coherent_drift", "ft8_coherent_drift_llr", "ft8_set_coherent_nsym", "ft8_coherent_nsym_llr")
 
 
 def limits():
@@ -327,6 +330,11 @@ class Context:
         rates over +-max_rate_hz_per_s (<= 4 Hz/s); (0, 1): off."""
         self.check(lib().ft8_set_coherent_drift(self.handle, float(max_rate_hz_per_s), int(n_rates)),
                    "ft8_set_coherent_drift")
+
+    def set_coherent_nsym(self, max_nsym: int = 1):
+        """ft8_set_coherent_nsym: an FT8_FLAG_COHERENT batch also decodes joint LLRs over 2 .. max_nsym
+        (<= 3) symbols; 1: off."""
+        self.check(lib().ft8_set_coherent_nsym(self.handle, int(max_nsym)), "ft8_set_coherent_nsym")
 
     def replay(self, stage: str, reps: int = 1, stream=None):
         """ft8_replay_stage: re-launch one kernel of the last ft8_decode_batch `reps` times."""

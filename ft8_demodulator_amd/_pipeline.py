@@ -227,7 +227,7 @@ class SlotDecoder:
     def __init__(self, sample_rate=12000, bins_per_tone=2, steps_per_symbol=2, max_candidates=20,
                  min_score=10, max_iterations=20, freq_min=None, freq_max=None, time_min=None,
                  time_max=None, device=None, flags=0, max_results_per_slot=None, context=None, ap=None,
-                 ap_max_hard_errors=None, coherent=None, coherent_drift=None):
+                 ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1):
         """ap: a-priori patterns (ap.ap_hypothesis, e.g. ["CQ ? ?", "K1ABC ? ?"], tried in order on every
         candidate BP fails on; at most 8) -- sets FT8_FLAG_AP; None: plain decoding.  ap_max_hard_errors:
         the most hard decisions of an accepted AP decode that may contradict the received LLRs' signs
@@ -237,9 +237,14 @@ class SlotDecoder:
         (coherent.py) and decoded from those LLRs; None / False: off.
         coherent_drift: True or (max_rate Hz/s, n_rates) -- the coherent pass also searches n_rates (odd,
         <= 33) linear frequency drift rates over +-max_rate (<= 4; True: 1.0, 9) for every listed
-        candidate (ft8_set_coherent_drift); needs coherent.  None / False: off."""
+        candidate (ft8_set_coherent_drift); needs coherent.  None / False: off.
+        coherent_nsym: 1, 2 or 3 -- the coherent pass also decodes joint LLRs over 2 .. coherent_nsym symbols
+        for every listed candidate (ft8_set_coherent_nsym); more than 1 needs coherent.  1: off."""
         from . import ap as _ap
         from . import coherent as _coh
+        self.coherent_nsym = _coh.check_nsym(coherent_nsym)   # ValueError for what the library refuses
+        if self.coherent_nsym > 1 and (coherent is None or coherent is False):
+            raise ValueError("coherent_nsym needs coherent")
         if coherent_drift is None or coherent_drift is False:
             self.coherent_drift = None
         else:
@@ -327,6 +332,7 @@ class SlotDecoder:
         if self.coherent is not None:
             self.ctx.set_coherent(self.coherent)
             self.ctx.set_coherent_drift(*(self.coherent_drift or (0.0, 1)))
+            self.ctx.set_coherent_nsym(self.coherent_nsym)
         rc = _lib.lib().ft8_decode_batch(self.ctx.handle, _lib.ptr(x), int(code), n, n_slots, n,
                                          ctypes.byref(p), _lib.ptr(out), _lib.ptr(counts), self.cap,
                                          _lib.stream_handle(torch.device("cuda", self.device)))
@@ -446,7 +452,7 @@ def decode_slots(samples, sample_rate=12000, **kwargs):
 
 def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_candidates=20, min_score=10,
                max_iterations=20, freq_min=None, freq_max=None, time_min=None, time_max=None, *, flags=0, snr=False,
-               ap=None, ap_max_hard_errors=None, coherent=None, coherent_drift=None):
+               ap=None, ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1):
     """One slot, x [N] on the GPU with its ft8 dtype code, through a SlotDecoder of its own:
     -> (decode_ft8_message's 5-tuples, with snr the ft8_snr_rec records aligned with them else None,
     the ft8_result records).  Nothing is launched when the masks leave nothing or max_candidates <= 0."""
@@ -456,7 +462,8 @@ def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_ca
     if not plan.empty and max_candidates > 0:
         dec = SlotDecoder(sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score, max_iterations,
                           freq_min, freq_max, time_min, time_max, device=x.device, flags=flags, ap=ap,
-                          ap_max_hard_errors=ap_max_hard_errors, coherent=coherent, coherent_drift=coherent_drift)
+                          ap_max_hard_errors=ap_max_hard_errors, coherent=coherent, coherent_drift=coherent_drift,
+                          coherent_nsym=coherent_nsym)
         recs, _, reps = (v if v is None else v[0] for v in dec._fetch(x.unsqueeze(0), code, snr=snr))
     wf_f64 = code in (_lib.FT8_F64, _lib.FT8_C128)
     return records_to_results(recs, sample_rate, bins_per_tone, wf_f64), reps, recs

@@ -4,7 +4,8 @@
 A candidate that belief propagation fails on is demodulated again from the slot's samples instead of
 the Hann STFT's dB bins: mixed down and box-car decimated to Q samples per symbol, fine-synchronised
 on the 21 Costas symbols (start offsets of D samples, tone-0 offsets of a quarter bin), and its LLRs
-formed from matched rectangular symbol windows at the refined point.  The device runs it
+formed from matched rectangular symbol windows at the refined point; with nsym > 1 further LLR vectors
+come from joint metrics over 2 and 3 adjacent symbols (the header's step 4b).  The device runs it
 (csrc/coherent.hip); this module restates it for tests and tools.  Nothing here runs on the decode
 path.
 """
@@ -34,6 +35,7 @@ STATUS_VALID, STATUS_NOTHING, STATUS_NOT_ATTEMPTED = 0, 2, 3
 DRIFT_DTYPE = np.dtype([("rate_hz_per_s", "<f4"), ("rate_index", "<i4")])
 MAX_DRIFT_RATES, MAX_DRIFT_HZ_PER_S = 33, 4.0
 DEFAULT_DRIFT = (1.0, 9)           # SlotDecoder(coherent_drift=True)
+MAX_NSYM = 3                       # ft8_set_coherent_nsym: joint metrics over up to 3 symbols
 
 
 def sub_q(nsps: int) -> int:
@@ -63,6 +65,46 @@ def coherent_index(record) -> int:
 def drift_index(record) -> int:
     """1 when the record was rescued at a drift rate other than 0 (pass_index bit 2), else 0."""
     return (int(record["pass_index"]) >> 2) & 1
+
+
+def multisymbol_index(record) -> int:
+    """1 when the record was rescued by a joint metric over 2 or 3 symbols (pass_index bit 3), else 0."""
+    return (int(record["pass_index"]) >> 3) & 1
+
+
+def check_nsym(nsym) -> int:
+    """max_nsym as ft8_set_coherent_nsym takes it; ValueError for what it answers with FT8_E_ARG."""
+    S = int(nsym)
+    if S != nsym or S < 1 or S > MAX_NSYM:
+        raise ValueError(f"coherent nsym: max_nsym must be in [1, {MAX_NSYM}]")
+    return S
+
+
+def symbol_groups(n: int):
+    """The groups of step 4b for n symbols per group: each half (symbols 7 .. 35, 43 .. 71) cut in order
+    into groups of n with a shorter last group -> list of tuples of symbol indices."""
+    out = []
+    for lo in (7, 43):
+        half = list(range(lo, lo + 29))
+        out += [tuple(half[i:i + n]) for i in range(0, 29, n)]
+    return out
+
+
+def _joint_llr(cp: np.ndarray, n: int) -> np.ndarray:
+    """cp [79, 8] rotated correlations (zeros for absent symbols) -> the 174 joint LLRs of set n before
+    the normalisation (step 4b, items 3 and 4)."""
+    L = np.zeros((79, 3), dtype=np.float64)
+    g2 = cp[:, GRAY]                       # g2[k, j]: the tone that carries the bits of j
+    zero = np.zeros(1, dtype=np.complex128)
+    for grp in symbol_groups(n):
+        a, b, c = [g2[k] for k in grp] + [zero] * (3 - len(grp))
+        s = 10.0 * np.log10(1e-12 + np.abs(a[:, None, None] + b[None, :, None] + c[None, None, :]) ** 2)
+        for i, k in enumerate(grp):
+            m = np.moveaxis(s, i, 0).reshape(8, -1).max(axis=1)     # best tuple per value of a_i
+            L[k] = (m[[4, 5, 6, 7]].max() - m[[0, 1, 2, 3]].max(),
+                    m[[2, 3, 6, 7]].max() - m[[0, 1, 4, 5]].max(),
+                    m[[1, 3, 5, 7]].max() - m[[0, 2, 4, 6]].max())
+    return L[list(DATA_SYMBOLS)].reshape(174)
 
 
 def drift_rates(max_rate, n_rates) -> np.ndarray:
@@ -98,12 +140,17 @@ def _llr_of_spectra(s: np.ndarray) -> np.ndarray:
 
 
 def coherent_restate(samples, cand, slot_of, fs, nperseg, nfft, steps_per_symbol, t_lo=0, f_lo=0, details=False,
-                     drift=None):
+                     drift=None, nsym=1):
     """samples [n_slots, n_samples] (float32, or int16 PCM), cand [n, 2] = (abs_time, abs_freq), slot_of [n]
     -> (llr float64 [n, 174], fits FIT_DTYPE [n]); with details also the list of every candidate's
     metric grid [2 Mt + 1, 5] (None where no sync symbol was present).
     drift = (max_rate, n_rates): the search over linear drift rates (drift_rates; the header's step 1b)
-    -> (llr, fits, drifts DRIFT_DTYPE [n]) and with details the metric volumes [R, 2 Mt + 1, 5]."""
+    -> (llr, fits, drifts DRIFT_DTYPE [n]) and with details the metric volumes [R, 2 Mt + 1, 5].
+    nsym = S > 1: the joint metrics over 2 .. S symbols (the header's step 4b): llr is [n, S, 174], set 1
+    computed as without nsym, and a `valid` uint8 [n] follows the fits (and drifts): bit s - 1 for a valid set
+    s; with details the list of every candidate's rotated correlations c' [79, 8] (None where none were
+    formed) comes last."""
+    S = check_nsym(nsym)
     rates = None if drift is None else drift_rates(*drift)
     x_all = np.asarray(samples)
     if x_all.ndim == 1:
@@ -128,6 +175,9 @@ def coherent_restate(samples, cand, slot_of, fs, nperseg, nfft, steps_per_symbol
     llr = np.zeros((n, 174), dtype=np.float64)
     fits = np.zeros(n, dtype=FIT_DTYPE)
     drifts = np.zeros(n, dtype=DRIFT_DTYPE)
+    llr_n = np.zeros((n, S, 174), dtype=np.float64)
+    valid = np.zeros(n, dtype=np.uint8)
+    rotated = [None] * n
     # centre of decimation block m relative to the centre of the nominal signal, squared
     tau2 = (((np.arange(Mz) - Mg + 0.5) * D - 39.5 * nperseg) / fs) ** 2
     grids = []
@@ -199,9 +249,30 @@ def coherent_restate(samples, cand, slot_of, fs, nperseg, nfft, steps_per_symbol
             continue
         llr[i] = L * np.sqrt(24.0 / var)
         f["status"] = STATUS_VALID
+        if S == 1:
+            continue
+        # 4b. joint LLRs over groups of 2 .. S symbols from the phase-continued correlations
+        llr_n[i, 0], valid[i] = llr[i], 1
+        k79 = np.arange(79)
+        cyc = (df / TONE_HZ - 3.5) * k79
+        cp = (W[di] @ E.T) * present[di][:, None] * np.exp(-2j * np.pi * (cyc - np.floor(cyc)))[:, None]
+        rotated[i] = cp
+        for m in range(2, S + 1):
+            Lm = _joint_llr(cp, m)
+            var = np.mean((Lm - np.mean(Lm)) ** 2)
+            if var > 0.0:
+                llr_n[i, m - 1] = Lm * np.sqrt(24.0 / var)
+                valid[i] |= 1 << (m - 1)
+    out = (llr, fits) if S == 1 else (llr_n, fits)
     if rates is not None:
-        return (llr, fits, drifts, grids) if details else (llr, fits, drifts)
-    return (llr, fits, grids) if details else (llr, fits)
+        out += (drifts,)
+    if S > 1:
+        out += (valid,)
+    if details:
+        out += (grids,)
+        if S > 1:
+            out += (rotated,)
+    return out
 
 
 def near_tie(metric, rel=1e-5) -> bool:

@@ -124,16 +124,19 @@ struct RetryView {
 struct RetryScratch {
   DevBuf list, count, cand, score, llr, res;
   int M = 0;
-  int ensure(ft8_ctx* c, size_t n_slots, int M_) {
+  size_t n_all = 0;  // list positions of all chunks: the distance between two sets' LLRs and records
+  // sets: LLR vectors and records per list position (the coherent pass's multi-symbol sets), set-major
+  int ensure(ft8_ctx* c, size_t n_slots, int M_, int sets = 1) {
     const size_t n = n_slots * (size_t)M_;
     M = M_;
+    n_all = n;
     int rc;
     if ((rc = ::ensure(c, list, sizeof(int32_t) * n))) return rc;
     if ((rc = ::ensure(c, count, sizeof(int32_t) * n_slots))) return rc;
     if ((rc = ::ensure(c, cand, sizeof(int32_t) * 2 * n))) return rc;
     if ((rc = ::ensure(c, score, sizeof(double) * n))) return rc;
-    if ((rc = ::ensure(c, llr, sizeof(double) * FT8_LDPC_N * n))) return rc;
-    return ::ensure(c, res, sizeof(ft8_result) * n);
+    if ((rc = ::ensure(c, llr, sizeof(double) * FT8_LDPC_N * n * sets))) return rc;
+    return ::ensure(c, res, sizeof(ft8_result) * n * sets);
   }
   RetryView at(RetryLists in, int slot0) const {
     const size_t r0 = (size_t)slot0 * M;
@@ -208,6 +211,9 @@ struct ft8_ctx {
   float coh_drift_rate = 0.f;
   int coh_drift_n = 1;
   DevBuf coh_drift;
+  // its multi-symbol sets (ft8_set_coherent_nsym; off: 1) and the validity byte per list position
+  int coh_nsym = 1;
+  DevBuf coh_valid;
   // the stream of the last entry point that enqueued work, and an event recorded on it after that
   // work (StreamOrder): a call on another stream first waits for it
   hipStream_t last_stream = nullptr;
@@ -959,11 +965,11 @@ int baseband_setup(ft8_ctx* c, const void* x, int dtype, int64_t n_samples, int 
 // ---- coherent re-demodulation -------------------------------------------------------------------
 // the checks ft8_coherent_llr and FT8_FLAG_COHERENT share; fills the launch's baseband
 int coherent_setup(ft8_ctx* c, const void* x, int dtype, int64_t n_samples, int n_slots, int64_t slot_stride,
-                   const ft8_params* p, CohLaunch* L) {
+                   const ft8_params* p, bool multi, CohLaunch* L) {
   *L = CohLaunch{};
   const int rc = baseband_setup(c, x, dtype, n_samples, n_slots, slot_stride, p, "coherent re-demodulation", &L->b);
   if (rc) return rc;
-  if (coherent_lds_bytes(L->b.nsps, L->b.Q) > 64 * 1024)
+  if (coherent_lds_bytes(L->b.nsps, L->b.Q, multi) > 64 * 1024)
     return fail(c, FT8_E_RANGE, "coherent re-demodulation: the decimation's twiddle table does not fit 64 KB of LDS");
   return FT8_OK;
 }
@@ -977,20 +983,27 @@ int check_coherent_drift(ft8_ctx* c, float max_rate, int n_rates) {
   return FT8_OK;
 }
 
+// the set count, as ft8_coherent_nsym_llr and ft8_set_coherent_nsym take it
+int check_coherent_nsym(ft8_ctx* c, int max_nsym) {
+  if (max_nsym < 1 || max_nsym > 3) return fail(c, FT8_E_ARG, "coherent nsym: max_nsym must be in [1, 3]");
+  return FT8_OK;
+}
+
 // listed candidates per slot of an FT8_FLAG_COHERENT batch
 int coherent_cap(const ft8_ctx* c, int N) { return c->coh_max > 0 ? std::min(c->coh_max, N) : N; }
 
 // the coherent pass's scratch for n_slots lists of M candidates (ft8hip.h states the sizes)
 int ensure_coh_scratch(ft8_ctx* c, size_t n_slots, int M) {
-  int rc = c->coh.ensure(c, n_slots, M);
+  int rc = c->coh.ensure(c, n_slots, M, c->coh_nsym);
   if (!rc) rc = ensure(c, c->coh_fit, sizeof(ft8_coh_fit) * n_slots * M);
+  if (!rc && c->coh_nsym > 1) rc = ensure(c, c->coh_valid, n_slots * M);
   if (!rc && coherent_drift_on(CohDrift{c->coh_drift_rate, c->coh_drift_n, nullptr}))
     rc = ensure(c, c->coh_drift, sizeof(ft8_coh_drift) * n_slots * M);
   return rc;
 }
 
 // The coherent pass over the records `failed` describes, one chunk's (coherent.hip): list, k_coherent,
-// k_bp over the lists, merge.  Like ap_pass, its scratch starts at slot `slot0` of the buffers
+// then per set k_bp over the lists and the merge, on one claim counter as ap_pass's hypotheses.  Like ap_pass, its scratch starts at slot `slot0` of the buffers
 // ensure_coh_scratch sized and `counter` is the k_bp claim counter its launch draws its tickets from.
 // L: coherent_setup's launch for the chunk's samples.
 int coherent_pass(ft8_ctx* c, CohLaunch L, const RetryLists& failed, int slot0, int max_iterations, int counter,
@@ -1009,11 +1022,20 @@ int coherent_pass(ft8_ctx* c, CohLaunch L, const RetryLists& failed, int slot0, 
   L.fit = fit;
   CohDrift G{c->coh_drift_rate, c->coh_drift_n, nullptr};
   if (coherent_drift_on(G)) G.out = c->coh_drift.as<ft8_coh_drift>() + (size_t)slot0 * l.M;
-  if ((e = launch_coherent(L, G, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
-  if ((e = bp_over_lists(c, l, v.llr, nullptr, v.res, max_iterations, counter, s)) != hipSuccess)
-    return hipfail(c, e, "coherent bp launch");
-  const CohPass A{l, fit, v.res, G.out};
-  if ((e = launch_coh_merge(A, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
+  // set n of the chunk's positions: n_all positions after set n - 1's, in the LLRs and in the records
+  const int S = c->coh_nsym;
+  const size_t n_all = c->coh.n_all;
+  CohMulti Ms{S, FT8_LDPC_N, (int64_t)(FT8_LDPC_N * n_all), nullptr};
+  if (S > 1) Ms.valid = c->coh_valid.as<uint8_t>() + (size_t)slot0 * l.M;
+  if ((e = launch_coherent(L, G, Ms, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
+  for (int n = 0; n < S; ++n) {
+    const double* llr_n = v.llr + (size_t)n * Ms.set_stride;
+    ft8_result* res_n = v.res + (size_t)n * n_all;
+    if ((e = bp_over_lists(c, l, llr_n, nullptr, res_n, max_iterations, counter, s)) != hipSuccess)
+      return hipfail(c, e, "coherent bp launch");
+    const CohPass A{l, fit, res_n, G.out, Ms.valid, n};
+    if ((e = launch_coh_merge(A, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
+  }
   return FT8_OK;
 }
 
@@ -1102,7 +1124,7 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     failed.N = N;
     if (coh) {
       CohLaunch L;
-      if ((rc = coherent_setup(c, xs, dtype, n_samples, ns, slot_stride, p, &L))) return rc;
+      if ((rc = coherent_setup(c, xs, dtype, n_samples, ns, slot_stride, p, c->coh_nsym > 1, &L))) return rc;
       if ((rc = coherent_pass(c, L, failed, c0, p->max_iterations, bp_counter(kChunkCoherent, k, n_chunks), cs)))
         return rc;
     }
@@ -1561,6 +1583,14 @@ int ft8_set_coherent_drift(ft8_ctx* c, float max_rate_hz_per_s, int32_t n_rates)
   return FT8_OK;
 }
 
+int ft8_set_coherent_nsym(ft8_ctx* c, int32_t max_nsym) {
+  if (!c) return FT8_E_ARG;
+  const int rc = check_coherent_nsym(c, max_nsym);
+  if (rc) return rc;
+  c->coh_nsym = max_nsym;
+  return FT8_OK;
+}
+
 int ft8_coherent_llr(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
                      int64_t slot_stride, const ft8_params* p, const int32_t* d_cand, const int32_t* d_slot_of,
                      int32_t n, double* d_llr_out, ft8_coh_fit* d_fit_out, void* stream) {
@@ -1572,16 +1602,26 @@ int ft8_coherent_drift_llr(ft8_ctx* c, const void* d_samples, int dtype, int64_t
                            int64_t slot_stride, const ft8_params* p, const int32_t* d_cand,
                            const int32_t* d_slot_of, int32_t n, float max_rate_hz_per_s, int32_t n_rates,
                            double* d_llr_out, ft8_coh_fit* d_fit_out, ft8_coh_drift* d_drift_out, void* stream) {
+  return ft8_coherent_nsym_llr(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, d_cand, d_slot_of, n,
+                               max_rate_hz_per_s, n_rates, d_llr_out, d_fit_out, d_drift_out, 1, nullptr, stream);
+}
+
+int ft8_coherent_nsym_llr(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
+                          int64_t slot_stride, const ft8_params* p, const int32_t* d_cand,
+                          const int32_t* d_slot_of, int32_t n, float max_rate_hz_per_s, int32_t n_rates,
+                          double* d_llr_out, ft8_coh_fit* d_fit_out, ft8_coh_drift* d_drift_out, int32_t max_nsym,
+                          uint8_t* d_valid_out, void* stream) {
   if (c) c->replay_ok = c->snr_ok = false;
   if (!c || !p || n < 0 || n_slots < 0 || n_samples < 0 || slot_stride < n_samples ||
       (n > 0 && (!d_samples || !d_cand || !d_slot_of || !d_llr_out || !d_fit_out)))
     return fail(c, FT8_E_ARG, "bad argument");
   if (p->steps_per_symbol <= 0 || p->bins_per_tone <= 0) return fail(c, FT8_E_ARG, "bad oversampling factors");
   int rc = check_coherent_drift(c, max_rate_hz_per_s, n_rates);
+  if (!rc) rc = check_coherent_nsym(c, max_nsym);
   if (rc) return rc;
   DeviceGuard dg(c->device);
   CohLaunch L;
-  rc = coherent_setup(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, &L);
+  rc = coherent_setup(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, max_nsym > 1, &L);
   if (rc) return rc;
   if (n == 0) return FT8_OK;
   L.cand = d_cand;
@@ -1596,7 +1636,10 @@ int ft8_coherent_drift_llr(ft8_ctx* c, const void* d_samples, int dtype, int64_t
     const hipError_t e = hipMemsetAsync(d_drift_out, 0, sizeof(ft8_coh_drift) * (size_t)n, s);
     if (e != hipSuccess) return hipfail(c, e, "memset");
   }
-  const hipError_t e = launch_coherent(L, G, s);
+  // [n][max_nsym][174]; one set: the plain or the drift kernel, and the validity bytes from its fits
+  const CohMulti Ms{max_nsym, (int64_t)max_nsym * FT8_LDPC_N, FT8_LDPC_N, d_valid_out};
+  hipError_t e = launch_coherent(L, G, Ms, s);
+  if (e == hipSuccess && max_nsym == 1 && d_valid_out) e = launch_coh_valid1(d_fit_out, d_valid_out, n, s);
   return e == hipSuccess ? FT8_OK : hipfail(c, e, "coherent launch");
 }
 
@@ -1624,7 +1667,8 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
     if (p->flags & FT8_FLAG_SUBTRACT)
       return fail(c, FT8_E_UNSUPPORTED, "FT8_FLAG_COHERENT with FT8_FLAG_SUBTRACT is not supported");
     CohLaunch probe;
-    if ((rc = coherent_setup(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, &probe))) return rc;
+    if ((rc = coherent_setup(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, c->coh_nsym > 1, &probe)))
+      return rc;
   }
   const int T = p->t_hi - p->t_lo, F = p->f_hi - p->f_lo;
   const bool f64 = is_f64_dtype(dtype);

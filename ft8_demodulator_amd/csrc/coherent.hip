@@ -15,9 +15,15 @@
 //        symbols that lie inside the slot); first largest wins, the tone-0 offset refined by a parabola;
 //     3. the 58 x 8 tone spectra at the refined point (matched rectangular windows), the reference's
 //        Gray map and max-of-4 LLRs in double, ftx_normalize_logl with NumPy's pairwise sums.
-//   k_bp         unchanged (launch_bp, mode 0 over the compacted lists)
+//    4b. multi-symbol sets (ft8_set_coherent_nsym / ft8_coherent_nsym_llr only): phase 3 keeps the complex
+//        correlations, rotated to a common phase reference; per group of 2 or 3 adjacent data symbols one
+//        wave forms the power of every joint tone tuple and the per-bit maxima, and each further set is
+//        normalised like the first;
+//   k_bp         unchanged (launch_bp, mode 0 over the compacted lists), once per set
 //   k_coh_merge  one wave per list position: a valid fit whose attempt decoded rewrites its record
 // No atomics; every sample index is range-checked or proven in range in 64-bit arithmetic.
+#include <type_traits>
+
 #include "baseband.h"
 
 namespace ft8 {
@@ -30,6 +36,12 @@ constexpr int kSymbols = kBbSymbols, kSync = 21, kData = 58;
 constexpr double kToneHz = 6.25;
 
 __host__ __device__ inline int coh_rot_words(int Q) { return kCohNF * 8 * (Q + 1); }
+// multi-symbol sets: the 58 x 8 rotated correlations of phase 3 follow rows 0 .. 7 of the rotation table,
+// in rows 8 .. 39, which are dead by then (Q >= 14: they fit; below, the table's allocation grows)
+__host__ __device__ inline int coh_multi_words(int Q) {
+  const int need = 8 * (Q + 1) + kData * 8;
+  return need > coh_rot_words(Q) ? need : coh_rot_words(Q);
+}
 
 __device__ __forceinline__ int costas_tone(int i) {  // 3 1 4 0 6 5 2, packed in nibbles
   return (int)((0x2560413u >> (4 * i)) & 7u);
@@ -38,9 +50,10 @@ __device__ __forceinline__ int gray_map(int j) {     // FT8_Gray_map 0 1 3 2 5 6
   return (int)((0x74652310u >> (4 * j)) & 7u);
 }
 
-// blank LLRs and a fit that carries only its status
-__device__ void coh_blank(double* llr, ft8_coh_fit* fit, int status) {
-  for (int i = threadIdx.x; i < FT8_LDPC_N; i += kCohThreads) llr[i] = 0.0;
+// blank LLRs (of every set) and a fit that carries only its status
+__device__ void coh_blank(double* llr, ft8_coh_fit* fit, int status, int sets = 1, int64_t set_stride = 0) {
+  for (int n = 0; n < sets; ++n)
+    for (int i = threadIdx.x; i < FT8_LDPC_N; i += kCohThreads) llr[n * set_stride + i] = 0.0;
   if (threadIdx.x == 0) {
     ft8_coh_fit f{};
     f.status = (uint8_t)status;
@@ -56,16 +69,24 @@ constexpr int kCohOwn = (kSymbols * kBbMaxQ + 2 * (kBbMaxQ / 2 + 1) + kCohThread
 // exp(-i pi (r_{i+1} - r_i) tau_m^2), a factor that is the same for every i (the rates are equidistant)
 // and that each lane keeps in registers for the elements it owns; only the running best and its two
 // tone-0 neighbours are kept, and one more rotation takes z to the winning rate before phase 3.
-// The drift kernels take the search's settings as a second argument (G = CohDrift); without it
-// (G empty) the kernel and its argument are the plain pass's.
-__device__ __forceinline__ CohDrift coh_drift_arg() { return CohDrift{}; }
-__device__ __forceinline__ CohDrift coh_drift_arg(const CohDrift& g) { return g; }
+// The drift kernels take the search's settings as a further argument (CohDrift among G), the
+// multi-symbol kernels theirs (CohMulti); without either (G empty) the kernel and its argument are the
+// plain pass's.
+template <typename T>
+__device__ __forceinline__ T coh_arg() { return T{}; }
+template <typename T, typename H, typename... R>
+__device__ __forceinline__ T coh_arg(const H& h, const R&... r) {
+  if constexpr (std::is_same_v<T, H>) return h;
+  else return coh_arg<T>(r...);
+}
 
 template <typename InT, typename... G>
-__global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a, G... drift) {
+__global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a, G... opt) {
   FT8_RACE_PROLOGUE();
-  constexpr bool Drift = sizeof...(G) != 0;
-  [[maybe_unused]] const CohDrift g = coh_drift_arg(drift...);
+  constexpr bool Drift = (std::is_same_v<G, CohDrift> || ...);
+  constexpr bool Multi = (std::is_same_v<G, CohMulti> || ...);
+  [[maybe_unused]] const CohDrift g = coh_arg<CohDrift>(opt...);
+  [[maybe_unused]] const CohMulti ms = coh_arg<CohMulti>(opt...);
   // dynamic LDS: z and the D twiddles of phase 1 (baseband.h's layout), then the rotation table
   // [5 * 8][Q + 1] of phase 2 (phase 3 rebuilds its first 8 rows for the refined offset)
   extern __shared__ float4 s_dyn[];
@@ -96,10 +117,19 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a, G... drif
     if (slot >= a.b.n_slots || j >= a.count[slot]) return;
     pos = (int64_t)slot * a.M + j;
   }
-  double* llr_out = a.llr + pos * FT8_LDPC_N;
+  double* llr_out = a.llr + pos * (Multi ? ms.pos_stride : (int64_t)FT8_LDPC_N);
   ft8_coh_fit* fit_out = a.fit + pos;
+  // status 2 or 3: zeros in every set, no set valid
+  auto blank = [&](int status) {
+    if constexpr (Multi) {
+      coh_blank(llr_out, fit_out, status, ms.nsym, ms.set_stride);
+      if (ms.valid && threadIdx.x == 0) ms.valid[pos] = 0;
+    } else {
+      coh_blank(llr_out, fit_out, status);
+    }
+  };
   if (slot < 0 || slot >= a.b.n_slots) {
-    coh_blank(llr_out, fit_out, 3);
+    blank(3);
     if constexpr (Drift)
       if (g.out && threadIdx.x == 0) g.out[pos] = ft8_coh_drift{};
     return;
@@ -128,7 +158,7 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a, G... drif
   }
   __syncthreads();
   if (!s_flag) {
-    coh_blank(llr_out, fit_out, 2);
+    blank(2);
     if constexpr (Drift)
       if (g.out && threadIdx.x == 0) g.out[pos] = ft8_coh_drift{};
     return;
@@ -267,6 +297,12 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a, G... drif
       cy = fmaf(z.x, W.y, fmaf(z.y, W.x, cy));
     }
     s_pow[e] = cx * cx + cy * cy;
+    if constexpr (Multi) {
+      // step 4b, items 1 and 2: c'_k[t], carried to symbol 0's phase reference; 0 for an absent symbol
+      const float2 w = bb_rot((df / kToneHz - 3.5) * (double)k);
+      s_R[8 * (Q + 1) + e] =
+          present(db, k) ? make_float2(cx * w.x - cy * w.y, cx * w.y + cy * w.x) : make_float2(0.f, 0.f);
+    }
   }
   __syncthreads();
   if (threadIdx.x < kData) {  // ft8_extract_symbol in double
@@ -343,6 +379,96 @@ __global__ __launch_bounds__(kCohThreads) void k_coherent(CohLaunch a, G... drif
         g.out[pos] = w;
       }
   }
+  if constexpr (Multi) {
+    // ---- 4b. sets 2 .. S: joint metrics over groups of n adjacent data symbols.  One wave per group:
+    // lane (j1, j2) fixes the first two tones (tone gray_map(j) carries the bits of j), loops over the
+    // third and keeps, per symbol, bit and bit value, the largest power over its tuples; float max is
+    // exact, so the wave reduction's order does not matter.  0 is the identity: powers are >= 0 and
+    // every (symbol, bit, value) has a tuple.  The maxima replace s_pow, which set 1 has consumed.
+    const float2* s_c = s_R + 8 * (Q + 1);
+    float* s_max = s_pow;  // [58][bit][value]
+    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+    const int j1 = lane >> 3, j2 = lane & 7;
+    int vbits = valid ? 1 : 0;
+    // set 1's normalisation above, for a further set (set 1 keeps its own statements: as a call of this
+    // lambda it changed the register allocation of the plain and the drift instantiations)
+    auto normalise = [&](double* out) {
+      const double mean_n = pairwise174(s_llr) / 174.0;
+      for (int i = threadIdx.x; i < FT8_LDPC_N; i += kCohThreads) {
+        const double dd = s_llr[i] - mean_n;
+        s_sq[i] = dd * dd;
+      }
+      __syncthreads();
+      const double var_n = pairwise174(s_sq) / 174.0;
+      const bool ok = var_n > 0.0;
+      const double scale_n = ok ? sqrt(24.0 / var_n) : 0.0;
+      for (int i = threadIdx.x; i < FT8_LDPC_N; i += kCohThreads) out[i] = ok ? s_llr[i] * scale_n : 0.0;
+      return ok;
+    };
+    for (int n = 2; n <= ms.nsym; ++n) {
+      double* out_n = llr_out + (int64_t)(n - 1) * ms.set_stride;
+      if (!valid) {  // workgroup-uniform: an invalid fit has no further sets
+        for (int i = threadIdx.x; i < FT8_LDPC_N; i += kCohThreads) out_n[i] = 0.0;
+        continue;
+      }
+      const int per_half = (29 + n - 1) / n;
+      for (int gi = wave; gi < 2 * per_half; gi += kCohThreads / kWave) {
+        const int h = gi / per_half, r = gi - h * per_half;
+        const int kd0 = 29 * h + r * n, len = min(n, 29 - r * n);
+        const float2 c1 = s_c[kd0 * 8 + gray_map(j1)];
+        const float2 c2 = len > 1 ? s_c[(kd0 + 1) * 8 + gray_map(j2)] : make_float2(0.f, 0.f);
+        const float bx = c1.x + c2.x, by = c1.y + c2.y;
+        float v[18];
+#pragma unroll
+        for (int e = 0; e < 18; ++e) v[e] = 0.f;
+        float pm = 0.f;
+        const int n3 = len > 2 ? 8 : 1;
+        for (int j3 = 0; j3 < n3; ++j3) {
+          const float2 c3 = len > 2 ? s_c[(kd0 + 2) * 8 + gray_map(j3)] : make_float2(0.f, 0.f);
+          const float x = bx + c3.x, y = by + c3.y;
+          const float p = x * x + y * y;
+          pm = fmaxf(pm, p);
+#pragma unroll
+          for (int b = 0; b < 3; ++b) {
+            const bool one = (j3 >> (2 - b)) & 1;
+            v[12 + 2 * b] = fmaxf(v[12 + 2 * b], one ? 0.f : p);
+            v[12 + 2 * b + 1] = fmaxf(v[12 + 2 * b + 1], one ? p : 0.f);
+          }
+        }
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+          const bool one1 = (j1 >> (2 - b)) & 1, one2 = (j2 >> (2 - b)) & 1;
+          v[2 * b] = one1 ? 0.f : pm;
+          v[2 * b + 1] = one1 ? pm : 0.f;
+          v[6 + 2 * b] = one2 ? 0.f : pm;
+          v[6 + 2 * b + 1] = one2 ? pm : 0.f;
+        }
+#pragma unroll
+        for (int e = 0; e < 18; ++e) {
+#pragma unroll
+          for (int o = kWave / 2; o > 0; o >>= 1) v[e] = fmaxf(v[e], __shfl_xor(v[e], o, kWave));
+          if (lane == e && e < 6 * len) s_max[kd0 * 6 + e] = v[e];
+        }
+      }
+      __syncthreads();
+      if (threadIdx.x < kData) {
+        const int kd = threadIdx.x;
+#pragma unroll
+        for (int b = 0; b < 3; ++b)
+          s_llr[3 * kd + b] = 10.0 * log10(1e-12 + (double)s_max[kd * 6 + 2 * b + 1]) -
+                              10.0 * log10(1e-12 + (double)s_max[kd * 6 + 2 * b]);
+      }
+      __syncthreads();
+      if (normalise(out_n)) vbits |= 1 << (n - 1);
+    }
+    if (ms.valid && threadIdx.x == 0) ms.valid[pos] = (uint8_t)vbits;
+  }
+}
+
+// the validity bytes of one set (max_nsym = 1 of the stage call): bit 0 for a valid fit
+__global__ void k_coh_valid1(const ft8_coh_fit* fit, uint8_t* valid, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) valid[i] = fit[i].status == 0 ? 1 : 0;
 }
 
 // one wave per list position: a valid fit whose attempt the tail accepted rewrites its record
@@ -355,22 +481,36 @@ __global__ __launch_bounds__(4 * kWave) void k_coh_merge(CohPass a) {
   if (j >= r.count[slot]) return;
   const ft8_result& got = a.res_c[pos];
   if (!got.ok || a.fit[pos].status != 0) return;
-  // a.drift (null without the drift search): a rescue at a rate other than 0 also sets bit 2
-  const int bits = a.drift && a.drift[pos].rate_hz_per_s != 0.f ? 6 : 2;
-  if (lane == 0) retry_accept(r.res + (int64_t)slot * r.N + r.list[pos], got, bits);
+  ft8_result* rec = r.res + (int64_t)slot * r.N + r.list[pos];
+  // a.valid (null with one set): set a.set must be valid, and the first set that decodes wins
+  if (a.valid && (!((a.valid[pos] >> a.set) & 1) || rec->ok)) return;
+  // a.drift (null without the drift search): a rescue at a rate other than 0 also sets bit 2; a set
+  // after the first sets bit 3
+  const int bits = (a.drift && a.drift[pos].rate_hz_per_s != 0.f ? 6 : 2) | (a.set > 0 ? 8 : 0);
+  if (lane == 0) retry_accept(rec, got, bits);
 }
 
 }  // namespace
 
-size_t coherent_lds_bytes(int nsps, int Q) {
-  return sizeof(float2) * ((size_t)bb_tail_at(Q, nsps / Q) + (size_t)coh_rot_words(Q));
+size_t coherent_lds_bytes(int nsps, int Q, bool multi) {
+  return sizeof(float2) * ((size_t)bb_tail_at(Q, nsps / Q) + (size_t)(multi ? coh_multi_words(Q) : coh_rot_words(Q)));
 }
 
-hipError_t launch_coherent(const CohLaunch& a, const CohDrift& g, hipStream_t s) {
+hipError_t launch_coherent(const CohLaunch& a, const CohDrift& g, const CohMulti& m, hipStream_t s) {
   const int64_t grid = a.slot_of ? (int64_t)a.n : (int64_t)((a.b.n_slots + 7) / 8) * 8 * a.M;
   if (grid <= 0) return hipSuccess;
   if (!bb_valid(a.b)) return hipErrorInvalidValue;
-  const size_t lds = coherent_lds_bytes(a.b.nsps, a.b.Q);
+  const size_t lds = coherent_lds_bytes(a.b.nsps, a.b.Q, coherent_multi_on(m));
+  if (coherent_multi_on(m)) {
+    if (m.nsym > 3) return hipErrorInvalidValue;
+    const dim3 gr((unsigned)grid), bl(kCohThreads);
+    if (coherent_drift_on(g)) {
+      if (a.b.dtype == FT8_I16) return lds_launch(k_coherent<int16_t, CohDrift, CohMulti>, gr, bl, lds, s, a, g, m);
+      return lds_launch(k_coherent<float, CohDrift, CohMulti>, gr, bl, lds, s, a, g, m);
+    }
+    if (a.b.dtype == FT8_I16) return lds_launch(k_coherent<int16_t, CohMulti>, gr, bl, lds, s, a, m);
+    return lds_launch(k_coherent<float, CohMulti>, gr, bl, lds, s, a, m);
+  }
   if (coherent_drift_on(g)) {
     if (a.b.dtype == FT8_I16)
       return lds_launch(k_coherent<int16_t, CohDrift>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a, g);
@@ -378,6 +518,12 @@ hipError_t launch_coherent(const CohLaunch& a, const CohDrift& g, hipStream_t s)
   }
   if (a.b.dtype == FT8_I16) return lds_launch(k_coherent<int16_t>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a);
   return lds_launch(k_coherent<float>, dim3((unsigned)grid), dim3(kCohThreads), lds, s, a);
+}
+
+hipError_t launch_coh_valid1(const ft8_coh_fit* fit, uint8_t* valid, int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_coh_valid1, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, fit, valid, n);
+  return hipGetLastError();
 }
 
 hipError_t launch_coh_merge(const CohPass& a, hipStream_t s) {

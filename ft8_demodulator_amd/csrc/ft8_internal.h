@@ -317,7 +317,7 @@ __device__ inline int slot_count(const RetryLists& r, int slot) {
 // in candidate order; count = min(found, M)
 hipError_t launch_retry_list(const RetryLists& r, hipStream_t s);
 // an accepted attempt `got` rewrites the record it retried; pass_bits: (h + 1) << 4 for AP hypothesis
-// h, 2 for the coherent pass (6 at a drift rate other than 0)
+// h, 2 for the coherent pass (6 at a drift rate other than 0, and 8 more from a multi-symbol set)
 __device__ inline void retry_accept(ft8_result* rec, const ft8_result& got, int pass_bits) {
   ft8_result w = *rec;
   w.ok = 1;
@@ -368,15 +368,29 @@ struct CohDrift {
   ft8_coh_drift* out;          // nullable [positions]
 };
 inline bool coherent_drift_on(const CohDrift& g) { return g.n_rates > 1 && g.max_rate > 0.f; }
-size_t coherent_lds_bytes(int nsps, int Q);   // k_coherent's dynamic LDS
-hipError_t launch_coherent(const CohLaunch& a, const CohDrift& g, hipStream_t s);
+// the multi-symbol sets (ft8hip.h, step 4b): on when nsym > 1.  Like the drift search, instantiations of
+// their own with this as a further argument: set s (0-based) of position pos is written at
+// llr + pos * pos_stride + s * set_stride (in doubles), so the stage call's [n][S][174] and the pass's
+// one [positions][174] per set are both reached.
+struct CohMulti {
+  int nsym;                    // S: sets per position, 2 or 3
+  int64_t pos_stride, set_stride;
+  uint8_t* valid;              // nullable [positions]: bit s for a valid set s
+};
+inline bool coherent_multi_on(const CohMulti& m) { return m.nsym > 1; }
+size_t coherent_lds_bytes(int nsps, int Q, bool multi);   // k_coherent's dynamic LDS
+hipError_t launch_coherent(const CohLaunch& a, const CohDrift& g, const CohMulti& m, hipStream_t s);
+// valid[i] = fit[i].status == 0: the validity bytes where only set 1 exists
+hipError_t launch_coh_valid1(const ft8_coh_fit* fit, uint8_t* valid, int n, hipStream_t s);
 // The coherent retry inside ft8_decode_batch: the list (M = the per-slot cap), k_coherent -> fit and
-// the LLRs, launch_bp -> res_c, k_coh_merge.
+// the LLRs, then per set launch_bp -> res_c and k_coh_merge.
 struct CohPass {
   RetryLists r;
   const ft8_coh_fit* fit;      // k_coherent's fits of the lists
   const ft8_result* res_c;     // launch_bp's records of them
   const ft8_coh_drift* drift;  // null without the drift search: the winning rates of the lists
+  const uint8_t* valid;        // null with one set: k_coherent's validity bytes of the lists
+  int set;                     // the set (0-based) res_c was decoded from
 };
 hipError_t launch_coh_merge(const CohPass& a, hipStream_t s);
 

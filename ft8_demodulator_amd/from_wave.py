@@ -51,13 +51,15 @@ def read_wave_file(wave_path: str, verbose: bool = False) -> tuple:
 
 
 def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_errors: int = None, coherent=None,
-                 coherent_drift=None, device=None, verbose: bool = False, **decode_kw) -> tuple:
+                 coherent_drift=None, coherent_nsym: int = 1, device=None, verbose: bool = False,
+                 **decode_kw) -> tuple:
     """One file, any PCM width, as one slot through _pipeline.decode_one -> (results, snr_db, patterns)
     and, with coherent, a fourth entry.  snr_db (with snr, else None): one SNR in 2500 Hz per result.
     patterns (with ap, else None): per result the a-priori pattern that rescued it, None for a plain
     decode.  fits (with coherent): per result (dt_s, df_hz) of the coherent fit that rescued it (one
     ft8_coherent_llr call for those records), None for any other decode; with coherent_drift
-    (True or (max_rate, n_rates)) the fit is (dt_s, df_hz, rate_hz_per_s)."""
+    (True or (max_rate, n_rates)) the fit is (dt_s, df_hz, rate_hz_per_s); a decode from a joint metric over
+    2 or 3 symbols (coherent_nsym > 1) has MULTI_SYMBOL as a further, last entry."""
     import torch
     from . import _lib
     from ._pipeline import decode_one
@@ -74,7 +76,8 @@ def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_erro
         x, code = torch.from_numpy(h).to(dev), _lib.FT8_F32
     ap = None if ap is None else tuple(ap)
     results, reports, recs = decode_one(x, code, sample_rate, snr=snr, ap=ap, ap_max_hard_errors=ap_max_hard_errors,
-                                        coherent=coherent, coherent_drift=coherent_drift, **decode_kw)
+                                        coherent=coherent, coherent_drift=coherent_drift,
+                                        coherent_nsym=coherent_nsym, **decode_kw)
     out = (results, snr_db_or_nan(reports) if snr else None,
            None if ap is None else [ap[ap_index(r) - 1] if ap_index(r) else None for r in recs])
     if coherent is None:
@@ -82,11 +85,15 @@ def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_erro
     return out + (_coherent_fits(x, code, sample_rate, recs, decode_kw, coherent_drift),)
 
 
+MULTI_SYMBOL = "multi-symbol"   # last entry of the fit of a decode from a multi-symbol set
+
+
 def _coherent_fits(x, code, sample_rate, recs, decode_kw, drift=None):
     """(dt_s, df_hz) of every record the coherent pass rescued (the stage call on those candidates), None
-    for the others; with the drift search (True or (max_rate, n_rates)) also the winning rate in Hz/s."""
+    for the others; with the drift search (True or (max_rate, n_rates)) also the winning rate in Hz/s;
+    MULTI_SYMBOL last for a record with pass_index bit 3."""
     from ._pipeline import make_plan
-    from .coherent import DEFAULT_DRIFT, coherent_index
+    from .coherent import DEFAULT_DRIFT, coherent_index, multisymbol_index
     from .ldpc_decoder import coherent_llr_batch
     fits = [None] * len(recs)
     idx = [i for i, r in enumerate(recs) if coherent_index(r)]
@@ -104,6 +111,9 @@ def _coherent_fits(x, code, sample_rate, recs, decode_kw, drift=None):
                                          drift=DEFAULT_DRIFT if drift is True else drift)
             for i, fi, gi in zip(idx, f, g):
                 fits[i] = (float(fi["dt_s"]), float(fi["df_hz"]), float(gi["rate_hz_per_s"]))
+        for i in idx:
+            if multisymbol_index(recs[i]):
+                fits[i] += (MULTI_SYMBOL,)
     return fits
 
 
@@ -158,7 +168,8 @@ def _print_results(results, text: bool = False, snr=None, ap=None, coherent=None
     value per result): one extra `SNR:` line per result, dB in 2500 Hz.  ap (one pattern or None per
     result): one extra `AP: <pattern>` line for every a-priori decode.  coherent (one (dt_s, df_hz) or
     None per result): one extra `Coherent:` line for every decode from the coherent LLRs; a third entry
-    (the drift search's rate, Hz/s) ends the line with `, drift +0.50 Hz/s`."""
+    (the drift search's rate, Hz/s) ends the line with `, drift +0.50 Hz/s`, and a last entry MULTI_SYMBOL
+    with `, multi-symbol` after that."""
     if not results:
         print("No FT8 messages decoded")
         return
@@ -180,8 +191,10 @@ def _print_results(results, text: bool = False, snr=None, ap=None, coherent=None
         if ap is not None and ap[k] is not None:
             print(f"AP: {ap[k]}")
         if coherent is not None and coherent[k] is not None:
-            drift = f", drift {coherent[k][2]:+.2f} Hz/s" if len(coherent[k]) > 2 else ""
-            print(f"Coherent: dt {coherent[k][0] * 1e3:+.2f} ms, df {coherent[k][1]:+.2f} Hz{drift}")
+            multi = coherent[k][-1] == MULTI_SYMBOL
+            fit = coherent[k][:-1] if multi else coherent[k]
+            drift = f", drift {fit[2]:+.2f} Hz/s" if len(fit) > 2 else ""
+            print(f"Coherent: dt {fit[0] * 1e3:+.2f} ms, df {fit[1]:+.2f} Hz{drift}{', multi-symbol' if multi else ''}")
         print(f"CRC check: {status.crc_calculated}")
         print(f"LDPC errors: {status.ldpc_errors}")
         print("-" * 50)
@@ -242,10 +255,15 @@ def main(argv=None):
                         help="with --coherent: also search N (odd, at most 33) linear frequency drift rates over "
                              "+-MAX Hz/s (at most 4) for each of those candidates (default 1.0:9; the decode's "
                              "mark then carries the rate)")
+    parser.add_argument("--coherent-nsym", type=int, choices=(1, 2, 3), default=None, metavar="N",
+                        help="with --coherent: also decode joint LLRs over 2 .. N (at most 3) adjacent symbols for "
+                             "each of those candidates (default 1: off; such a decode's mark ends with multi-symbol)")
     args = parser.parse_args(argv)
     coherent = None if args.coherent is None else (True if args.coherent < 0 else args.coherent)
     if args.coherent_drift is not None and coherent is None:
         parser.error("--coherent-drift needs --coherent")
+    if args.coherent_nsym is not None and coherent is None:
+        parser.error("--coherent-nsym needs --coherent")
     paths = args.wave_file
     for path in paths:
         if not os.path.exists(path):
@@ -264,6 +282,8 @@ def main(argv=None):
             kw = dict(kw, coherent=coherent)
         if args.coherent_drift is not None:
             kw = dict(kw, coherent_drift=args.coherent_drift)
+        if args.coherent_nsym is not None:
+            kw = dict(kw, coherent_nsym=args.coherent_nsym)
         decoded = (_decode_file(path, snr=args.snr, ap=args.ap, ap_max_hard_errors=args.ap_max_hard_errors, **kw)
                    for path in paths)
     elif many:

@@ -39,11 +39,13 @@ def ap_decode_batch(llrs: np.ndarray, records: np.ndarray, max_iterations: int):
 
 
 def coherent_llr_batch(samples, cand, slot_of, sample_rate=12000, bins_per_tone=2, steps_per_symbol=2, t_lo=0,
-                       f_lo=0, code=None, drift=None):
+                       f_lo=0, code=None, drift=None, nsym=1):
     """Coherent re-demodulation (ft8_coherent_llr) of the candidates cand [n, 2] = (abs_time, abs_freq) of
     the slots slot_of [n] from samples [n_slots, n_samples] (float32 or int16 PCM): -> (LLRs float64
     [n, 174], fits coherent.FIT_DTYPE [n]).  drift = (max_rate Hz/s, n_rates): with the search over
     linear frequency drift (ft8_coherent_drift_llr) -> (LLRs, fits, drifts coherent.DRIFT_DTYPE [n]).
+    nsym = S in {2, 3}: with the joint LLRs over 2 .. S symbols (ft8_coherent_nsym_llr): LLRs [n, S, 174],
+    and the validity bytes uint8 [n] come last.
     The contract is in include/ft8hip.h; coherent.coherent_restate is its NumPy restatement."""
     return _device.coherent_llr(samples, cand, slot_of, sample_rate, bins_per_tone, steps_per_symbol, t_lo, f_lo, code,
-                                drift)
+                                drift, nsym)

@@ -90,7 +90,8 @@ typedef struct ft8_params {
  *                      slot), and decodes the new LLRs.  Rescued candidates come out in candidate order
  *                      among the plain decodes with pass_index bit 1 set.  F32 and I16 samples only; not
  *                      with FT8_FLAG_SUBTRACT.  ft8_set_coherent_drift adds a search over linear
- *                      frequency drift to it (off by default). */
+ *                      frequency drift to it, ft8_set_coherent_nsym joint LLRs over 2 and 3 symbols
+ *                      (both off by default). */
 #define FT8_FLAG_TOPK 1
 #define FT8_FLAG_SUBTRACT 2
 #define FT8_FLAG_AP 4
@@ -111,6 +112,7 @@ typedef struct ft8_result {
   uint8_t pass_index;      /* low nibble bit 0: 0 decoded from the slot, 1 decoded after subtraction (FT8_FLAG_SUBTRACT);
                               bit 1: decoded from the coherent LLRs (FT8_FLAG_COHERENT);
                               bit 2: ... at a drift rate other than 0 (ft8_set_coherent_drift);
+                              bit 3: ... from a joint metric over 2 or 3 symbols (ft8_set_coherent_nsym);
                               high nibble 0: plain BP; h + 1: a-priori hypothesis h (FT8_FLAG_AP, ft8_ap_decode) */
 } ft8_result;
 
@@ -473,6 +475,50 @@ int ft8_coherent_drift_llr(ft8_ctx* ctx, const void* d_samples, int dtype, int64
  * not carried in ft8_result (the stage call gives it).  The pass's scratch grows by 8 bytes per listed
  * candidate.  Errors as for the stage call. */
 int ft8_set_coherent_drift(ft8_ctx* ctx, float max_rate_hz_per_s, int32_t n_rates);
+
+/* ---- coherent re-demodulation with joint LLRs over 2 and 3 symbols ----------------------------------
+ * Opt-in and build-defined like the pass itself; coherent.py: coherent_restate(nsym=...) restates it.
+ * FT8 is continuous-phase 8-FSK: after the fit of steps 1 - 3 the phase carried from one symbol to the
+ * next is known, so the correlations of adjacent symbols can be added coherently under each joint tone
+ * hypothesis.  With max_nsym = S in {1, 2, 3} the pass produces S LLR vectors ("sets") per candidate; set
+ * 1 is step 4's vector, unchanged (S = 1: exactly the pass above).  Step 4b, for n = 2 .. S:
+ *   spectra   c_k[t], t = 0 .. 7: the complex correlations of step 4 at the winning (dt, df), of the 58
+ *             data symbols k (under the drift search on z of the winning rate); c_k[t] = 0 for every t of
+ *             a symbol that is not present (step 2).
+ *   phase     c'_k[t] = c_k[t] exp(-2 pi i frac((df / 6.25 - 3.5) k)), k the symbol index 0 .. 78.  (The
+ *             baseband is mixed to the centre of the band and 6.25 nsps / fs = 1, so a symbol of tone t
+ *             advances the phase by 2 pi (t - 3.5 + df / 6.25); the integer t drops out.)
+ *   groups    each half (symbols 7 .. 35 and 43 .. 71) is cut, in order, into groups of n symbols with a
+ *             shorter last group: 14 pairs and 1 single for n = 2, 9 triples and 1 pair for n = 3.
+ *   metric    for a group of g symbols k_1 .. k_g and each of the 8^g tone tuples (a_1 .. a_g):
+ *             p = |sum_i c'_{k_i}[a_i]|^2, s = 10 log10(1e-12 + p).  Tone FT8_Gray_map[j] carries the three
+ *             bits of j, MSB first (ft8_extract_symbol).  The LLR of bit b of symbol k_i is max(s over the
+ *             tuples whose a_i has the bit 1) - max(s over those whose a_i has it 0).  The bits of an
+ *             absent symbol come out 0.
+ *   validity  each set is normalised by ftx_normalize_logl as in step 4; a set whose variance is 0 or NaN
+ *             is written as zeros and is invalid.  One byte per candidate: bit n - 1 set for a valid set
+ *             n; bit 0 exactly when fit.status == 0; 0 for status 2 or 3 (every set zeros).
+ * The device adds the correlations and takes each maximum in float32 (the maximum is exact), and forms
+ * the six logarithms per symbol, the differences and the normalisation in double. */
+
+/* ft8_coherent_drift_llr with max_nsym sets: d_llr_out[n][max_nsym][174], d_valid_out[n] (may be NULL) the
+ * validity bytes.  max_nsym = 1 writes exactly the bytes of ft8_coherent_drift_llr.  FT8_E_ARG for max_nsym
+ * outside [1, 3]; other errors as for ft8_coherent_drift_llr. */
+int ft8_coherent_nsym_llr(ft8_ctx* ctx, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
+                          int64_t slot_stride, const ft8_params* p, const int32_t* d_cand,
+                          const int32_t* d_slot_of, int32_t n, float max_rate_hz_per_s, int32_t n_rates,
+                          double* d_llr_out, ft8_coh_fit* d_fit_out, ft8_coh_drift* d_drift_out, int32_t max_nsym,
+                          uint8_t* d_valid_out, void* stream);
+/* The sets inside FT8_FLAG_COHERENT (a context setting like ft8_set_coherent_drift; default 1: off).  The
+ * list and the demodulation run once per chunk; then for n = 1 .. max_nsym in order BP decodes the lists
+ * from set n's LLRs and a merge follows.  Set n rewrites the record of a list position when the fit is
+ * valid, set n is valid, the tail accepted the attempt and the record is not ok already: the first set
+ * wins.  The record is written as by the pass above (pass_index |= 2, or |= 6 at a drift rate other than
+ * 0) and gets pass_index |= 8 when n > 1; which of sets 2 and 3 won is not carried (the stage call tells).
+ * Positions an earlier set rescued are decoded again by the later sets' BP launches.  Scratch per listed
+ * candidate: max_nsym * 174 * 8 bytes of LLRs, max_nsym * 40 bytes of records (instead of 174 * 8 and 40)
+ * and, for max_nsym > 1, 1 validity byte.  FT8_E_ARG for max_nsym outside [1, 3]. */
+int ft8_set_coherent_nsym(ft8_ctx* ctx, int32_t max_nsym);
 
 /* Per-slot flags of the last selection (copied device->device into d_out[n_slots]):
  * bit 0: an exact score tie reached a heap comparison (the reference raises TypeError there,

@@ -16,6 +16,10 @@
           decoded over the drift rate at two SNRs -- plain, coherent, coherent with the search (top-K,
           K = 40, min_score 2); decodes on the noise-only slots with the search on; k_coherent ms per launch
           at 1, 9, 17 and 33 rates for M = 8 and 32; the step with coherent = 8 and 32, search off and (1.0, 9)
+  nsym    (--nsym, or --legs nsym) the multi-symbol sets (ft8_set_coherent_nsym): the sweep's decode fractions
+          with a row per max_nsym (1 and 3), decodes on the noise-only slots at 3, k_coherent ms per launch at
+          max_nsym 1 and 3 for M = 8 and 32, and the flagged step (config 3, and the same batch under top-K)
+          at coherent = 32 for max_nsym 1, 2 and 3 with the rescued record counts
 
 Prints one JSON line and writes it to --out.  Needs a GPU; there is no CPU fallback.
 """
@@ -257,10 +261,89 @@ def leg_drift(torch, dev, args):
             "table": table, "noise": noise, "kernel": kernel, "step": step}
 
 
+def leg_nsym(torch, dev, args):
+    from ft8_demodulator_amd import SlotDecoder, _lib, coherent
+    from ft8_demodulator_amd._pipeline import make_params, make_plan
+    kw = dict(max_candidates=40, min_score=2, max_iterations=20, flags=_lib.FT8_FLAG_TOPK)
+    decs = [("plain", SlotDecoder(FS, 2, 2, device=dev, context=_lib.Context(dev.index), **kw))]
+    decs += [(f"nsym_{n}", SlotDecoder(FS, 2, 2, device=dev, context=_lib.Context(dev.index), coherent=True,
+                                       coherent_nsym=n, **kw)) for n in (1, 3)]
+    # ---- decode fractions, the sweep's slots
+    table = []
+    for i, snr in enumerate(np.arange(args.snr_lo, args.snr_hi + 0.5, 1.0)):
+        x, pay = cq_slots(args.sweep_slots, float(snr), args.seed + i, dev)
+        row = {"snr_db_full_band": float(snr), "snr_db_2500": float(snr + 10.0 * np.log10(FS / 2.0 / 2500.0))}
+        for name, dec in decs:
+            recs = dec.records(x)
+            hit = sum(any(bytes(r["payload"]) == bytes(pay[s]) for r in recs[s]) for s in range(len(recs)))
+            false = sum(sum(bytes(r["payload"]) != bytes(pay[s]) for r in recs[s]) for s in range(len(recs)))
+            row[name] = {"decoded": hit, "fraction": hit / len(recs), "false": false,
+                         "multi_symbol": sum(int(sum(coherent.multisymbol_index(r) for r in s)) for s in recs)}
+        table.append(row)
+    # ---- noise-only slots at max_nsym 3
+    g = torch.Generator(device=dev)
+    g.manual_seed(args.seed)
+    xn = torch.randn(args.slots, N, generator=g, device=dev, dtype=torch.float32)
+    recs = SlotDecoder(FS, 2, 2, device=dev, coherent=32, coherent_nsym=3, **CFG3).records(xn)
+    noise = {"slots": args.slots, "max_nsym": 3, "decodes": sum(len(s) for s in recs),
+             "multi_symbol_decodes": sum(int(sum(coherent.multisymbol_index(r) for r in s)) for s in recs)}
+    # ---- k_coherent per launch at max_nsym 1 and 3, candidates listed as the in-batch launch lists them
+    x = crowded(args, dev)
+    S, K = args.slots, CFG3["max_candidates"]
+    ctx, L, st = _lib.Context(dev.index), _lib.lib(), _lib.stream_handle(dev)
+    plan = make_plan(N, FS)
+    p = make_params(plan, K, CFG3["min_score"], 20, _lib.FT8_FLAG_TOPK)
+    d_wf = torch.empty(S, plan.T, plan.F, dtype=torch.float32, device=dev)
+    ctx.check(L.ft8_stft(ctx.handle, _lib.ptr(x), _lib.FT8_F32, N, S, N, ctypes.byref(p), _lib.ptr(d_wf), st), "stft")
+    d_cand = torch.zeros(S, K, 2, dtype=torch.int32, device=dev)
+    d_score = torch.zeros(S, K, dtype=torch.float64, device=dev)
+    d_cnt = torch.zeros(S, dtype=torch.int32, device=dev)
+    ctx.check(L.ft8_sync_select(ctx.handle, _lib.ptr(d_wf), 0, S, plan.T, plan.F, ctypes.byref(p), _lib.ptr(d_cand),
+                                _lib.ptr(d_score), _lib.ptr(d_cnt), None, st), "select")
+    cand, cnt = d_cand.cpu().numpy(), d_cnt.cpu().numpy()
+    del d_wf
+    kernel = {}
+    for M in (8, 32):
+        w = np.arange(((S + 7) // 8) * 8 * M)
+        slot, j = (w % 8) + 8 * ((w // 8) // M), (w // 8) % M
+        keep = (slot < S) & (j < np.minimum(cnt[np.minimum(slot, S - 1)], M))
+        slot, j = slot[keep], j[keep]
+        n = len(slot)
+        d_c = torch.from_numpy(np.ascontiguousarray(cand[slot, j])).to(dev)
+        d_so = torch.from_numpy(slot.astype(np.int32)).to(dev)
+        d_llr = torch.empty(n, 3, 174, dtype=torch.float64, device=dev)
+        d_fit = torch.empty(n * coherent.FIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_v = torch.empty(n, dtype=torch.uint8, device=dev)
+        for ns in (1, 3):
+            def launch():
+                ctx.check(L.ft8_coherent_nsym_llr(ctx.handle, _lib.ptr(x), _lib.FT8_F32, N, S, N, ctypes.byref(p),
+                                                  _lib.ptr(d_c), _lib.ptr(d_so), n, 0.0, 1, _lib.ptr(d_llr),
+                                                  _lib.ptr(d_fit), None, ns, _lib.ptr(d_v), st), "coherent nsym")
+            kernel[f"M_{M}_nsym_{ns}"] = dict(_timed_launches(torch, launch, args.steps, args.warmup), candidates=int(n))
+    # ---- the flagged step at coherent = 32, alternating on the crowded batch: config 3 and top-K
+    names, sd = [], []
+    for sel, cfg in (("", CFG3), ("topk_", dict(CFG3, flags=_lib.FT8_FLAG_TOPK))):
+        for ns in (1, 2, 3):
+            names.append(f"{sel}nsym_{ns}")
+            sd.append(SlotDecoder(FS, 2, 2, device=dev, context=_lib.Context(dev.index), coherent=32, coherent_nsym=ns,
+                                  **cfg))
+    times = timed_steps(torch, sd, x, args.steps, args.warmup)
+    step = {"coherent": 32}
+    for name, dec, t in zip(names, sd, times):
+        recs = dec.records(x)
+        step[name] = dict(t, decodes=sum(len(s) for s in recs),
+                          rescued=sum(int(sum(coherent.coherent_index(r) for r in s)) for s in recs),
+                          rescued_multi_symbol=sum(int(sum(coherent.multisymbol_index(r) for r in s)) for s in recs),
+                          distinct_messages=sum(len({bytes(r["payload"]) for r in s}) for s in recs))
+    return {"slots_per_step": args.sweep_slots, "selection": "top-K, K = 40, min_score 2", "table": table,
+            "noise": noise, "kernel": kernel, "step": step}
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--legs", default="step,kernel,sweep,noise",
-                   help="comma-separated subset of step,kernel,sweep,noise,drift")
+                   help="comma-separated subset of step,kernel,sweep,noise,drift,nsym")
+    p.add_argument("--nsym", action="store_true", help="the multi-symbol sets' measurements only (--legs nsym)")
     p.add_argument("--drift", action="store_true", help="the drift search's measurements only (--legs drift)")
     p.add_argument("--drift-search", default="2.0:17", metavar="MAX:N",
                    help="the search of the drift leg's decode fractions and noise slots")
@@ -282,8 +365,9 @@ def main():
     dev = torch.device("cuda", 0)
     res = {"box": socket.gethostname(), "gpu": torch.cuda.get_device_name(0),
            "build_id": _lib.lib().ft8_build_id().decode()}
-    legs = {"step": leg_step, "kernel": leg_kernel, "sweep": leg_sweep, "noise": leg_noise, "drift": leg_drift}
-    for name in (["drift"] if args.drift else args.legs.split(",")):
+    legs = {"step": leg_step, "kernel": leg_kernel, "sweep": leg_sweep, "noise": leg_noise, "drift": leg_drift,
+            "nsym": leg_nsym}
+    for name in (["drift"] if args.drift else ["nsym"] if args.nsym else args.legs.split(",")):
         res[name] = legs[name](torch, dev, args)
     line = json.dumps(res)
     out = args.out if os.path.isabs(args.out) else os.path.join(ROOT, args.out)
