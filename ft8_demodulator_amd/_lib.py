@@ -18,6 +18,7 @@ FT8_F32, FT8_F64, FT8_C64, FT8_C128, FT8_I16 = 0, 1, 2, 3, 4
 FT8_OK, FT8_E_ARG, FT8_E_HIP, FT8_E_UNSUPPORTED, FT8_E_NOMEM, FT8_E_RANGE = 0, -1, -2, -3, -4, -5
 FT8_FLAG_TOPK, FT8_FLAG_SUBTRACT, FT8_FLAG_AP, FT8_FLAG_COHERENT = 1, 2, 4, 8
 FT8_AP_MAX_HYP = 8
+FT8_SUBTRACT_MAX_PASSES = 4
 FT8_TX_PROTOCOL, FT8_TX_REFERENCE = 0, 1
 FT8_STFT_STOCKHAM, FT8_STFT_PACKED3840, FT8_STFT_CHIRPZ, FT8_STFT_DFT = 0, 1, 2, 3
 N_STAGES = 12
@@ -178,6 +179,8 @@ def lib():
             "ft8_set_coherent_nsym": ([vp, i32], ctypes.c_int),
             "ft8_coherent_nsym_llr": ([vp, vp, ctypes.c_int, i64, i32, i64, P, vp, vp, i32, ctypes.c_float, i32, vp, vp,
                                        vp, i32, vp, vp], ctypes.c_int),
+            "ft8_set_subtract": ([vp, i32, i32], ctypes.c_int),
+            "ft8_subtract_counts": ([vp, vp, i32, i32, vp], ctypes.c_int),
         }
         stale_ok = os.environ.get("FT8HIP_ALLOW_STALE") == "1"
         for name, (args, res) in sig.items():
@@ -230,7 +233,8 @@ EXPORTED_SYMBOLS = (
     "ft8_pack_bytes", "ft8_pack_decodes", "ft8_subtract_fits", "ft8_stft_method", "ft8_stft_screen_stats",
     "ft8_unpack77", "ft8_unpack77_host", "ft8_hash_call", "ft8_noise_floor", "ft8_snr", "ft8_snr_last",
     "ft8_set_ap", "ft8_ap_decode", "ft8_set_coherent", "ft8_coherent_llr",
-    "ft8_set_coherent_drift", "ft8_coherent_drift_llr", "ft8_set_coherent_nsym", "ft8_coherent_nsym_llr")
+    "ft8_set_coherent_drift", "ft8_coherent_drift_llr", "ft8_set_coherent_nsym", "ft8_coherent_nsym_llr",
+    "ft8_set_subtract", "ft8_subtract_counts")
 
 
 def limits():
@@ -335,6 +339,11 @@ class Context:
         """ft8_set_coherent_nsym: an FT8_FLAG_COHERENT batch also decodes joint LLRs over 2 .. max_nsym
         (<= 3) symbols; 1: off."""
         self.check(lib().ft8_set_coherent_nsym(self.handle, int(max_nsym)), "ft8_set_coherent_nsym")
+
+    def set_subtract(self, n_passes: int = 2, retry: bool = False):
+        """ft8_set_subtract: the passes (2..4) of an FT8_FLAG_SUBTRACT batch and whether every pass runs the
+        FT8_FLAG_AP / FT8_FLAG_COHERENT retries (False: those flags are refused with FT8_FLAG_SUBTRACT)."""
+        self.check(lib().ft8_set_subtract(self.handle, int(n_passes), int(bool(retry))), "ft8_set_subtract")
 
     def replay(self, stage: str, reps: int = 1, stream=None):
         """ft8_replay_stage: re-launch one kernel of the last ft8_decode_batch `reps` times."""

@@ -227,8 +227,13 @@ class SlotDecoder:
     def __init__(self, sample_rate=12000, bins_per_tone=2, steps_per_symbol=2, max_candidates=20,
                  min_score=10, max_iterations=20, freq_min=None, freq_max=None, time_min=None,
                  time_max=None, device=None, flags=0, max_results_per_slot=None, context=None, ap=None,
-                 ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1):
-        """ap: a-priori patterns (ap.ap_hypothesis, e.g. ["CQ ? ?", "K1ABC ? ?"], tried in order on every
+                 ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1, subtract=None):
+        """subtract: True or a pass count in [2, 4] (True: 2) -- sets FT8_FLAG_SUBTRACT: what each pass decodes is
+        subtracted and the residual decoded again, that many passes in all, every pass with the ap / coherent
+        retries asked for below (ft8_set_subtract(n, 1)); the default capacity holds n * max_candidates rows.
+        None / False: off -- a decoder given flags=FT8_FLAG_SUBTRACT instead runs the two plain passes and
+        takes neither ap nor coherent.
+        ap: a-priori patterns (ap.ap_hypothesis, e.g. ["CQ ? ?", "K1ABC ? ?"], tried in order on every
         candidate BP fails on; at most 8) -- sets FT8_FLAG_AP; None: plain decoding.  ap_max_hard_errors:
         the most hard decisions of an accepted AP decode that may contradict the received LLRs' signs
         (default ap.DEFAULT_MAX_HARD_ERRORS = 36; 174: no limit).
@@ -242,6 +247,10 @@ class SlotDecoder:
         for every listed candidate (ft8_set_coherent_nsym); more than 1 needs coherent.  1: off."""
         from . import ap as _ap
         from . import coherent as _coh
+        from . import subtract as _sub
+        self.subtract = _sub.passes_of(subtract)   # ValueError for what the library refuses
+        if self.subtract is not None:
+            flags |= _lib.FT8_FLAG_SUBTRACT
         self.coherent_nsym = _coh.check_nsym(coherent_nsym)   # ValueError for what the library refuses
         if self.coherent_nsym > 1 and (coherent is None or coherent is False):
             raise ValueError("coherent_nsym needs coherent")
@@ -278,13 +287,15 @@ class SlotDecoder:
         # that run concurrently on different streams want one context each (the library orders a
         # shared context's work across streams, which serialises them)
         self.ctx = context if context is not None else _lib.context(self.device)
-        # a subtract-and-redecode batch appends up to max_candidates pass-2 records after up to
-        # max_candidates pass-1 records, so its default capacity holds both passes
-        default_cap = max(self.max_candidates, 1) * (2 if flags & _lib.FT8_FLAG_SUBTRACT else 1)
+        # a subtract-and-redecode batch appends up to max_candidates records per further pass after up to
+        # max_candidates pass-1 records, so its default capacity holds every pass
+        self.n_passes = (self.subtract or 2) if flags & _lib.FT8_FLAG_SUBTRACT else 1
+        default_cap = max(self.max_candidates, 1) * self.n_passes
         self.cap = int(max_results_per_slot if max_results_per_slot is not None else default_cap)
         self._plans = {}
         self._bufs = {}
         self._launched = False  # whether the last run() reached ft8_decode_batch (else: nothing to decode)
+        self._last_slots = 0    # slots of the last run()
 
     def plan(self, n_samples) -> Plan:
         if n_samples not in self._plans:
@@ -323,6 +334,7 @@ class SlotDecoder:
         out, counts = self._buffers(n_slots)
         plan = self.plan(n)
         self._launched = False
+        self._last_slots = n_slots
         if plan.empty or n_slots == 0:
             counts[:n_slots].zero_()
             return out, counts[:n_slots]
@@ -333,12 +345,32 @@ class SlotDecoder:
             self.ctx.set_coherent(self.coherent)
             self.ctx.set_coherent_drift(*(self.coherent_drift or (0.0, 1)))
             self.ctx.set_coherent_nsym(self.coherent_nsym)
+        if self.flags & _lib.FT8_FLAG_SUBTRACT:
+            # every batch states its own setting, so a shared context never carries the opt-in over to a
+            # decoder built with the flag alone (whose two passes refuse the retries)
+            self.ctx.set_subtract(self.n_passes, self.subtract is not None)
         rc = _lib.lib().ft8_decode_batch(self.ctx.handle, _lib.ptr(x), int(code), n, n_slots, n,
                                          ctypes.byref(p), _lib.ptr(out), _lib.ptr(counts), self.cap,
                                          _lib.stream_handle(torch.device("cuda", self.device)))
         self.ctx.check(rc, "ft8_decode_batch")
         self._launched = True
         return out, counts[:n_slots]
+
+    def pass_counts(self):
+        """Synchronous: ft8_subtract_counts of the last run() (or records() / messages() ...) of a subtract
+        decoder -> int32 array [n_slots, n_passes], the uncapped row count of every slot after each pass
+        (subtract.pass_of gives a row's pass).  Zeros when that run had nothing to decode."""
+        import torch
+        if not self.flags & _lib.FT8_FLAG_SUBTRACT:
+            raise ValueError("pass_counts needs a subtract decoder")
+        n_slots, n = self._last_slots, self.n_passes
+        if not self._launched or n_slots == 0:
+            return np.zeros((n_slots, n), dtype=np.int32)
+        dev = torch.device("cuda", self.device)
+        d = self._buf("pass_counts", n_slots * n, torch.int32)
+        rc = _lib.lib().ft8_subtract_counts(self.ctx.handle, _lib.ptr(d), n_slots, n, _lib.stream_handle(dev))
+        self.ctx.check(rc, "ft8_subtract_counts")
+        return d[: n_slots * n].cpu().numpy().reshape(n_slots, n).copy()
 
     def _snr_last(self, out, counts):
         """ft8_snr_last for the records run() just wrote, on the same stream: -> the device buffer of
@@ -452,18 +484,25 @@ def decode_slots(samples, sample_rate=12000, **kwargs):
 
 def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_candidates=20, min_score=10,
                max_iterations=20, freq_min=None, freq_max=None, time_min=None, time_max=None, *, flags=0, snr=False,
-               ap=None, ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1):
+               ap=None, ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1, subtract=None,
+               pass_counts=False):
     """One slot, x [N] on the GPU with its ft8 dtype code, through a SlotDecoder of its own:
     -> (decode_ft8_message's 5-tuples, with snr the ft8_snr_rec records aligned with them else None,
-    the ft8_result records).  Nothing is launched when the masks leave nothing or max_candidates <= 0."""
+    the ft8_result records) and, with pass_counts (a subtract decode), the slot's row of
+    SlotDecoder.pass_counts as a fourth entry.  Nothing is launched when the masks leave nothing or
+    max_candidates <= 0."""
     recs, reps = np.zeros(0, _lib.RESULT_DTYPE), np.zeros(0, _lib.SNR_DTYPE) if snr else None
+    per_pass = np.zeros(0, np.int32)
     plan = make_plan(int(x.shape[0]), sample_rate, bins_per_tone, steps_per_symbol, freq_min, freq_max, time_min,
                      time_max)
     if not plan.empty and max_candidates > 0:
         dec = SlotDecoder(sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score, max_iterations,
                           freq_min, freq_max, time_min, time_max, device=x.device, flags=flags, ap=ap,
                           ap_max_hard_errors=ap_max_hard_errors, coherent=coherent, coherent_drift=coherent_drift,
-                          coherent_nsym=coherent_nsym)
+                          coherent_nsym=coherent_nsym, subtract=subtract)
         recs, _, reps = (v if v is None else v[0] for v in dec._fetch(x.unsqueeze(0), code, snr=snr))
+        if pass_counts:
+            per_pass = dec.pass_counts()[0]
     wf_f64 = code in (_lib.FT8_F64, _lib.FT8_C128)
-    return records_to_results(recs, sample_rate, bins_per_tone, wf_f64), reps, recs
+    out = records_to_results(recs, sample_rate, bins_per_tone, wf_f64), reps, recs
+    return out + (per_pass,) if pass_counts else out

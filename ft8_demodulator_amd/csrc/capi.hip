@@ -158,8 +158,15 @@ struct ft8_ctx {
   // first ticket of the next k_bp launch per claim counter in `work` (8 B each, indexed by
   // bp_counter); reset with the buffer, which is zeroed whenever it is (re)allocated
   std::vector<unsigned long long> work_base;
-  // FT8_FLAG_SUBTRACT: residual samples, per-record fits, pass-1 / pass-2 records
+  // FT8_FLAG_SUBTRACT: residual samples, per-record fits, the accumulated records (pass 1's, then what
+  // every pass but the last appended) / the current pass's records
   DevBuf residual, sub_est, sub_list, out1, counts1, out2, counts2;
+  // ft8_set_subtract: passes of an FT8_FLAG_SUBTRACT batch and whether each runs the AP / coherent retries
+  int sub_passes = 2, sub_retry = 0;
+  // ft8_subtract_counts: [n_slots][n_passes] row counts after each pass of the last FT8_FLAG_SUBTRACT batch,
+  // and that batch's shape (-1: the last batch was none, or had nothing to search)
+  DevBuf sub_pass_counts;
+  int subc_slots = -1, subc_passes = -1;
   DevBuf screen;  // complex128 argmax STFT: [count][frames] uncertain-frame list (stft.hip)
   int64_t screen_frames = 0;  // frames of the last screened call (0: the last call was not screened)
   int sub_slots = 0, sub_cap = 0;  // shape of the fits in sub_est (ft8_subtract_fits)
@@ -798,7 +805,7 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
                 hipStream_t s);
 int subtract_core(ft8_ctx* c, const void* x, int dtype, float* resid, int64_t n_samples, int n_slots,
                   int64_t x_stride, int64_t r_stride, const ft8_params* p, const ft8_result* res,
-                  const int32_t* counts, int cap, hipStream_t s);
+                  const int32_t* counts, int cap, hipStream_t s, const int32_t* first = nullptr, int first_stride = 0);
 int gfsk_tables(ft8_ctx* c, int nsps);
 
 // the counter half of a k_bp launch: claim counter `counter` (ensure_work) and its host ticket base,
@@ -1180,7 +1187,7 @@ int gfsk_tables(ft8_ctx* c, int nsps) {
 
 int subtract_core(ft8_ctx* c, const void* x, int dtype, float* resid, int64_t n_samples, int n_slots,
                   int64_t x_stride, int64_t r_stride, const ft8_params* p, const ft8_result* res,
-                  const int32_t* counts, int cap, hipStream_t s) {
+                  const int32_t* counts, int cap, hipStream_t s, const int32_t* first, int first_stride) {
   // FT8_FLAG_SUBTRACT, the one caller whose strides can differ, has passed the geometry and dtype checks
   if (x_stride != r_stride) return fail(c, FT8_E_ARG, "residual and sample strides differ");
   SubLaunch L{};
@@ -1199,6 +1206,8 @@ int subtract_core(ft8_ctx* c, const void* x, int dtype, float* resid, int64_t n_
   L.Pf = c->gfsk_Pf.as<const float>();
   L.est = c->sub_est.p;
   L.list = c->sub_list.as<int32_t>();
+  L.first = first;
+  L.first_stride = first_stride;
   if ((rc = timed_launch(c, kSubEst, s, "subtract launch", [&] { return launch_sub_est(L, s); }))) return rc;
   if ((rc = timed_launch(c, kSubApply, s, "subtract launch", [&] { return launch_sub_apply(L, s); }))) return rc;
   c->sub_slots = n_slots;
@@ -1648,6 +1657,7 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
                      int32_t cap, void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
   if (c) c->replay_ok = c->snr_ok = false;
+  if (c) c->subc_slots = c->subc_passes = -1;
   if (!c || !p || !d_counts || (n_slots > 0 && !d_samples) || n_slots < 0 || cap < 0)
     return fail(c, FT8_E_ARG, "bad argument");
   if (cap > 0 && !d_out) return fail(c, FT8_E_ARG, "null output with positive capacity");
@@ -1660,11 +1670,12 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
   if (rc) return fail(c, rc, why);
   if (p->flags & FT8_FLAG_AP) {  // also where there is nothing to search
-    if (p->flags & FT8_FLAG_SUBTRACT) return fail(c, FT8_E_UNSUPPORTED, "FT8_FLAG_AP with FT8_FLAG_SUBTRACT is not supported");
+    if ((p->flags & FT8_FLAG_SUBTRACT) && !c->sub_retry)
+      return fail(c, FT8_E_UNSUPPORTED, "FT8_FLAG_AP with FT8_FLAG_SUBTRACT is not supported");
     if (c->ap_hyps.empty()) return fail(c, FT8_E_ARG, "FT8_FLAG_AP without hypotheses (ft8_set_ap)");
   }
   if (p->flags & FT8_FLAG_COHERENT) {  // also where there is nothing to search
-    if (p->flags & FT8_FLAG_SUBTRACT)
+    if ((p->flags & FT8_FLAG_SUBTRACT) && !c->sub_retry)
       return fail(c, FT8_E_UNSUPPORTED, "FT8_FLAG_COHERENT with FT8_FLAG_SUBTRACT is not supported");
     CohLaunch probe;
     if ((rc = coherent_setup(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, c->coh_nsym > 1, &probe)))
@@ -1699,26 +1710,44 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
     whole.done();
     return FT8_OK;
   }
-  // ---- FT8_FLAG_SUBTRACT: pass 1 (complete record lists), subtract, pass 2 on the residual, merge
+  // ---- FT8_FLAG_SUBTRACT: pass 1 (complete record lists), then per further pass: subtract what the last
+  // pass added, decode the residual, append the new payloads (ft8_set_subtract: 2 to 4 passes, each with
+  // the retries the flags ask for when the setting allows them)
   if (dtype != FT8_F32 && dtype != FT8_I16)
     return fail(c, FT8_E_UNSUPPORTED, "FT8_FLAG_SUBTRACT needs float32 or int16 samples");
-  if ((rc = ensure(c, c->out1, sizeof(ft8_result) * (size_t)n_slots * N))) return rc;
+  const int n_passes = c->sub_passes;
+  const int acc_cap = (n_passes - 1) * N;  // the accumulated list before the last merge
+  if ((rc = ensure(c, c->out1, sizeof(ft8_result) * (size_t)n_slots * acc_cap))) return rc;
   if ((rc = ensure(c, c->out2, sizeof(ft8_result) * (size_t)n_slots * N))) return rc;
   if ((rc = ensure(c, c->counts1, sizeof(int32_t) * (size_t)n_slots))) return rc;
   if ((rc = ensure(c, c->counts2, sizeof(int32_t) * (size_t)n_slots))) return rc;
+  if ((rc = ensure(c, c->sub_pass_counts, sizeof(int32_t) * (size_t)n_slots * n_passes))) return rc;
   if ((rc = ensure(c, c->residual, sizeof(float) * (size_t)n_slots * n_samples))) return rc;
-  ft8_result* out1 = c->out1.as<ft8_result>();
+  ft8_result* acc = c->out1.as<ft8_result>();
   ft8_result* out2 = c->out2.as<ft8_result>();
-  int32_t* counts1 = c->counts1.as<int32_t>();
+  int32_t* acc_counts = c->counts1.as<int32_t>();
   int32_t* counts2 = c->counts2.as<int32_t>();
+  int32_t* pass_counts = c->sub_pass_counts.as<int32_t>();
   float* resid = c->residual.as<float>();
-  if ((rc = decode_pass(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, out1, counts1, N, s))) return rc;
-  if ((rc = subtract_core(c, d_samples, dtype, resid, n_samples, n_slots, slot_stride, n_samples, p, out1, counts1,
-                          N, s)))
+  if ((rc = decode_pass(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, acc, acc_counts, acc_cap, s)))
     return rc;
-  if ((rc = decode_pass(c, resid, FT8_F32, n_samples, n_slots, n_samples, p, out2, counts2, N, s))) return rc;
-  hipError_t e = launch_merge_pass(d_out, d_counts, cap, out1, counts1, N, out2, counts2, N, n_slots, s);
-  if (e != hipSuccess) return hipfail(c, e, "merge launch");
+  if ((rc = subtract_core(c, d_samples, dtype, resid, n_samples, n_slots, slot_stride, n_samples, p, acc, acc_counts,
+                          acc_cap, s)))
+    return rc;
+  for (int k = 2; k <= n_passes; ++k) {
+    if ((rc = decode_pass(c, resid, FT8_F32, n_samples, n_slots, n_samples, p, out2, counts2, N, s))) return rc;
+    const bool last = k == n_passes;
+    hipError_t e = launch_merge_pass(last ? d_out : acc, last ? d_counts : acc_counts, last ? cap : acc_cap, acc,
+                                     acc_counts, acc_cap, out2, counts2, N, n_slots, pass_counts, n_passes, k, s);
+    if (e != hipSuccess) return hipfail(c, e, "merge launch");
+    // the rows this merge appended (from pass_counts' column k - 2 on), fitted on and taken out of the residual
+    if (!last && (rc = subtract_core(c, resid, FT8_F32, resid, n_samples, n_slots, n_samples, n_samples, p, acc,
+                                     acc_counts, acc_cap, s, pass_counts + (k - 2), n_passes)))
+      return rc;
+  }
+  if (n_passes > 2) c->sub_slots = c->sub_cap = -1;  // the fits' scratch was used again: none to report
+  c->subc_slots = n_slots;
+  c->subc_passes = n_passes;
   c->replay_ok = false;
   remember_snr_batch(c, p, g, n_slots, T, F, cap, false);
   whole.done();
@@ -1787,6 +1816,30 @@ int ft8_subtract(ft8_ctx* c, const void* d_samples, int dtype, float* d_residual
   DeviceGuard dg(c->device);
   return subtract_core(c, d_samples, dtype, d_residual, n_samples, n_slots, slot_stride, slot_stride, p, d_res,
                        d_counts, cap, (hipStream_t)stream);
+}
+
+int ft8_set_subtract(ft8_ctx* c, int32_t n_passes, int32_t retry) {
+  if (!c) return FT8_E_ARG;
+  if (n_passes < 2 || n_passes > FT8_SUBTRACT_MAX_PASSES)
+    return fail(c, FT8_E_ARG, "subtract: n_passes must be in [2, " + std::to_string(FT8_SUBTRACT_MAX_PASSES) + "]");
+  if (retry != 0 && retry != 1) return fail(c, FT8_E_ARG, "subtract: retry must be 0 or 1");
+  c->sub_passes = n_passes;
+  c->sub_retry = retry;
+  return FT8_OK;
+}
+
+int ft8_subtract_counts(ft8_ctx* c, int32_t* d_out, int32_t n_slots, int32_t n_passes, void* stream) {
+  StreamOrder order_(c, (hipStream_t)stream);
+  if (!c || !d_out) return fail(c, FT8_E_ARG, "bad argument");
+  if (c->subc_slots < 0)
+    return fail(c, FT8_E_ARG, "the last ft8_decode_batch was no FT8_FLAG_SUBTRACT batch (or had nothing to search)");
+  if (n_slots != c->subc_slots || n_passes != c->subc_passes)
+    return fail(c, FT8_E_ARG, "n_slots / n_passes differ from the last FT8_FLAG_SUBTRACT batch's (" +
+                                  std::to_string(c->subc_slots) + " / " + std::to_string(c->subc_passes) + ")");
+  DeviceGuard dg(c->device);
+  hipError_t e = hipMemcpyAsync(d_out, c->sub_pass_counts.p, sizeof(int32_t) * (size_t)n_slots * n_passes,
+                                hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  return e == hipSuccess ? FT8_OK : hipfail(c, e, "counts copy");
 }
 
 int ft8_subtract_fits(ft8_ctx* c, ft8_sub_fit* d_out, int32_t n_slots, int32_t cap, void* stream) {

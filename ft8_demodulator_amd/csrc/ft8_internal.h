@@ -441,16 +441,20 @@ struct SubLaunch {
   void* est;                   // scratch [n_slots * cap] SubEst records
   int32_t* list;               // scratch [n_slots][cap + 1]: the records to fit (ok, first of their
                                // payload in the slot), in record order, then their count
+  const int32_t* first;        // null, or the slot's first row at first[slot * first_stride]: the rows
+  int first_stride;            // before it are neither fitted nor seen (an accumulated list's earlier passes)
 };
 size_t sub_est_bytes();        // sizeof one SubEst record
 hipError_t launch_sub_est(const SubLaunch& a, hipStream_t s);    // fits of the records (k_sub_est)
 hipError_t launch_sub_apply(const SubLaunch& a, hipStream_t s);  // residual = x - fitted signals
 
-// out[slot] = the pass-1 records out1[slot][0 .. counts1) followed by the pass-2 records
-// out2[slot][0 .. counts2) whose payload no pass-1 record carries (pass_index = 1); counts uncapped
+// out[slot] = the accumulated records out1[slot][0 .. counts1) followed by this pass's records
+// out2[slot][0 .. counts2) whose payload no accumulated record carries (pass_index |= 1); counts
+// uncapped.  out == out1 (cap == cap1, counts == counts1) appends in place.  pass_counts (nullable)
+// [n_slots][n_passes]: column pass - 2 receives counts1, column pass - 1 the new count.
 hipError_t launch_merge_pass(ft8_result* out, int32_t* counts, int cap, const ft8_result* out1,
                              const int32_t* counts1, int cap1, const ft8_result* out2, const int32_t* counts2,
-                             int cap2, int n_slots, hipStream_t s);
+                             int cap2, int n_slots, int32_t* pass_counts, int n_passes, int pass, hipStream_t s);
 
 // ---- frequency-drift correction (drift.hip) ---------------------------------------------------
 struct DriftFitLaunch {

@@ -19,7 +19,8 @@
 // k_sub_apply one workgroup per (slot, tile): residual = x - sum over the slot's fitted signals of
 //            r(n) Re(A(n) exp(i psi(n))), A linearly interpolated between symbol centres; signals
 //            summed in record order (deterministic).
-// k_merge    one wave per slot: pass-2 records with a payload not decoded in pass 1 are appended.
+// k_merge    one wave per slot: a pass's records with a payload no earlier pass decoded are appended to
+//            the slot's accumulated list (pass_index |= 1); the count before and after is recorded.
 #include <algorithm>
 
 #include "baseband.h"
@@ -46,10 +47,13 @@ __device__ __forceinline__ float ramp_f(int n, int L, int nsps) { return tx::gfs
 // k_sub_list: one wave per slot lists the records worth a fit -- ok, and the first record of the
 // slot carrying its payload (a crowded top-k slot decodes ~40 records for ~21 distinct messages) --
 // in record order, and marks every record inactive (k_sub_est then activates the ones it fits), so
-// k_sub_est's workgroups index fits directly instead of one workgroup per record testing itself
+// k_sub_est's workgroups index fits directly instead of one workgroup per record testing itself.
+// a.first (nullable): the slot's first row; the rows before it (an accumulated list's earlier passes,
+// subtracted already) are not listed and shadow nothing
 __global__ __launch_bounds__(kWave) void k_sub_list(SubLaunch a) {
   const int slot = blockIdx.x, lane = threadIdx.x;
   const int cnt = min(a.counts[slot], a.cap);
+  const int row0 = a.first ? max(0, min(a.first[(int64_t)slot * a.first_stride], cnt)) : 0;
   const ft8_result* rs = a.res + (int64_t)slot * a.cap;
   SubEst* est = reinterpret_cast<SubEst*>(a.est) + (int64_t)slot * a.cap;
   int32_t* list = a.list + (int64_t)slot * (a.cap + 1);
@@ -59,8 +63,8 @@ __global__ __launch_bounds__(kWave) void k_sub_list(SubLaunch a) {
     bool keep = false;
     if (j < cnt) {
       const ft8_result r = rs[j];
-      keep = r.ok != 0;
-      for (int q = 0; q < j && keep; ++q) {
+      keep = r.ok != 0 && j >= row0;
+      for (int q = row0; q < j && keep; ++q) {
         if (!rs[q].ok) continue;
         bool eq = true;
         for (int b = 0; b < 10; ++b) eq = eq && rs[q].payload[b] == r.payload[b];
@@ -499,15 +503,21 @@ __device__ __forceinline__ bool same_payload(const ft8_result& p, const ft8_resu
   return eq;
 }
 
+// out may be out1 (with cap == cap1, counts == counts1): the accumulated list grows in place.  The
+// appended rows keep their marks (coherent bits, a-priori hypothesis) and get bit 0.  pass_counts
+// (nullable) [n_slots][n_passes]: the slot's count before this merge goes to column pass - 2 and the
+// count after it to column pass - 1 (pass: this merge's, 2 .. n_passes).
 __global__ __launch_bounds__(kWave) void k_merge(ft8_result* out, int32_t* counts, int cap, const ft8_result* out1,
                                                  const int32_t* counts1, int cap1, const ft8_result* out2,
-                                                 const int32_t* counts2, int cap2) {
+                                                 const int32_t* counts2, int cap2, int32_t* pass_counts,
+                                                 int n_passes, int pass) {
   const int slot = blockIdx.x, lane = threadIdx.x;
   const int c1 = counts1[slot], c1v = min(c1, cap1);
   const int c2 = min(counts2[slot], cap2);
   const ft8_result* p1 = out1 + (int64_t)slot * cap1;
   const ft8_result* p2 = out2 + (int64_t)slot * cap2;
-  for (int c = lane; c < min(c1v, cap); c += kWave) out[(int64_t)slot * cap + c] = p1[c];
+  if (out != out1)
+    for (int c = lane; c < min(c1v, cap); c += kWave) out[(int64_t)slot * cap + c] = p1[c];
   int base = c1;
   for (int c0 = 0; c0 < c2; c0 += kWave) {
     const int c = c0 + lane;
@@ -521,12 +531,18 @@ __global__ __launch_bounds__(kWave) void k_merge(ft8_result* out, int32_t* count
     const unsigned long long m = __ballot(keep);
     const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
     if (keep && pos < cap) {
-      r.pass_index = 1;
+      r.pass_index |= 1;
       out[(int64_t)slot * cap + pos] = r;
     }
     base += __popcll(m);
   }
-  if (lane == 0) counts[slot] = base;
+  if (lane == 0) {
+    counts[slot] = base;
+    if (pass_counts) {
+      pass_counts[(int64_t)slot * n_passes + pass - 2] = c1;
+      pass_counts[(int64_t)slot * n_passes + pass - 1] = base;
+    }
+  }
 }
 
 }  // namespace
@@ -574,10 +590,10 @@ hipError_t launch_sub_apply(const SubLaunch& a, hipStream_t s) {
 
 hipError_t launch_merge_pass(ft8_result* out, int32_t* counts, int cap, const ft8_result* out1,
                              const int32_t* counts1, int cap1, const ft8_result* out2, const int32_t* counts2,
-                             int cap2, int n_slots, hipStream_t s) {
+                             int cap2, int n_slots, int32_t* pass_counts, int n_passes, int pass, hipStream_t s) {
   if (n_slots <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_merge, dim3(n_slots), dim3(kWave), 0, s, out, counts, cap, out1, counts1, cap1, out2, counts2,
-                     cap2);
+                     cap2, pass_counts, n_passes, pass);
   return hipGetLastError();
 }
 

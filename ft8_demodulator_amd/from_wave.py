@@ -51,20 +51,29 @@ def read_wave_file(wave_path: str, verbose: bool = False) -> tuple:
 
 
 def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_errors: int = None, coherent=None,
-                 coherent_drift=None, coherent_nsym: int = 1, device=None, verbose: bool = False,
-                 **decode_kw) -> tuple:
+                 coherent_drift=None, coherent_nsym: int = 1, selection: str = "reference", subtract=None,
+                 device=None, verbose: bool = False, **decode_kw) -> tuple:
     """One file, any PCM width, as one slot through _pipeline.decode_one -> (results, snr_db, patterns)
     and, with coherent, a fourth entry.  snr_db (with snr, else None): one SNR in 2500 Hz per result.
     patterns (with ap, else None): per result the a-priori pattern that rescued it, None for a plain
     decode.  fits (with coherent): per result (dt_s, df_hz) of the coherent fit that rescued it (one
     ft8_coherent_llr call for those records), None for any other decode; with coherent_drift
     (True or (max_rate, n_rates)) the fit is (dt_s, df_hz, rate_hz_per_s); a decode from a joint metric over
-    2 or 3 symbols (coherent_nsym > 1) has MULTI_SYMBOL as a further, last entry."""
+    2 or 3 symbols (coherent_nsym > 1) has MULTI_SYMBOL as a further, last entry.
+    selection: "reference" or "topk".  subtract (True or a pass count in [2, 4]; not with snr): subtract-and-
+    redecode with the retries above in every pass, and a last entry passes: per result the 1-based pass that
+    appended it.  A decode from a residual has no fit entry (the stage call would fit it on the samples)."""
     import torch
     from . import _lib
     from ._pipeline import decode_one
     from .ap import ap_index
+    from .ft8_decode import selection_flags
     from .snr import snr_db_or_nan
+    from .subtract import pass_of, passes_of, subtract_index
+    flags = selection_flags(selection)
+    subtract = passes_of(subtract)
+    if subtract is not None and snr:
+        raise NotImplementedError("no signal reports for a subtract decode")
     data, dtype, sample_rate = _read_raw(wave_path, verbose)
     _lib.require_gpu()
     dev = torch.device("cuda", _lib.device_index(device))
@@ -75,14 +84,18 @@ def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_erro
         h /= np.iinfo(dtype).max
         x, code = torch.from_numpy(h).to(dev), _lib.FT8_F32
     ap = None if ap is None else tuple(ap)
-    results, reports, recs = decode_one(x, code, sample_rate, snr=snr, ap=ap, ap_max_hard_errors=ap_max_hard_errors,
-                                        coherent=coherent, coherent_drift=coherent_drift,
-                                        coherent_nsym=coherent_nsym, **decode_kw)
+    results, reports, recs, *per_pass = decode_one(
+        x, code, sample_rate, snr=snr, ap=ap, ap_max_hard_errors=ap_max_hard_errors, coherent=coherent,
+        coherent_drift=coherent_drift, coherent_nsym=coherent_nsym, flags=flags, subtract=subtract,
+        pass_counts=subtract is not None, **decode_kw)
     out = (results, snr_db_or_nan(reports) if snr else None,
            None if ap is None else [ap[ap_index(r) - 1] if ap_index(r) else None for r in recs])
-    if coherent is None:
-        return out
-    return out + (_coherent_fits(x, code, sample_rate, recs, decode_kw, coherent_drift),)
+    if coherent is not None:
+        fits = _coherent_fits(x, code, sample_rate, recs, decode_kw, coherent_drift)
+        out += ([None if subtract_index(r) else f for r, f in zip(recs, fits)],)
+    if subtract is not None:
+        out += ([pass_of(per_pass[0], i) for i in range(len(recs))],)
+    return out
 
 
 MULTI_SYMBOL = "multi-symbol"   # last entry of the fit of a decode from a multi-symbol set
@@ -163,13 +176,14 @@ def decode_ft8_from_wave_ap(wave_path: str, ap, ap_max_hard_errors: int = None, 
     return results, patterns, snr_db
 
 
-def _print_results(results, text: bool = False, snr=None, ap=None, coherent=None):
+def _print_results(results, text: bool = False, snr=None, ap=None, coherent=None, passes=None):
     """text: one extra `Message:` line per result, the payload unpacked to message text.  snr (one
     value per result): one extra `SNR:` line per result, dB in 2500 Hz.  ap (one pattern or None per
     result): one extra `AP: <pattern>` line for every a-priori decode.  coherent (one (dt_s, df_hz) or
     None per result): one extra `Coherent:` line for every decode from the coherent LLRs; a third entry
     (the drift search's rate, Hz/s) ends the line with `, drift +0.50 Hz/s`, and a last entry MULTI_SYMBOL
-    with `, multi-symbol` after that."""
+    with `, multi-symbol` after that.  passes (one 1-based pass per result): one extra `Pass: k` line for
+    every decode a later pass of a subtract decode appended (k >= 2)."""
     if not results:
         print("No FT8 messages decoded")
         return
@@ -195,6 +209,8 @@ def _print_results(results, text: bool = False, snr=None, ap=None, coherent=None
             fit = coherent[k][:-1] if multi else coherent[k]
             drift = f", drift {fit[2]:+.2f} Hz/s" if len(fit) > 2 else ""
             print(f"Coherent: dt {fit[0] * 1e3:+.2f} ms, df {fit[1]:+.2f} Hz{drift}{', multi-symbol' if multi else ''}")
+        if passes is not None and passes[k] > 1:
+            print(f"Pass: {passes[k]}")
         print(f"CRC check: {status.crc_calculated}")
         print(f"LDPC errors: {status.ldpc_errors}")
         print("-" * 50)
@@ -258,7 +274,21 @@ def main(argv=None):
     parser.add_argument("--coherent-nsym", type=int, choices=(1, 2, 3), default=None, metavar="N",
                         help="with --coherent: also decode joint LLRs over 2 .. N (at most 3) adjacent symbols for "
                              "each of those candidates (default 1: off; such a decode's mark ends with multi-symbol)")
+    parser.add_argument("--selection", choices=("reference", "topk"), default="reference",
+                        help="candidate selection: the reference's, or the max-candidates highest scores")
+    parser.add_argument("--subtract", nargs="?", type=int, const=2, default=None, metavar="PASSES",
+                        help="subtract what each pass decodes and decode the residual again, PASSES passes in all "
+                             "(2 to 4, default 2), with --ap / --coherent in every pass; a decode a later pass "
+                             "added is marked with its pass (not with --snr)")
     args = parser.parse_args(argv)
+    if args.subtract is not None:
+        from .subtract import check_passes
+        try:
+            check_passes(args.subtract)
+        except ValueError as e:
+            parser.error(f"--subtract: {e}")
+        if args.snr:
+            parser.error("--subtract cannot report --snr (the waterfall left is the residual's)")
     coherent = None if args.coherent is None else (True if args.coherent < 0 else args.coherent)
     if args.coherent_drift is not None and coherent is None:
         parser.error("--coherent-drift needs --coherent")
@@ -273,7 +303,7 @@ def main(argv=None):
               bins_per_tone=args.bins_per_tone, steps_per_symbol=args.steps_per_symbol,
               max_candidates=args.max_candidates, min_score=args.min_score, max_iterations=args.max_iterations)
     many = len(paths) > 1
-    if args.ap or args.snr or coherent is not None:
+    if args.ap or args.snr or coherent is not None or args.subtract is not None or args.selection != "reference":
         # the report comes from the decode's own waterfall, an AP decode's mark from its own record:
         # one file at a time, each decoded once (lazily: a file is printed before the next is decoded)
         if args.correction:
@@ -284,6 +314,10 @@ def main(argv=None):
             kw = dict(kw, coherent_drift=args.coherent_drift)
         if args.coherent_nsym is not None:
             kw = dict(kw, coherent_nsym=args.coherent_nsym)
+        if args.selection != "reference":
+            kw = dict(kw, selection=args.selection)
+        if args.subtract is not None:
+            kw = dict(kw, subtract=args.subtract)
         decoded = (_decode_file(path, snr=args.snr, ap=args.ap, ap_max_hard_errors=args.ap_max_hard_errors, **kw)
                    for path in paths)
     elif many:
@@ -291,10 +325,12 @@ def main(argv=None):
     else:
         decoded = [(decode_ft8_from_wave(paths[0], correction=args.correction, **kw), None, None)]
     per_file = []
-    for path, (results, snr, patterns, *fits) in zip(paths, decoded):
+    for path, (results, snr, patterns, *more) in zip(paths, decoded):
         if many:
             print(f"\n== {path}")
-        _print_results(results, args.text, snr, patterns, fits[0] if fits else None)
+        fits = more.pop(0) if coherent is not None and more else None
+        passes = more.pop(0) if args.subtract is not None and more else None
+        _print_results(results, args.text, snr, patterns, fits, passes)
         per_file.append(results)
     return per_file if many else per_file[0]
 

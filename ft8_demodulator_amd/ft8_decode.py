@@ -130,18 +130,21 @@ def create_waterfall_from_spectrogram(spectrogram: np.ndarray, time_osr: int, fr
     return FT8Waterfall(mag=spectrogram, time_osr=time_osr, freq_osr=freq_osr)
 
 
-def selection_flags(selection: str = "reference", subtract: bool = False) -> int:
-    """ft8_params.flags for the build-defined options (include/ft8hip.h FT8_FLAG_*)."""
+def selection_flags(selection: str = "reference", subtract=False) -> int:
+    """ft8_params.flags for the build-defined options (include/ft8hip.h FT8_FLAG_*).  subtract: True or a
+    pass count in [2, 4] (subtract.passes_of) sets FT8_FLAG_SUBTRACT."""
+    from .subtract import passes_of
     if selection not in ("reference", "topk"):
         raise ValueError("selection must be 'reference' or 'topk'")
-    return (_lib.FT8_FLAG_TOPK if selection == "topk" else 0) | (_lib.FT8_FLAG_SUBTRACT if subtract else 0)
+    return ((_lib.FT8_FLAG_TOPK if selection == "topk" else 0) |
+            (_lib.FT8_FLAG_SUBTRACT if passes_of(subtract) is not None else 0))
 
 
 def decode_ft8_message(wave_data, sample_rate: int, bins_per_tone: int = 2, steps_per_symbol: int = 2,
                        max_candidates: int = 20, min_score=10, max_iterations: int = 20,
                        freq_min: float = None, freq_max: float = None, time_min: float = None,
                        time_max: float = None, *, plot: bool = False, verbose: bool = False, device=None,
-                       selection: str = "reference", subtract: bool = False):
+                       selection: str = "reference", subtract=False):
     """ft8_decode.py:288-394 -> [(FT8Message, FT8DecodeStatus, time_sec, freq_hz, score)].
 
     time_sec = abs_time / sample_rate and freq_hz = abs_freq / bins_per_tone * 6.25 relative to the
@@ -149,13 +152,14 @@ def decode_ft8_message(wave_data, sample_rate: int, bins_per_tone: int = 2, step
 
     Build-defined options (outside reference parity, defaults reproduce the reference):
     selection="topk" keeps the max_candidates highest scores; subtract=True subtracts the decoded
-    signals and decodes the residual once more, appending new messages (float32 input only)."""
+    signals and decodes the residual once more, appending new messages (float32 input only); a pass
+    count in [2, 4] instead of True runs that many passes, each subtracting what the last one added."""
     x, code, _ = device_samples(wave_data, device)
     if x.dim() != 1:
         raise ValueError("wave_data must be one-dimensional")
     results = decode_one(x, code, sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score,
                          max_iterations, freq_min, freq_max, time_min, time_max,
-                         flags=selection_flags(selection, subtract))[0]
+                         flags=selection_flags(selection), subtract=subtract or None)[0]
     if plot:
         plan = make_plan(int(x.shape[0]), sample_rate, bins_per_tone, steps_per_symbol, freq_min, freq_max,
                          time_min, time_max)

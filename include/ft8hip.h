@@ -80,16 +80,19 @@ typedef struct ft8_params {
  *                      pass 1 is re-modulated (ft8_encode + GFSK), fitted to the slot (time/
  *                      frequency refinement, per-symbol complex amplitude) and subtracted, and
  *                      the residual is decoded again.  New messages are appended after the
- *                      pass-1 results with pass_index = 1.  F32 and I16 samples only.
+ *                      pass-1 results with pass_index bit 0 set.  F32 and I16 samples only.
+ *                      ft8_set_subtract asks for up to FT8_SUBTRACT_MAX_PASSES passes and for the
+ *                      FT8_FLAG_AP / FT8_FLAG_COHERENT retries inside every pass (default: 2, none).
  *   FT8_FLAG_AP        ft8_decode_batch retries every candidate BP failed on with the context's
  *                      a-priori hypotheses (ft8_set_ap; "a-priori decoding" below).  Rescued
  *                      candidates come out in candidate order among the plain decodes, with
- *                      pass_index >> 4 = hypothesis index + 1.  Not with FT8_FLAG_SUBTRACT.
+ *                      pass_index >> 4 = hypothesis index + 1.  With FT8_FLAG_SUBTRACT only after
+ *                      ft8_set_subtract(ctx, n, 1).
  *   FT8_FLAG_COHERENT  ft8_decode_batch demodulates the best-scoring candidates BP failed on again, coherently
  *                      from the samples ("coherent re-demodulation" below; ft8_set_coherent caps them per
  *                      slot), and decodes the new LLRs.  Rescued candidates come out in candidate order
- *                      among the plain decodes with pass_index bit 1 set.  F32 and I16 samples only; not
- *                      with FT8_FLAG_SUBTRACT.  ft8_set_coherent_drift adds a search over linear
+ *                      among the plain decodes with pass_index bit 1 set.  F32 and I16 samples only; with
+ *                      FT8_FLAG_SUBTRACT only after ft8_set_subtract(ctx, n, 1).  ft8_set_coherent_drift adds a search over linear
  *                      frequency drift to it, ft8_set_coherent_nsym joint LLRs over 2 and 3 symbols
  *                      (both off by default). */
 #define FT8_FLAG_TOPK 1
@@ -109,7 +112,8 @@ typedef struct ft8_result {
   uint16_t cand_index;     /* position in the reference candidate order */
   uint8_t payload[10];     /* FT8Message.payload (77 bits, [9] & 0xF8) */
   uint8_t ok;              /* 1: LDPC converged and CRC matched (ft8_decode_candidate True) */
-  uint8_t pass_index;      /* low nibble bit 0: 0 decoded from the slot, 1 decoded after subtraction (FT8_FLAG_SUBTRACT);
+  uint8_t pass_index;      /* low nibble bit 0: 0 decoded from the slot, 1 appended by any pass >= 2 of an FT8_FLAG_SUBTRACT
+                              batch, i.e. decoded from a residual (which pass: ft8_subtract_counts);
                               bit 1: decoded from the coherent LLRs (FT8_FLAG_COHERENT);
                               bit 2: ... at a drift rate other than 0 (ft8_set_coherent_drift);
                               bit 3: ... from a joint metric over 2 or 3 symbols (ft8_set_coherent_nsym);
@@ -223,7 +227,8 @@ int ft8_bp(ft8_ctx* ctx, const double* d_llr, int32_t n, int32_t max_iterations,
  * decodes in candidate order to d_out[s][0 .. d_counts[s]) (capped at max_results_per_slot;
  * d_counts holds the uncapped count).  With FT8_FLAG_AP the a-priori pass ("a-priori decoding"
  * below) runs between BP and the compaction, on the batch's own LLRs and records: FT8_E_ARG when the
- * context holds no hypotheses, FT8_E_UNSUPPORTED together with FT8_FLAG_SUBTRACT. */
+ * context holds no hypotheses, FT8_E_UNSUPPORTED together with FT8_FLAG_SUBTRACT unless
+ * ft8_set_subtract(ctx, n, 1) lifted that. */
 int ft8_decode_batch(ft8_ctx* ctx, const void* d_samples, int dtype, int64_t n_samples,
                      int32_t n_slots, int64_t slot_stride, const ft8_params* p,
                      ft8_result* d_out, int32_t* d_counts, int32_t max_results_per_slot,
@@ -439,7 +444,7 @@ int ft8_coherent_llr(ft8_ctx* ctx, const void* d_samples, int dtype, int64_t n_s
  * ldpc_errors, and pass_index |= 2; score, slot, abs_time, abs_freq and cand_index do not change, and
  * every other candidate keeps the record plain BP wrote.  The pass runs before the a-priori pass, which
  * sees the STFT LLRs of the candidates still failed.  FT8_E_UNSUPPORTED as for the stage call, and
- * together with FT8_FLAG_SUBTRACT.  Scratch (context-owned, grow-only) per listed candidate: 174 * 8
+ * together with FT8_FLAG_SUBTRACT unless ft8_set_subtract(ctx, n, 1) lifted that.  Scratch (context-owned, grow-only) per listed candidate: 174 * 8
  * bytes of LLRs and 76 bytes of lists, fits and records.  max_per_slot < 0: FT8_E_ARG.  Default 0. */
 int ft8_set_coherent(ft8_ctx* ctx, int32_t max_per_slot);
 
@@ -565,10 +570,11 @@ int ft8_subtract(ft8_ctx* ctx, const void* d_samples, int dtype, float* d_residu
                  int32_t n_slots, int64_t slot_stride, const ft8_params* p, const ft8_result* d_res,
                  const int32_t* d_counts, int32_t cap, void* stream);
 
-/* The signals the last subtraction of this context fitted (ft8_subtract, or pass 1 of an
+/* The signals the last subtraction of this context fitted (ft8_subtract, or pass 1 of a two-pass
  * FT8_FLAG_SUBTRACT ft8_decode_batch, whose cap is max_candidates): fit of record r of slot s at
  * d_out[s * cap + r] for r < min(counts[s], cap), copied device -> device.  n_slots and cap must
- * equal that subtraction's.  The residual is x - sum over the active fits of
+ * equal that subtraction's.  After an FT8_FLAG_SUBTRACT batch of more than two passes the context
+ * holds no valid fits (the scratch was used again by the later subtractions): FT8_E_ARG.  The residual is x - sum over the active fits of
  * ramp(n) Re(A(n) exp(2 pi i phase(n))), A interpolated linearly between symbol centres. */
 typedef struct ft8_sub_fit {
   int32_t active;          /* 1: fitted and subtracted; 0: failed record, or a payload an earlier record carries */
@@ -580,6 +586,42 @@ typedef struct ft8_sub_fit {
   uint8_t tones[80];       /* the payload's re-encoded tone sequence (79 used) */
 } ft8_sub_fit;
 int ft8_subtract_fits(ft8_ctx* ctx, ft8_sub_fit* d_out, int32_t n_slots, int32_t cap, void* stream);
+
+/* ---- FT8_FLAG_SUBTRACT with more than two passes, and with the retries in every pass ---------------
+ * Opt-in and build-defined (a host-side context setting, like ft8_set_coherent; it takes effect at the
+ * next ft8_decode_batch with FT8_FLAG_SUBTRACT).  n_passes in [2, FT8_SUBTRACT_MAX_PASSES], retry 0 or 1;
+ * anything else is FT8_E_ARG and leaves the setting as it was.  Default (2, 0).
+ *
+ * An n-pass batch, per slot, with x_0 the samples and N = max_candidates:
+ *   R_k    the records (compacted, capacity N) of the receive path without FT8_FLAG_SUBTRACT on x_{k-1};
+ *   acc_1  = R_1;  acc_k = acc_{k-1} followed by the ok rows of R_k whose payload no row of acc_{k-1}
+ *          carries (only rows present before the pass count as seen), in R_k order, pass_index |= 1;
+ *   x_k    (k < n) = x_{k-1} minus the fits of the rows pass k appended (k = 1: all of R_1): the rows that
+ *          are ok and the first of their payload among those rows, fitted on x_{k-1} and subtracted in
+ *          record order as ft8_subtract does, in place in the context's float32 residual.
+ * d_out / d_counts receive acc_n under max_results_per_slot; the count is uncapped.  n = 2, retry = 0 is the
+ * two-pass batch described at FT8_FLAG_SUBTRACT.
+ *
+ * retry = 0: FT8_FLAG_AP or FT8_FLAG_COHERENT together with FT8_FLAG_SUBTRACT is FT8_E_UNSUPPORTED.
+ * retry = 1: every pass runs the retries the flags ask for, as a batch without FT8_FLAG_SUBTRACT would on
+ * that pass's input: the coherent pass reads x_{k-1} (from pass 2 on the float32 residual) with the
+ * context's cap, drift search and nsym settings, the a-priori pass sees that pass's STFT LLRs.  A row
+ * rescued at a drift rate other than 0 (pass_index bit 2) is fitted like any other, WITHOUT a drift term:
+ * its subtraction is as good as a constant-frequency fit of it is.
+ *
+ * Scratch (context-owned, grow-only) per slot: (n - 1) N records (40 B) and fits (ft8_sub_fit, 1056 B) and
+ * (n - 1) N + 1 list entries (4 B) for the accumulated rows, N records of the current pass, n counts, and
+ * n_samples floats of residual; n = 2 is what the two-pass batch always took.  ft8_snr_last after any such
+ * batch stays FT8_E_UNSUPPORTED, and slot_stride >= n_samples as before. */
+#define FT8_SUBTRACT_MAX_PASSES 4
+int ft8_set_subtract(ft8_ctx* ctx, int32_t n_passes, int32_t retry);
+
+/* d_out[s * n_passes + k] (device, int32) = the uncapped row count of slot s after pass k + 1 of this
+ * context's last ft8_decode_batch: rows [count_{k-1}, count_k) of the slot (count_{-1} = 0) are the ones
+ * pass k + 1 appended.  The low nibble of pass_index is full, so the pass number is reported here and not
+ * in the record.  FT8_E_ARG unless that batch ran FT8_FLAG_SUBTRACT (and had something to search) with
+ * these n_slots and n_passes. */
+int ft8_subtract_counts(ft8_ctx* ctx, int32_t* d_out, int32_t n_slots, int32_t n_passes, void* stream);
 
 /* ---- frequency-drift correction (ft8_beacon_receiver/frequency_correction.py) -------------
  * Paths below are relative to src/ft8_tools/ft8_beacon_receiver/.  Parameters of
