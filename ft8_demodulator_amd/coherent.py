@@ -275,6 +275,55 @@ def coherent_restate(samples, cand, slot_of, fs, nperseg, nfft, steps_per_symbol
     return out
 
 
+def retry_list(records, cap=None):
+    """The retry pass's list (k_retry_list without a gate; csrc/ft8_internal.h, RetryLists): records is a
+    structured array with the ft8_result fields that holds every slot's candidates with slot and cand_index
+    filled -> indices into records, int64: per slot, in slot order, the first `cap` (None: all) records with
+    ok == 0, in cand_index order."""
+    out = []
+    for s in np.unique(records["slot"]):
+        idx = np.nonzero((records["slot"] == s) & (records["ok"] == 0))[0]
+        out += idx[np.argsort(records["cand_index"][idx], kind="stable")][:cap].tolist()
+    return np.array(out, dtype=np.int64)
+
+
+def coherent_pass_restate(records, listed, llr, fits, max_iterations, bp_decode, decode_tail, drifts=None, valid=None):
+    """What the coherent pass of ft8_decode_batch does to the records, on the CPU: records as retry_list takes
+    them, listed = retry_list(records, cap), and the stage call's results for the listed candidates -- llr
+    [len(listed), 174] or [len(listed), S, 174], fits FIT_DTYPE, and where the pass ran with them drifts
+    DRIFT_DTYPE and the validity bytes `valid` -> an updated copy of records.
+    bp_decode(llr, iters) -> (plain, errors) and decode_tail(plain, errors) -> (ok, payload, crc_e, crc_c) are
+    the reference's (tests pass the oracle's), as in ap.ap_restate.
+
+    The pass decodes set after set over the lists and merges after each (coherent_pass, csrc/capi.hip); this
+    walks the same attempts per list position.  k_coh_merge (csrc/coherent.hip) accepts the attempt of set s
+    where the decode is ok and fits.status == 0, and with validity bytes only where bit s is set and the record
+    is not ok yet, so the first valid set that decodes wins; a record that was ok before the pass is never
+    listed and never touched.  retry_accept (csrc/ft8_internal.h) then writes ok, payload, crc_extracted,
+    crc_calculated and ldpc_errors and ORs pass_index with 2, with 4 more where drifts.rate_hz_per_s != 0 and 8
+    more for a set after the first; score, slot, abs_time, abs_freq and cand_index stay the record's."""
+    out = np.array(records, copy=True)
+    llr = np.asarray(llr, dtype=np.float64)
+    if llr.ndim == 2:
+        llr = llr[:, None, :]
+    for pos, i in enumerate(listed):
+        if out["ok"][i] or fits["status"][pos] != STATUS_VALID:
+            continue
+        for s in range(llr.shape[1]):
+            if valid is not None and not (int(valid[pos]) >> s) & 1:
+                continue
+            plain, err = bp_decode(llr[pos, s], max_iterations)
+            ok, payload, ce, cc = decode_tail(plain, err)
+            if ok:
+                out["ok"][i] = 1
+                out["payload"][i] = np.frombuffer(bytes(payload), dtype=np.uint8)
+                out["crc_extracted"][i], out["crc_calculated"][i], out["ldpc_errors"][i] = ce, cc, err
+                drifted = drifts is not None and drifts["rate_hz_per_s"][pos] != 0
+                out["pass_index"][i] |= 2 | (4 if drifted else 0) | (8 if s > 0 else 0)
+                break
+    return out
+
+
 def near_tie(metric, rel=1e-5) -> bool:
     """Whether a metric grid's two largest values differ by less than rel (relative to the largest)."""
     m = np.sort(np.asarray(metric, dtype=np.float64).reshape(-1))

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import ap_cases as C
+import retry_cases as R
 
 pytestmark = pytest.mark.gpu
 
@@ -152,52 +153,14 @@ def _flags():
 
 @pytest.fixture(scope="module")
 def e2e(gpu, oracle):
-    """The expectation, from the device's own LLRs: ft8_stft, ft8_sync_select and ft8_llr on the device,
-    then the CPU restatement -> per slot the records the AP batch must return (read-only), and all
-    records of every candidate."""
-    from ft8_demodulator_amd import ap
-    from ft8_demodulator_amd._pipeline import make_params, make_plan
-    _lib = _L()
-    torch = gpu
-    x = C.e2e_samples()
-    ctx = _lib.Context(0)
-    L, st = _lib.lib(), _lib.stream_handle(0)
-    plan = make_plan(C.E2E_N, C.E2E_FS)
-    N = E2E["max_candidates"]
-    p = make_params(plan, N, E2E["min_score"], ITERS, _flags())
-    d_x = torch.from_numpy(np.array(x)).cuda()
-    T, F = plan.T, plan.F
-    d_wf = torch.empty(2, T, F, dtype=torch.float32, device="cuda")
-    ctx.check(L.ft8_stft(ctx.handle, _lib.ptr(d_x), _lib.FT8_F32, C.E2E_N, 2, C.E2E_N, ctypes.byref(p), _lib.ptr(d_wf),
-                         st), "ft8_stft")
-    d_cand = torch.zeros(2, N, 2, dtype=torch.int32, device="cuda")
-    d_score = torch.zeros(2, N, dtype=torch.float64, device="cuda")
-    d_cnt = torch.zeros(2, dtype=torch.int32, device="cuda")
-    ctx.check(L.ft8_sync_select(ctx.handle, _lib.ptr(d_wf), 0, 2, T, F, ctypes.byref(p), _lib.ptr(d_cand),
-                                _lib.ptr(d_score), _lib.ptr(d_cnt), None, st), "ft8_sync_select")
-    cand, score, cnt = d_cand.cpu().numpy(), d_score.cpu().numpy(), d_cnt.cpu().numpy()
-    rows = [(s, int(cand[s, i, 0]), int(cand[s, i, 1])) for s in range(2) for i in range(int(cnt[s]))]
-    d_c3 = torch.tensor(rows, dtype=torch.int32, device="cuda")
-    d_llr = torch.empty(len(rows), 174, dtype=torch.float64, device="cuda")
-    ctx.check(L.ft8_llr(ctx.handle, _lib.ptr(d_wf), 0, T, F, 2, 2, _lib.ptr(d_c3), len(rows), 1, _lib.ptr(d_llr), st),
-              "ft8_llr")
-    llr = d_llr.cpu().numpy()
-    rec0 = C.plain_records(llr)
-    k = 0
-    for s in range(2):
-        for i in range(int(cnt[s])):
-            rec0["score"][k], rec0["slot"][k], rec0["cand_index"][k] = score[s, i], s, i
-            rec0["abs_time"][k], rec0["abs_freq"][k] = cand[s, i]
-            k += 1
-    hyps = [ap.ap_hypothesis(t) for t in AP]
-    ref, hard = C.restate(llr, rec0, hyps, ap.DEFAULT_MAX_HARD_ERRORS)
-    ref.setflags(write=False)
-    return {"all": ref, "plain": rec0, "per_slot": [ref[(ref["slot"] == s) & (ref["ok"] == 1)] for s in range(2)]}
+    """The expectation, from the device's own LLRs (retry_cases.expectation without a coherent pass) -> per
+    slot the records the AP batch must return (read-only), and all records of every candidate."""
+    e = R.expectation(C.e2e_samples(), C.E2E_FS, E2E, ap=AP)
+    return {"all": e["both"], "plain": e["plain"], "per_slot": [R.per_slot(e["both"], s) for s in range(2)]}
 
 
 def _decoder(**kw):
-    from ft8_demodulator_amd._pipeline import SlotDecoder
-    return SlotDecoder(sample_rate=C.E2E_FS, max_iterations=ITERS, flags=kw.pop("flags", _flags()), **E2E, **kw)
+    return R.decoder(C.E2E_FS, E2E, **kw)
 
 
 def test_e2e_expectation_shows_every_outcome(e2e):

@@ -9,6 +9,7 @@ import pytest
 import ap_cases as A
 import coherent_cases as C
 import drift_cases as Dc
+import retry_cases as R
 
 pytestmark = pytest.mark.gpu
 
@@ -118,89 +119,20 @@ E2E_LATE = dict(max_candidates=80, min_score=2)
 
 
 def _decoder(search=E2E, **kw):
-    from ft8_demodulator_amd._pipeline import SlotDecoder
-    return SlotDecoder(C.FS, max_iterations=ITERS, flags=_L().FT8_FLAG_TOPK, **search, **kw)
-
-
-def _late_cap(plain):
-    """(slot, cap) from the plain records alone, as test_gpu_coherent.py chooses it: the slot with the most
-    failed candidates past its first 64, and a cap halfway between its failed candidates among the first
-    64 and all its failed ones."""
-    fails = [(int(((plain["slot"] == s) & (plain["ok"] == 0) & (plain["cand_index"] < 64)).sum()),
-              int(((plain["slot"] == s) & (plain["ok"] == 0)).sum())) for s in range(3)]
-    s = max(range(3), key=lambda i: fails[i][1] - fails[i][0])
-    return s, (fails[s][0] + fails[s][1] + 1) // 2
-
-
-def _expectation(gpu, oracle, search, cap):
-    """test_gpu_coherent.py's construction on the drifting slots: ft8_stft, ft8_sync_select and ft8_llr give
-    every candidate's STFT LLRs, the oracle's BP the plain records; each slot's first `cap` (a number, or a
-    function of the plain records that returns (slot, cap)) failed candidates get the stage call's LLRs
-    with the drift search, decoded by the oracle again; an accepted attempt sets pass_index 2, and 6 where
-    the stage call's winning rate is not 0."""
-    from ft8_demodulator_amd._pipeline import make_params, make_plan
-    from ft8_demodulator_amd.ldpc_decoder import coherent_llr_batch
-    _lib, torch = _L(), gpu
-    x = np.array(Dc.stage_slots_12k()["x"])
-    n_slots, n = x.shape
-    ctx = _lib.Context(0)
-    L, st = _lib.lib(), _lib.stream_handle(0)
-    plan = make_plan(n, C.FS)
-    N = search["max_candidates"]
-    p = make_params(plan, N, search["min_score"], ITERS, _lib.FT8_FLAG_TOPK)
-    d_x = torch.from_numpy(x).cuda()
-    T, F = plan.T, plan.F
-    d_wf = torch.empty(n_slots, T, F, dtype=torch.float32, device="cuda")
-    ctx.check(L.ft8_stft(ctx.handle, _lib.ptr(d_x), _lib.FT8_F32, n, n_slots, n, ctypes.byref(p), _lib.ptr(d_wf), st),
-              "ft8_stft")
-    d_cand = torch.zeros(n_slots, N, 2, dtype=torch.int32, device="cuda")
-    d_score = torch.zeros(n_slots, N, dtype=torch.float64, device="cuda")
-    d_cnt = torch.zeros(n_slots, dtype=torch.int32, device="cuda")
-    ctx.check(L.ft8_sync_select(ctx.handle, _lib.ptr(d_wf), 0, n_slots, T, F, ctypes.byref(p), _lib.ptr(d_cand),
-                                _lib.ptr(d_score), _lib.ptr(d_cnt), None, st), "ft8_sync_select")
-    cand, score, cnt = d_cand.cpu().numpy(), d_score.cpu().numpy(), d_cnt.cpu().numpy()
-    rows = [(s, int(cand[s, i, 0]), int(cand[s, i, 1])) for s in range(n_slots) for i in range(int(cnt[s]))]
-    d_c3 = torch.tensor(rows, dtype=torch.int32, device="cuda")
-    d_llr = torch.empty(len(rows), 174, dtype=torch.float64, device="cuda")
-    ctx.check(L.ft8_llr(ctx.handle, _lib.ptr(d_wf), 0, T, F, 2, 2, _lib.ptr(d_c3), len(rows), 1, _lib.ptr(d_llr), st),
-              "ft8_llr")
-    rec0 = A.plain_records(d_llr.cpu().numpy())
-    k = 0
-    for s in range(n_slots):
-        for i in range(int(cnt[s])):
-            rec0["score"][k], rec0["slot"][k], rec0["cand_index"][k] = score[s, i], s, i
-            rec0["abs_time"][k], rec0["abs_freq"][k] = cand[s, i]
-            k += 1
-    slot = None
-    if callable(cap):
-        slot, cap = cap(rec0)
-    listed = [i for s in range(n_slots) for i in np.nonzero((rec0["slot"] == s) & (rec0["ok"] == 0))[0][:cap]]
-    cl, cf, cd = coherent_llr_batch(x, [(rows[i][1], rows[i][2]) for i in listed], [rows[i][0] for i in listed], C.FS,
-                                    drift=Dc.DRIFT)
-    coh = np.array(rec0, copy=True)
-    for i, v, f, d in zip(listed, cl, cf, cd):
-        ok, pay, ce, cc, err = C.decode_llr(oracle, v)
-        if ok and f["status"] == 0:
-            coh["ok"][i], coh["pass_index"][i] = 1, 6 if d["rate_index"] != (Dc.DRIFT[1] - 1) // 2 else 2
-            coh["payload"][i] = np.frombuffer(pay, dtype=np.uint8)
-            coh["crc_extracted"][i], coh["crc_calculated"][i], coh["ldpc_errors"][i] = ce, cc, err
-    for a in (rec0, coh):
-        a.setflags(write=False)
-    return {"x": x, "plain": rec0, "coherent": coh, "listed": listed, "cap": cap, "slot": slot}
+    return R.decoder(C.FS, search, **kw)
 
 
 @pytest.fixture(scope="module")
 def e2e(gpu, oracle):
-    return _expectation(gpu, oracle, E2E, CAP)
+    return R.expectation(Dc.stage_slots_12k()["x"], C.FS, E2E, CAP, drift=Dc.DRIFT)
 
 
 @pytest.fixture(scope="module")
 def e2e_late(gpu, oracle):
-    return _expectation(gpu, oracle, E2E_LATE, _late_cap)
+    return R.expectation(Dc.stage_slots_12k()["x"], C.FS, E2E_LATE, R.late_cap, drift=Dc.DRIFT)
 
 
-def _per_slot(rec, s):
-    return rec[(rec["slot"] == s) & (rec["ok"] == 1)]
+_per_slot = R.per_slot
 
 
 def test_e2e_expectation_shows_every_outcome(e2e, e2e_late):

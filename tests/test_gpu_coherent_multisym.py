@@ -11,6 +11,7 @@ import ap_cases as A
 import coherent_cases as C
 import drift_cases as Dc
 import multisym_cases as M
+import retry_cases as R
 
 pytestmark = pytest.mark.gpu
 
@@ -174,17 +175,15 @@ E2E, CAP, AP = M.E2E, M.CAP, M.AP
 
 
 def _decoder(search=E2E, **kw):
-    from ft8_demodulator_amd._pipeline import SlotDecoder
-    return SlotDecoder(C.FS, max_iterations=ITERS, flags=_L().FT8_FLAG_TOPK, **search, **kw)
+    return R.decoder(C.FS, search, **kw)
 
 
 @pytest.fixture(scope="module")
 def e2e(gpu, oracle):
-    return M.expectation(gpu, _L(), oracle, True)
+    return R.expectation(M.e2e_slots()[0], C.FS, E2E, CAP, nsym=M.S, ap=AP)
 
 
-def _per_slot(rec, s):
-    return rec[(rec["slot"] == s) & (rec["ok"] == 1)]
+_per_slot = R.per_slot
 
 
 def test_e2e_expectation_shows_every_outcome(e2e):
@@ -226,6 +225,31 @@ def test_e2e_with_ap(gpu, e2e):
         A.records_equal(got[s], _per_slot(e2e["both"], s))
         assert all(ap.ap_index(r) == 0 for r in got[s] if coherent.coherent_index(r))
     assert any(coherent.multisymbol_index(r) for s in range(9) for r in got[s])
+
+
+DRIFT_CAP = 6
+
+
+@pytest.fixture(scope="module")
+def e2e_drift(gpu, oracle):
+    return R.expectation(Dc.stage_slots_12k()["x"], C.FS, E2E, DRIFT_CAP, drift=Dc.DRIFT, nsym=2, ap=AP)
+
+
+def test_e2e_drift_search_and_sets_together(gpu, e2e_drift):
+    """The drifting slots of the drift tests with the drift search, two sets and the a-priori pass at once
+    (k_coherent<.., CohDrift, CohMulti>; k_coh_merge ORs 4 and 8 into the 2): the batch's records equal the
+    construction's with and without AP.  On the expectation alone: a rescue at a rate other than 0."""
+    coh = e2e_drift["coherent"]
+    rescued = coh[(coh["pass_index"] & 2) != 0]
+    print("rescues", len(rescued), "at a rate other than 0", int(((rescued["pass_index"] & 4) != 0).sum()),
+          "from set 2", int(((rescued["pass_index"] & 8) != 0).sum()), "listed", len(e2e_drift["listed"]))
+    assert ((rescued["pass_index"] & 4) != 0).any()
+    x = gpu.from_numpy(e2e_drift["x"]).cuda()
+    for ap_kw, key in ((dict(ap=AP), "both"), ({}, "coherent")):
+        got = _decoder(coherent=DRIFT_CAP, coherent_drift=Dc.DRIFT, coherent_nsym=2, **ap_kw).records(x)
+        assert len(got) == 3
+        for s in range(3):
+            A.records_equal(got[s], _per_slot(e2e_drift[key], s))
 
 
 def test_off_means_off_in_the_whole_path(gpu):
