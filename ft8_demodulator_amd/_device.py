@@ -162,6 +162,36 @@ def ap_decode(llrs, records, max_iterations):
     return res.cpu().numpy()[: n * _lib.RESULT_DTYPE.itemsize].view(_lib.RESULT_DTYPE).copy(), hard.cpu().numpy()[:n]
 
 
+def coherent_ap_decode(llrs, records, max_iterations, valid=None):
+    """ft8_coherent_ap_decode: coherent LLRs [n, 174] or [n, S, 174], the records ft8_bp left and the validity
+    bytes uint8 [n] (None: every set usable) -> (records updated by the context's a-priori hypotheses
+    (Context.set_ap) on those LLRs, hard int16 [n])."""
+    torch = _lib.require_gpu()
+    ctx = _lib.context()
+    L = np.asarray(llrs, dtype=np.float64)
+    if L.ndim == 2:
+        L = L[:, None, :]
+    if L.ndim != 3 or L.shape[2] != 174:
+        raise ValueError("llrs must be [n, 174] or [n, S, 174]")
+    n, S = int(L.shape[0]), int(L.shape[1])
+    rec = np.ascontiguousarray(np.asarray(records, dtype=_lib.RESULT_DTYPE).reshape(-1))
+    if len(rec) != n:
+        raise ValueError(f"{n} LLR vectors but {len(rec)} records")
+    a = torch.from_numpy(np.concatenate([np.ascontiguousarray(L).reshape(-1), np.zeros(1)])).cuda()
+    res = torch.from_numpy(np.concatenate([rec.view(np.uint8), np.zeros(8, np.uint8)])).to(a.device)
+    hard = torch.zeros(max(n, 1), dtype=torch.int16, device=a.device)
+    d_v = None
+    if valid is not None:
+        v = np.ascontiguousarray(np.asarray(valid, dtype=np.uint8).reshape(-1))
+        if len(v) != n:
+            raise ValueError(f"{n} LLR vectors but {len(v)} validity bytes")
+        d_v = torch.from_numpy(np.concatenate([v, np.zeros(1, np.uint8)])).to(a.device)
+    ctx.check(_lib.lib().ft8_coherent_ap_decode(ctx.handle, _lib.ptr(a), S, None if d_v is None else _lib.ptr(d_v),
+                                                _lib.ptr(res), n, int(max_iterations), _lib.ptr(hard),
+                                                _lib.stream_handle()), "ft8_coherent_ap_decode")
+    return res.cpu().numpy()[: n * _lib.RESULT_DTYPE.itemsize].view(_lib.RESULT_DTYPE).copy(), hard.cpu().numpy()[:n]
+
+
 def coherent_llr(samples, cand, slot_of, sample_rate=12000, bins_per_tone=2, steps_per_symbol=2, t_lo=0, f_lo=0,
                  code=None, drift=None, nsym=1):
     """ft8_coherent_llr: samples [n_slots, n_samples] (float32, or int16 PCM; NumPy or a GPU tensor with

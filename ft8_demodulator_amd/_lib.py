@@ -180,6 +180,8 @@ def lib():
             "ft8_coherent_nsym_llr": ([vp, vp, ctypes.c_int, i64, i32, i64, P, vp, vp, i32, ctypes.c_float, i32, vp, vp,
                                        vp, i32, vp, vp], ctypes.c_int),
             "ft8_set_subtract": ([vp, i32, i32], ctypes.c_int),
+            "ft8_set_coherent_ap": ([vp, i32], ctypes.c_int),
+            "ft8_coherent_ap_decode": ([vp, vp, i32, vp, vp, i32, i32, vp, vp], ctypes.c_int),
             "ft8_subtract_counts": ([vp, vp, i32, i32, vp], ctypes.c_int),
         }
         stale_ok = os.environ.get("FT8HIP_ALLOW_STALE") == "1"
@@ -234,7 +236,7 @@ EXPORTED_SYMBOLS = (
     "ft8_unpack77", "ft8_unpack77_host", "ft8_hash_call", "ft8_noise_floor", "ft8_snr", "ft8_snr_last",
     "ft8_set_ap", "ft8_ap_decode", "ft8_set_coherent", "ft8_coherent_llr",
     "ft8_set_coherent_drift", "ft8_coherent_drift_llr", "ft8_set_coherent_nsym", "ft8_coherent_nsym_llr",
-    "ft8_set_subtract", "ft8_subtract_counts")
+    "ft8_set_subtract", "ft8_subtract_counts", "ft8_set_coherent_ap", "ft8_coherent_ap_decode")
 
 
 def limits():
@@ -339,6 +341,11 @@ class Context:
         """ft8_set_coherent_nsym: an FT8_FLAG_COHERENT batch also decodes joint LLRs over 2 .. max_nsym
         (<= 3) symbols; 1: off."""
         self.check(lib().ft8_set_coherent_nsym(self.handle, int(max_nsym)), "ft8_set_coherent_nsym")
+
+    def set_coherent_ap(self, on: bool = False):
+        """ft8_set_coherent_ap: a batch with both FT8_FLAG_COHERENT and FT8_FLAG_AP also retries the candidates
+        the coherent pass listed and left failed with the a-priori hypotheses clamped on the coherent LLRs."""
+        self.check(lib().ft8_set_coherent_ap(self.handle, int(bool(on))), "ft8_set_coherent_ap")
 
     def set_subtract(self, n_passes: int = 2, retry: bool = False):
         """ft8_set_subtract: the passes (2..4) of an FT8_FLAG_SUBTRACT batch and whether every pass runs the

@@ -227,7 +227,8 @@ class SlotDecoder:
     def __init__(self, sample_rate=12000, bins_per_tone=2, steps_per_symbol=2, max_candidates=20,
                  min_score=10, max_iterations=20, freq_min=None, freq_max=None, time_min=None,
                  time_max=None, device=None, flags=0, max_results_per_slot=None, context=None, ap=None,
-                 ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1, subtract=None):
+                 ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1, subtract=None,
+                 coherent_ap=False):
         """subtract: True or a pass count in [2, 4] (True: 2) -- sets FT8_FLAG_SUBTRACT: what each pass decodes is
         subtracted and the residual decoded again, that many passes in all, every pass with the ap / coherent
         retries asked for below (ft8_set_subtract(n, 1)); the default capacity holds n * max_candidates rows.
@@ -244,7 +245,10 @@ class SlotDecoder:
         <= 33) linear frequency drift rates over +-max_rate (<= 4; True: 1.0, 9) for every listed
         candidate (ft8_set_coherent_drift); needs coherent.  None / False: off.
         coherent_nsym: 1, 2 or 3 -- the coherent pass also decodes joint LLRs over 2 .. coherent_nsym symbols
-        for every listed candidate (ft8_set_coherent_nsym); more than 1 needs coherent.  1: off."""
+        for every listed candidate (ft8_set_coherent_nsym); more than 1 needs coherent.  1: off.
+        coherent_ap: True -- the candidates the coherent pass listed and left failed are also retried with the
+        ap patterns clamped on their coherent LLRs, before the a-priori pass sees the STFT LLRs
+        (ft8_set_coherent_ap); needs both ap and coherent.  False: off."""
         from . import ap as _ap
         from . import coherent as _coh
         from . import subtract as _sub
@@ -252,6 +256,9 @@ class SlotDecoder:
         if self.subtract is not None:
             flags |= _lib.FT8_FLAG_SUBTRACT
         self.coherent_nsym = _coh.check_nsym(coherent_nsym)   # ValueError for what the library refuses
+        self.coherent_ap = bool(coherent_ap)
+        if self.coherent_ap and (ap is None or coherent is None or coherent is False):
+            raise ValueError("coherent_ap needs both ap and coherent")
         if self.coherent_nsym > 1 and (coherent is None or coherent is False):
             raise ValueError("coherent_nsym needs coherent")
         if coherent_drift is None or coherent_drift is False:
@@ -345,6 +352,7 @@ class SlotDecoder:
             self.ctx.set_coherent(self.coherent)
             self.ctx.set_coherent_drift(*(self.coherent_drift or (0.0, 1)))
             self.ctx.set_coherent_nsym(self.coherent_nsym)
+            self.ctx.set_coherent_ap(self.coherent_ap)
         if self.flags & _lib.FT8_FLAG_SUBTRACT:
             # every batch states its own setting, so a shared context never carries the opt-in over to a
             # decoder built with the flag alone (whose two passes refuse the retries)
@@ -485,7 +493,7 @@ def decode_slots(samples, sample_rate=12000, **kwargs):
 def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_candidates=20, min_score=10,
                max_iterations=20, freq_min=None, freq_max=None, time_min=None, time_max=None, *, flags=0, snr=False,
                ap=None, ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1, subtract=None,
-               pass_counts=False):
+               pass_counts=False, coherent_ap=False):
     """One slot, x [N] on the GPU with its ft8 dtype code, through a SlotDecoder of its own:
     -> (decode_ft8_message's 5-tuples, with snr the ft8_snr_rec records aligned with them else None,
     the ft8_result records) and, with pass_counts (a subtract decode), the slot's row of
@@ -499,7 +507,7 @@ def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_ca
         dec = SlotDecoder(sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score, max_iterations,
                           freq_min, freq_max, time_min, time_max, device=x.device, flags=flags, ap=ap,
                           ap_max_hard_errors=ap_max_hard_errors, coherent=coherent, coherent_drift=coherent_drift,
-                          coherent_nsym=coherent_nsym, subtract=subtract)
+                          coherent_nsym=coherent_nsym, subtract=subtract, coherent_ap=coherent_ap)
         recs, _, reps = (v if v is None else v[0] for v in dec._fetch(x.unsqueeze(0), code, snr=snr))
         if pass_counts:
             per_pass = dec.pass_counts()[0]

@@ -324,6 +324,52 @@ def coherent_pass_restate(records, listed, llr, fits, max_iterations, bp_decode,
     return out
 
 
+def coherent_ap_restate(records, listed, llr, fits, hyps, max_iterations, max_hard_errors, bp_decode, decode_tail,
+                        drifts=None, valid=None):
+    """The a-priori retries on the coherent LLRs (include/ft8hip.h, "coherent_ap"; ft8_set_coherent_ap), on the
+    CPU: records as the coherent pass left them (coherent_pass_restate's result), listed, llr, fits, drifts and
+    valid as that function takes them, hyps [(mask, value)] as ap.ap_hypothesis builds them -> (an updated copy
+    of records, hard int16 indexed like records: the accepted attempt's hard errors, -1 elsewhere).
+    bp_decode and decode_tail are the reference's, injected as in coherent_pass_restate and ap.ap_restate.
+
+    A listed position is tried while its record is not ok and fits.status == 0.  Its sets n are those whose
+    validity bit is set (every one without `valid`) and whose a_n = ap.ap_magnitude(L_n) is neither NaN nor 0.
+    Attempts run hypothesis outer, set inner: BP and the tail on ap.ap_llr(L_n, mask, value), accepted by
+    ap.ap_accept against the unclamped L_n.  The first accepted attempt writes ok, payload, crc_extracted,
+    crc_calculated and ldpc_errors and ORs pass_index with 2 | (h + 1) << 4, with 4 more where
+    drifts.rate_hz_per_s != 0 and 8 more for n > 0; later attempts of the position are not made."""
+    from . import ap as _ap
+    out = np.array(records, copy=True)
+    hard_out = np.full(len(out), -1, dtype=np.int16)
+    llr = np.asarray(llr, dtype=np.float64)
+    if llr.ndim == 2:
+        llr = llr[:, None, :]
+    for pos, i in enumerate(listed):
+        if out["ok"][i] or fits["status"][pos] != STATUS_VALID:
+            continue
+        sets = []
+        for n in range(llr.shape[1]):
+            if valid is not None and not (int(valid[pos]) >> n) & 1:
+                continue
+            a = _ap.ap_magnitude(llr[pos, n])
+            if a == a and a != 0.0:
+                sets.append(n)
+        for h, n in ((h, n) for h in range(len(hyps)) for n in sets):
+            mask, value = hyps[h]
+            plain, err = bp_decode(_ap.ap_llr(llr[pos, n], mask, value), max_iterations)
+            ok, payload, ce, cc = decode_tail(plain, err)
+            good, hard = _ap.ap_accept(ok, payload, plain, llr[pos, n], mask, value, max_hard_errors)
+            if good:
+                out["ok"][i] = 1
+                out["payload"][i] = np.frombuffer(bytes(payload), dtype=np.uint8)
+                out["crc_extracted"][i], out["crc_calculated"][i], out["ldpc_errors"][i] = ce, cc, err
+                drifted = drifts is not None and drifts["rate_hz_per_s"][pos] != 0
+                out["pass_index"][i] |= 2 | ((h + 1) << 4) | (4 if drifted else 0) | (8 if n > 0 else 0)
+                hard_out[i] = hard
+                break
+    return out, hard_out
+
+
 def near_tie(metric, rel=1e-5) -> bool:
     """Whether a metric grid's two largest values differ by less than rel (relative to the largest)."""
     m = np.sort(np.asarray(metric, dtype=np.float64).reshape(-1))

@@ -159,4 +159,178 @@ hipError_t launch_ap_merge(const ApLaunch& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---- a-priori retries on the coherent LLRs (ft8_internal.h, CohApLaunch) ----------------------------
+//   k_cohap_amax   one wave per (position, set): a_n, 0 where the position or the set is not tried
+//   k_cohap_list   one wave per slot: the attempts (j, h, n) with a_n != 0, hypothesis outer and set inner
+//                  within a position, compacted -> att (k_bp's candidate lists) and where
+//   k_cohap_clamp  one wave per listed attempt: set n's LLRs with hypothesis h's bits at +a_n / -a_n
+//   k_bp           unchanged, once over all attempts -> plain, res_a
+//   k_cohap_merge  one wave per position: the first attempt in order that passes the acceptance test
+//                  rewrites the record
+namespace {
+
+__device__ __forceinline__ int cohap_count(const CohApLaunch& a, int slot) {
+  return a.count ? min(a.M, max(a.count[slot], 0)) : a.M;
+}
+// attempts per slot (the stride of the attempt lists) and per position
+__device__ __forceinline__ int64_t cohap_stride(const CohApLaunch& a) { return (int64_t)a.M * a.H * a.S; }
+// the record of list position pos = slot * M + j, null where the list names none
+__device__ __forceinline__ ft8_result* cohap_record(const CohApLaunch& a, int slot, int j) {
+  const int orig = a.list ? a.list[(int64_t)slot * a.M + j] : j;
+  return orig >= 0 && orig < a.N ? a.res + (int64_t)slot * a.N + orig : nullptr;
+}
+
+__global__ __launch_bounds__(kApWaves* kWave) void k_cohap_amax(CohApLaunch a) {
+  const int lane = threadIdx.x % kWave;
+  const int64_t item = (int64_t)blockIdx.x * kApWaves + threadIdx.x / kWave;
+  if (item >= (int64_t)a.n_slots * a.M * a.S) return;
+  const int64_t pos = item / a.S;
+  const int n = (int)(item % a.S), slot = (int)(pos / a.M), j = (int)(pos % a.M);
+  bool tried = j < cohap_count(a, slot) && (!a.fit || a.fit[pos].status == 0) && (!a.valid || ((a.valid[pos] >> n) & 1));
+  if (tried) {
+    const ft8_result* rec = cohap_record(a, slot, j);
+    tried = rec && !rec->ok;
+  }
+  if (!tried) {
+    if (lane == 0) a.amax[item] = 0.0;
+    return;
+  }
+  const double* L = a.llr + pos * a.pos_stride + n * a.set_stride;
+  double m = 0.0;
+  bool nan = false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int i = lane + kWave * k;
+    if (i < FT8_LDPC_N) {
+      const double v = L[i];
+      nan |= v != v;
+      m = fmax(m, fabs(v));
+    }
+  }
+  for (int d = kWave / 2; d > 0; d >>= 1) m = fmax(m, __shfl_xor(m, d));
+  const bool any_nan = __ballot(nan) != 0;
+  if (lane == 0) a.amax[item] = any_nan ? 0.0 : 1.01 * m;
+}
+
+__global__ __launch_bounds__(kWave) void k_cohap_list(CohApLaunch a) {
+  const int slot = blockIdx.x, lane = threadIdx.x;
+  const int per = a.H * a.S;
+  const int64_t A = cohap_stride(a), l0 = (int64_t)slot * A;
+  const int64_t total = (int64_t)cohap_count(a, slot) * per;   // <= A
+  int64_t base = 0;
+  for (int64_t c0 = 0; c0 < total; c0 += kWave) {
+    const int64_t idx = c0 + lane;
+    const int j = (int)(idx / per), n = (int)(idx % a.S);
+    const int64_t pos = (int64_t)slot * a.M + j;
+    const bool take = idx < total && a.amax[pos * a.S + n] != 0.0;
+    const unsigned long long m = __ballot(take);
+    const int64_t at = base + __popcll(m & ((1ull << lane) - 1ull));
+    if (idx < total) a.where[l0 + idx] = take ? (int32_t)at : -1;
+    if (take) {   // at < total <= A
+      a.att.list[l0 + at] = (int32_t)idx;
+      a.att.cand[2 * (l0 + at)] = a.cand ? a.cand[2 * pos] : 0;
+      a.att.cand[2 * (l0 + at) + 1] = a.cand ? a.cand[2 * pos + 1] : 0;
+      a.att.score[l0 + at] = a.score ? a.score[pos] : 0.0;
+    }
+    base += __popcll(m);
+  }
+  if (lane == 0) a.att.count[slot] = (int32_t)base;
+}
+
+__global__ __launch_bounds__(kApWaves* kWave) void k_cohap_clamp(CohApLaunch a) {
+  const int lane = threadIdx.x % kWave;
+  const int64_t A = cohap_stride(a);
+  const int64_t ap = (int64_t)blockIdx.x * kApWaves + threadIdx.x / kWave;
+  if (ap >= (int64_t)a.n_slots * A) return;
+  const int slot = (int)(ap / A);
+  if (ap % A >= a.att.count[slot]) return;
+  const int64_t idx = a.att.list[ap];
+  if (idx < 0 || idx >= A) return;
+  const int n = (int)(idx % a.S), h = (int)(idx / a.S % a.H), j = (int)(idx / ((int64_t)a.H * a.S));
+  const int64_t pos = (int64_t)slot * a.M + j;
+  const double amp = a.amax[pos * a.S + n];
+  const double* L = a.llr + pos * a.pos_stride + n * a.set_stride;
+  double* out = a.llr_a + ap * FT8_LDPC_N;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int i = lane + kWave * k;
+    if (i < FT8_LDPC_N) {
+      double v = L[i];
+      if (i < 77 && bit77(a.hyp[h].mask, i)) v = bit77(a.hyp[h].value, i) ? amp : -amp;
+      out[i] = v;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kApWaves* kWave) void k_cohap_merge(CohApLaunch a) {
+  const int lane = threadIdx.x % kWave;
+  const int64_t pos = (int64_t)blockIdx.x * kApWaves + threadIdx.x / kWave;
+  if (pos >= (int64_t)a.n_slots * a.M) return;
+  const int slot = (int)(pos / a.M), j = (int)(pos % a.M);
+  if (j >= cohap_count(a, slot)) return;
+  ft8_result* rec = cohap_record(a, slot, j);
+  if (!rec || rec->ok) return;
+  const int64_t A = cohap_stride(a), l0 = (int64_t)slot * A;
+  for (int h = 0; h < a.H; ++h) {
+    for (int n = 0; n < a.S; ++n) {
+      const int32_t w = a.where[l0 + ((int64_t)j * a.H + h) * a.S + n];
+      if (w < 0 || w >= a.att.count[slot]) continue;   // not listed: the (position, set) is not tried
+      const ft8_result& got = a.res_a[l0 + w];
+      if (!got.ok) continue;  // 1. the tail says ok
+      // 2. the decoded payload agrees with the hypothesis on every masked bit
+      const bool differ = lane < 10 && ((got.payload[lane] ^ a.hyp[h].value[lane]) & a.hyp[h].mask[lane]) != 0;
+      if (__ballot(differ) != 0) continue;
+      // 3. hard errors of the attempt's decisions against the signs of set n's unclamped LLRs
+      const double* L = a.llr + pos * a.pos_stride + n * a.set_stride;
+      const uint8_t* plain = a.plain + (l0 + w) * FT8_LDPC_N;
+      int hard = 0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int i = lane + kWave * k;
+        const bool err = i < FT8_LDPC_N && (plain[i] != 0) != (L[i] > 0.0);
+        hard += __popcll(__ballot(err));
+      }
+      if (hard > a.max_hard) continue;
+      if (lane == 0) {
+        const int bits = (a.drift && a.drift[pos].rate_hz_per_s != 0.f ? 6 : 2) | (n > 0 ? 8 : 0) | ((h + 1) << 4);
+        retry_accept(rec, got, bits);
+        if (a.hard) a.hard[rec - a.res] = (int16_t)hard;
+      }
+      return;
+    }
+  }
+}
+
+bool cohap_valid(const CohApLaunch& a) {
+  return a.n_slots > 0 && a.M > 0 && a.H > 0 && a.H <= FT8_AP_MAX_HYP && a.S > 0 && a.S <= 3;
+}
+unsigned cohap_blocks(int64_t waves) { return (unsigned)((waves + kApWaves - 1) / kApWaves); }
+
+}  // namespace
+
+hipError_t launch_cohap_amax(const CohApLaunch& a, hipStream_t s) {
+  if (!cohap_valid(a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_cohap_amax, dim3(cohap_blocks((int64_t)a.n_slots * a.M * a.S)), dim3(kApWaves * kWave), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_cohap_list(const CohApLaunch& a, hipStream_t s) {
+  if (!cohap_valid(a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_cohap_list, dim3(a.n_slots), dim3(kWave), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_cohap_clamp(const CohApLaunch& a, hipStream_t s) {
+  if (!cohap_valid(a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_cohap_clamp, dim3(cohap_blocks((int64_t)a.n_slots * a.M * a.H * a.S)), dim3(kApWaves * kWave), 0,
+                     s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_cohap_merge(const CohApLaunch& a, hipStream_t s) {
+  if (!cohap_valid(a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_cohap_merge, dim3(cohap_blocks((int64_t)a.n_slots * a.M)), dim3(kApWaves * kWave), 0, s, a);
+  return hipGetLastError();
+}
+
 }  // namespace ft8

@@ -221,6 +221,11 @@ struct ft8_ctx {
   // its multi-symbol sets (ft8_set_coherent_nsym; off: 1) and the validity byte per list position
   int coh_nsym = 1;
   DevBuf coh_valid;
+  // a-priori retries on the coherent LLRs (ft8_set_coherent_ap; off: 0) and the stage's scratch: lists of
+  // M * H * S attempts per slot; a per (position, set), the place of every attempt, plain per attempt
+  int coh_ap = 0;
+  RetryScratch cohap;
+  DevBuf cohap_amax, cohap_where, cohap_plain;
   // the stream of the last entry point that enqueued work, and an event recorded on it after that
   // work (StreamOrder): a call on another stream first waits for it
   hipStream_t last_stream = nullptr;
@@ -298,12 +303,14 @@ int ensure_work(ft8_ctx* c, int n_counters, hipStream_t s) {
 
 // Claim counter indices: [0] belongs to ft8_bp / ft8_ap_decode (a caller stream, in order); a batch of
 // n_chunks chunks then holds one per chunk for plain BP, for the a-priori pass and for the coherent
-// pass, in that order, so that chunks on different streams never share one.
-enum BpUser { kCallerBp = -1, kChunkBp = 0, kChunkAp = 1, kChunkCoherent = 2 };
+// pass, in that order, and last for the a-priori retries on the coherent LLRs, so that chunks on
+// different streams never share one.
+enum BpUser { kCallerBp = -1, kChunkBp = 0, kChunkAp = 1, kChunkCoherent = 2, kChunkCoherentAp = 3 };
 int bp_counter(BpUser u, int k, int n_chunks) { return u == kCallerBp ? 0 : 1 + (int)u * n_chunks + k; }
 // counters of a batch: through its last user's
-int bp_counters(bool ap, bool coh, int n_chunks) {
-  return bp_counter(coh ? kChunkCoherent : ap ? kChunkAp : kChunkBp, n_chunks - 1, n_chunks) + 1;
+int bp_counters(bool ap, bool coh, bool coh_ap, int n_chunks) {
+  return bp_counter(coh_ap ? kChunkCoherentAp : coh ? kChunkCoherent : ap ? kChunkAp : kChunkBp, n_chunks - 1,
+                    n_chunks) + 1;
 }
 
 hipEvent_t get_event(ft8_ctx* c) {
@@ -1046,6 +1053,54 @@ int coherent_pass(ft8_ctx* c, CohLaunch L, const RetryLists& failed, int slot0, 
   return FT8_OK;
 }
 
+// ---- a-priori retries on the coherent LLRs ------------------------------------------------------
+// whether a batch with these flags runs the stage (ft8_set_coherent_ap)
+bool coherent_ap_on(const ft8_ctx* c, int flags) {
+  return c->coh_ap && (flags & FT8_FLAG_AP) && (flags & FT8_FLAG_COHERENT);
+}
+
+// the stage's scratch for n_slots lists of M positions, H hypotheses and S sets (ft8hip.h states the
+// sizes); FT8_E_RANGE where the attempts do not fit k_bp's 32-bit item count
+int ensure_cohap_scratch(ft8_ctx* c, size_t n_slots, int M, int H, int S) {
+  const uint64_t A = (uint64_t)M * (uint64_t)H * (uint64_t)S;
+  if (A * n_slots > (uint64_t)INT32_MAX)
+    return fail(c, FT8_E_RANGE, "coherent a-priori retries: more than 2^31 - 1 attempts");
+  int rc = c->cohap.ensure(c, n_slots, (int)A);
+  if (!rc) rc = ensure(c, c->cohap_amax, sizeof(double) * n_slots * M * S);
+  if (!rc) rc = ensure(c, c->cohap_where, sizeof(int32_t) * n_slots * A);
+  if (!rc) rc = ensure(c, c->cohap_plain, (size_t)FT8_LDPC_N * n_slots * A);
+  return rc;
+}
+
+// The stage over one chunk (ap.hip): A.res / n_slots / N / M / S and the coherent list, fits, validity
+// bytes, drift records and LLRs are the caller's; the hypotheses, the limit and the scratch, which starts
+// at slot `slot0` of the buffers ensure_cohap_scratch sized, are filled in here.  Five launches.
+int coherent_ap_pass(ft8_ctx* c, CohApLaunch A, int slot0, int max_iterations, int counter, hipStream_t s) {
+  A.H = (int)c->ap_hyps.size();
+  for (int h = 0; h < A.H; ++h) A.hyp[h] = c->ap_hyps[h];
+  A.max_hard = c->ap_max_hard;
+  RetryLists in{};
+  in.n_slots = A.n_slots;
+  in.N = A.M * A.H * A.S;
+  const RetryView v = c->cohap.at(in, slot0);
+  const size_t a0 = (size_t)slot0 * v.lists.M;
+  uint8_t* plain = c->cohap_plain.as<uint8_t>() + (size_t)FT8_LDPC_N * a0;
+  A.amax = c->cohap_amax.as<double>() + (size_t)slot0 * A.M * A.S;
+  A.att = v.lists;
+  A.where = c->cohap_where.as<int32_t>() + a0;
+  A.llr_a = v.llr;
+  A.plain = plain;
+  A.res_a = v.res;
+  hipError_t e = launch_cohap_amax(A, s);
+  if (e == hipSuccess) e = launch_cohap_list(A, s);
+  if (e == hipSuccess) e = launch_cohap_clamp(A, s);
+  if (e != hipSuccess) return hipfail(c, e, "coherent ap launch");
+  if ((e = bp_over_lists(c, A.att, v.llr, plain, v.res, max_iterations, counter, s)) != hipSuccess)
+    return hipfail(c, e, "coherent ap bp launch");
+  if ((e = launch_cohap_merge(A, s)) != hipSuccess) return hipfail(c, e, "coherent ap launch");
+  return FT8_OK;
+}
+
 int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
                 int64_t slot_stride, const ft8_params* p, ft8_result* d_out, int32_t* d_counts, int32_t cap,
                 hipStream_t s) {
@@ -1064,7 +1119,8 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
   const int n_str = (c->n_streams > 0 && n_chunks > 1) ? std::min(c->n_streams, n_chunks) : 0;
   const bool ap = (p->flags & FT8_FLAG_AP) != 0;
   const bool coh = (p->flags & FT8_FLAG_COHERENT) != 0;
-  if ((rc = ensure_work(c, bp_counters(ap, coh, n_chunks), s))) return rc;
+  const bool coh_ap = coherent_ap_on(c, p->flags);
+  if ((rc = ensure_work(c, bp_counters(ap, coh, coh_ap, n_chunks), s))) return rc;
   hipError_t e = hipSuccess;
   if (n_str > 0) {
     while ((int)c->streams.size() < n_str) {
@@ -1134,6 +1190,28 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
       if ((rc = coherent_setup(c, xs, dtype, n_samples, ns, slot_stride, p, c->coh_nsym > 1, &L))) return rc;
       if ((rc = coherent_pass(c, L, failed, c0, p->max_iterations, bp_counter(kChunkCoherent, k, n_chunks), cs)))
         return rc;
+      if (coh_ap) {  // the known bits on the coherent LLRs of what that pass listed and left failed
+        const RetryView v = c->coh.at(failed, c0);
+        CohApLaunch A{};
+        A.res = failed.res;
+        A.n_slots = ns;
+        A.N = N;
+        A.M = v.lists.M;
+        A.S = c->coh_nsym;
+        A.list = v.lists.list;
+        A.count = v.lists.count;
+        A.cand = v.lists.cand;
+        A.score = v.lists.score;
+        A.fit = c->coh_fit.as<ft8_coh_fit>() + (size_t)c0 * A.M;
+        if (coherent_drift_on(CohDrift{c->coh_drift_rate, c->coh_drift_n, nullptr}))
+          A.drift = c->coh_drift.as<ft8_coh_drift>() + (size_t)c0 * A.M;
+        if (A.S > 1) A.valid = c->coh_valid.as<uint8_t>() + (size_t)c0 * A.M;
+        A.llr = v.llr;
+        A.pos_stride = FT8_LDPC_N;
+        A.set_stride = (int64_t)(FT8_LDPC_N * c->coh.n_all);
+        if ((rc = coherent_ap_pass(c, A, c0, p->max_iterations, bp_counter(kChunkCoherentAp, k, n_chunks), cs)))
+          return rc;
+      }
     }
     if (ap && (rc = ap_pass(c, failed, B.llr_in, c0, p->max_iterations, nullptr, bp_counter(kChunkAp, k, n_chunks), cs)))
       return rc;
@@ -1600,6 +1678,44 @@ int ft8_set_coherent_nsym(ft8_ctx* c, int32_t max_nsym) {
   return FT8_OK;
 }
 
+int ft8_set_coherent_ap(ft8_ctx* c, int32_t on) {
+  if (!c) return FT8_E_ARG;
+  if (on != 0 && on != 1) return fail(c, FT8_E_ARG, "coherent ap: on must be 0 or 1");
+  c->coh_ap = on;
+  return FT8_OK;
+}
+
+int ft8_coherent_ap_decode(ft8_ctx* c, const double* d_llr, int32_t n_sets, const uint8_t* d_valid, ft8_result* d_res,
+                           int32_t n, int32_t max_iterations, int16_t* d_hard, void* stream) {
+  StreamOrder order_(c, (hipStream_t)stream);
+  if (c) c->replay_ok = c->snr_ok = false;
+  if (!c || n < 0 || (n > 0 && (!d_llr || !d_res))) return fail(c, FT8_E_ARG, "bad argument");
+  if (n_sets < 1 || n_sets > 3) return fail(c, FT8_E_ARG, "coherent ap: n_sets must be in [1, 3]");
+  if (c->ap_hyps.empty()) return fail(c, FT8_E_ARG, "no hypotheses set (ft8_set_ap)");
+  if (n == 0) return FT8_OK;
+  DeviceGuard dg(c->device);
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = ensure_work(c, 1, s))) return rc;
+  if ((rc = ensure_cohap_scratch(c, 1, n, (int)c->ap_hyps.size(), n_sets))) return rc;
+  if (d_hard) {
+    const hipError_t e = hipMemsetAsync(d_hard, 0xFF, sizeof(int16_t) * (size_t)n, s);  // -1 throughout
+    if (e != hipSuccess) return hipfail(c, e, "memset");
+  }
+  // records without slot structure: one list of n, position j is record j, every fit valid, no drift
+  CohApLaunch A{};
+  A.res = d_res;
+  A.n_slots = 1;
+  A.N = A.M = n;
+  A.S = n_sets;
+  A.valid = d_valid;
+  A.llr = d_llr;
+  A.pos_stride = (int64_t)n_sets * FT8_LDPC_N;
+  A.set_stride = FT8_LDPC_N;
+  A.hard = d_hard;
+  return coherent_ap_pass(c, A, 0, max_iterations, bp_counter(kCallerBp, 0, 0), s);
+}
+
 int ft8_coherent_llr(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
                      int64_t slot_stride, const ft8_params* p, const int32_t* d_cand, const int32_t* d_slot_of,
                      int32_t n, double* d_llr_out, ft8_coh_fit* d_fit_out, void* stream) {
@@ -1703,6 +1819,9 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   if ((rc = ensure_sel_scratch(c, n_slots, gr, N, f64))) return rc;
   if ((p->flags & FT8_FLAG_AP) && (rc = ensure_ap_scratch(c, (size_t)n_slots, N))) return rc;
   if ((p->flags & FT8_FLAG_COHERENT) && (rc = ensure_coh_scratch(c, (size_t)n_slots, coherent_cap(c, N))))
+    return rc;
+  if (coherent_ap_on(c, p->flags) &&
+      (rc = ensure_cohap_scratch(c, (size_t)n_slots, coherent_cap(c, N), (int)c->ap_hyps.size(), c->coh_nsym)))
     return rc;
   if (!(p->flags & FT8_FLAG_SUBTRACT)) {
     if ((rc = decode_pass(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, d_out, d_counts, cap, s))) return rc;

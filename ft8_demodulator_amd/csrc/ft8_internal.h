@@ -394,6 +394,39 @@ struct CohPass {
 };
 hipError_t launch_coh_merge(const CohPass& a, hipStream_t s);
 
+// ---- a-priori retries on the coherent LLRs (ap.hip; ft8hip.h, "coherent_ap") -------------------
+// The stage after the coherent pass's last merge, on the list that pass built: positions [n_slots][M],
+// S LLR sets per position (set n of position pos at llr + pos * pos_stride + n * set_stride, in
+// doubles), H hypotheses.  Attempt (j, h, n) of a slot has the index (j * H + h) * S + n, which is the
+// contract's order within a position; a slot's usable attempts are compacted in that order into lists
+// of stride A = M * H * S, which k_bp decodes in one launch (mode 0, `att` as its candidate lists).
+struct CohApLaunch {
+  ft8_result* res;             // in / out [n_slots][N]: the records as the coherent pass left them
+  int n_slots, N, M, H, S;
+  const int32_t* list;         // [n_slots][M] original indices of the positions; null: position j is record j
+  const int32_t* count;        // [n_slots] positions per slot; null: M
+  const int32_t* cand;         // nullable, compacted [n_slots][M][2] and [n_slots][M]: the positions'
+  const double* score;         // candidates and scores (copied to the attempts; zeros without them)
+  const ft8_coh_fit* fit;      // nullable [n_slots][M]: only positions with status 0 are tried
+  const ft8_coh_drift* drift;  // nullable [n_slots][M]: a rate other than 0 sets bit 2
+  const uint8_t* valid;        // nullable [n_slots][M]: set n is tried only where bit n is set
+  const double* llr;           // the coherent LLRs
+  int64_t pos_stride, set_stride;
+  ft8_ap_hyp hyp[FT8_AP_MAX_HYP];
+  int max_hard;
+  double* amax;                // [n_slots][M][S] a_n = 1.01 max |L_n|, 0 where (position, set) is not tried
+  RetryLists att;              // the attempts: N = M = A; list holds the attempt index; res is unused
+  int32_t* where;              // [n_slots][A] attempt index -> its place in the slot's list, -1: not listed
+  double* llr_a;               // [n_slots][A][174] clamped LLRs of the listed attempts
+  const uint8_t* plain;        // launch_bp's hard decisions of them
+  const ft8_result* res_a;     // launch_bp's records of them
+  int16_t* hard;               // nullable [n_slots * N], by original index: hard errors of an accepted attempt
+};
+hipError_t launch_cohap_amax(const CohApLaunch& a, hipStream_t s);
+hipError_t launch_cohap_list(const CohApLaunch& a, hipStream_t s);
+hipError_t launch_cohap_clamp(const CohApLaunch& a, hipStream_t s);
+hipError_t launch_cohap_merge(const CohApLaunch& a, hipStream_t s);
+
 // ft8_pack_decodes (bp.hip): one workgroup packs a batch's decodes for the all-gather
 inline __host__ __device__ int64_t pack_header_bytes(int n_slots) { return 8 + ((4 * (int64_t)n_slots + 7) & ~7ll); }
 hipError_t launch_pack(const ft8_result* rec, const int32_t* counts, int n_slots, int cap, int capacity,

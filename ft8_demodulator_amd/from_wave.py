@@ -52,14 +52,15 @@ def read_wave_file(wave_path: str, verbose: bool = False) -> tuple:
 
 def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_errors: int = None, coherent=None,
                  coherent_drift=None, coherent_nsym: int = 1, selection: str = "reference", subtract=None,
-                 device=None, verbose: bool = False, **decode_kw) -> tuple:
+                 coherent_ap: bool = False, device=None, verbose: bool = False, **decode_kw) -> tuple:
     """One file, any PCM width, as one slot through _pipeline.decode_one -> (results, snr_db, patterns)
     and, with coherent, a fourth entry.  snr_db (with snr, else None): one SNR in 2500 Hz per result.
     patterns (with ap, else None): per result the a-priori pattern that rescued it, None for a plain
     decode.  fits (with coherent): per result (dt_s, df_hz) of the coherent fit that rescued it (one
     ft8_coherent_llr call for those records), None for any other decode; with coherent_drift
     (True or (max_rate, n_rates)) the fit is (dt_s, df_hz, rate_hz_per_s); a decode from a joint metric over
-    2 or 3 symbols (coherent_nsym > 1) has MULTI_SYMBOL as a further, last entry.
+    2 or 3 symbols (coherent_nsym > 1) has MULTI_SYMBOL as a further, last entry.  With coherent_ap (needs ap
+    and coherent) a result may carry both marks: its pattern and its fit.
     selection: "reference" or "topk".  subtract (True or a pass count in [2, 4]; not with snr): subtract-and-
     redecode with the retries above in every pass, and a last entry passes: per result the 1-based pass that
     appended it.  A decode from a residual has no fit entry (the stage call would fit it on the samples)."""
@@ -87,7 +88,7 @@ def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_erro
     results, reports, recs, *per_pass = decode_one(
         x, code, sample_rate, snr=snr, ap=ap, ap_max_hard_errors=ap_max_hard_errors, coherent=coherent,
         coherent_drift=coherent_drift, coherent_nsym=coherent_nsym, flags=flags, subtract=subtract,
-        pass_counts=subtract is not None, **decode_kw)
+        pass_counts=subtract is not None, coherent_ap=coherent_ap, **decode_kw)
     out = (results, snr_db_or_nan(reports) if snr else None,
            None if ap is None else [ap[ap_index(r) - 1] if ap_index(r) else None for r in recs])
     if coherent is not None:
@@ -274,6 +275,9 @@ def main(argv=None):
     parser.add_argument("--coherent-nsym", type=int, choices=(1, 2, 3), default=None, metavar="N",
                         help="with --coherent: also decode joint LLRs over 2 .. N (at most 3) adjacent symbols for "
                              "each of those candidates (default 1: off; such a decode's mark ends with multi-symbol)")
+    parser.add_argument("--coherent-ap", action="store_true",
+                        help="with --ap and --coherent: also retry those candidates with the --ap patterns on their "
+                             "coherent LLRs (such a decode carries both marks)")
     parser.add_argument("--selection", choices=("reference", "topk"), default="reference",
                         help="candidate selection: the reference's, or the max-candidates highest scores")
     parser.add_argument("--subtract", nargs="?", type=int, const=2, default=None, metavar="PASSES",
@@ -294,6 +298,8 @@ def main(argv=None):
         parser.error("--coherent-drift needs --coherent")
     if args.coherent_nsym is not None and coherent is None:
         parser.error("--coherent-nsym needs --coherent")
+    if args.coherent_ap and (not args.ap or coherent is None):
+        parser.error("--coherent-ap needs --ap and --coherent")
     paths = args.wave_file
     for path in paths:
         if not os.path.exists(path):
@@ -314,6 +320,8 @@ def main(argv=None):
             kw = dict(kw, coherent_drift=args.coherent_drift)
         if args.coherent_nsym is not None:
             kw = dict(kw, coherent_nsym=args.coherent_nsym)
+        if args.coherent_ap:
+            kw = dict(kw, coherent_ap=True)
         if args.selection != "reference":
             kw = dict(kw, selection=args.selection)
         if args.subtract is not None:

@@ -144,7 +144,8 @@ def decode_ft8_message(wave_data, sample_rate: int, bins_per_tone: int = 2, step
                        max_candidates: int = 20, min_score=10, max_iterations: int = 20,
                        freq_min: float = None, freq_max: float = None, time_min: float = None,
                        time_max: float = None, *, plot: bool = False, verbose: bool = False, device=None,
-                       selection: str = "reference", subtract=False):
+                       selection: str = "reference", subtract=False, ap=None, coherent=None,
+                       coherent_ap: bool = False):
     """ft8_decode.py:288-394 -> [(FT8Message, FT8DecodeStatus, time_sec, freq_hz, score)].
 
     time_sec = abs_time / sample_rate and freq_hz = abs_freq / bins_per_tone * 6.25 relative to the
@@ -153,13 +154,16 @@ def decode_ft8_message(wave_data, sample_rate: int, bins_per_tone: int = 2, step
     Build-defined options (outside reference parity, defaults reproduce the reference):
     selection="topk" keeps the max_candidates highest scores; subtract=True subtracts the decoded
     signals and decodes the residual once more, appending new messages (float32 input only); a pass
-    count in [2, 4] instead of True runs that many passes, each subtracting what the last one added."""
+    count in [2, 4] instead of True runs that many passes, each subtracting what the last one added.
+    ap (a-priori patterns), coherent (True or a count) and coherent_ap (the patterns on the coherent LLRs as
+    well; needs both) are SlotDecoder's retries of the candidates BP fails on."""
     x, code, _ = device_samples(wave_data, device)
     if x.dim() != 1:
         raise ValueError("wave_data must be one-dimensional")
     results = decode_one(x, code, sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score,
                          max_iterations, freq_min, freq_max, time_min, time_max,
-                         flags=selection_flags(selection), subtract=subtract or None)[0]
+                         flags=selection_flags(selection), subtract=subtract or None, ap=ap, coherent=coherent,
+                         coherent_ap=coherent_ap)[0]
     if plot:
         plan = make_plan(int(x.shape[0]), sample_rate, bins_per_tone, steps_per_symbol, freq_min, freq_max,
                          time_min, time_max)

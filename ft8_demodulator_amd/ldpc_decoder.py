@@ -38,6 +38,15 @@ def ap_decode_batch(llrs: np.ndarray, records: np.ndarray, max_iterations: int):
     return _device.ap_decode(llrs, records, max_iterations)
 
 
+def coherent_ap_decode_batch(llrs: np.ndarray, records: np.ndarray, max_iterations: int, valid=None):
+    """A-priori retry on coherent LLRs (ft8_coherent_ap_decode) of the failed records among `records`, with
+    the hypotheses of the thread's context (_lib.context().set_ap): llrs [n, 174] or [n, S, 174] as
+    coherent_llr_batch gives them, valid its validity bytes (None: every set usable) -> (updated records,
+    hard int16 [n]: the hard errors of an accepted attempt, -1 otherwise).  The contract is in
+    include/ft8hip.h; coherent.coherent_ap_restate is its NumPy restatement."""
+    return _device.coherent_ap_decode(llrs, records, max_iterations, valid)
+
+
 def coherent_llr_batch(samples, cand, slot_of, sample_rate=12000, bins_per_tone=2, steps_per_symbol=2, t_lo=0,
                        f_lo=0, code=None, drift=None, nsym=1):
     """Coherent re-demodulation (ft8_coherent_llr) of the candidates cand [n, 2] = (abs_time, abs_freq) of

@@ -525,6 +525,49 @@ int ft8_coherent_nsym_llr(ft8_ctx* ctx, const void* d_samples, int dtype, int64_
  * and, for max_nsym > 1, 1 validity byte.  FT8_E_ARG for max_nsym outside [1, 3]. */
 int ft8_set_coherent_nsym(ft8_ctx* ctx, int32_t max_nsym);
 
+/* ---- a-priori retries on the coherent LLRs (coherent_ap) ------------------------------------------------
+ * Opt-in and build-defined like both passes; coherent.py: coherent_ap_restate restates it.  The coherent
+ * pass demodulates a failed candidate again but decodes it without known bits; the a-priori pass has the
+ * known bits but only on the STFT LLRs.  With this setting on, a batch that carries both FT8_FLAG_COHERENT
+ * and FT8_FLAG_AP runs a third stage per chunk, after the coherent pass's last merge and before the
+ * a-priori pass, on the list the coherent pass built: the same M positions per slot, fits, S = max_nsym LLR
+ * sets, validity bytes and drift records.  For each list position:
+ *   eligible   only while the original record has ok == 0 and the position's fit has status 0.
+ *   sets       n = 0 .. S - 1; with validity bytes (S > 1) only where bit n is set.  L_n is the set's 174
+ *              coherent LLRs and a_n = 1.01 * max_i |L_n[i]| (one multiply in double); a_n NaN or 0: set n is
+ *              skipped for every hypothesis.
+ *   attempts   hypothesis h = 0 .. H - 1 outer, usable set n ascending inner: L_{h,n} is the clamp of the
+ *              a-priori contract on L_n (+-a_n on the masked bits below 77, L_n[i] elsewhere), then
+ *              bp_decode(L_{h,n}, max_iterations) and the reference tail, exactly as ft8_bp runs them.
+ *   accepted   as in the a-priori contract: (1) the tail says ok, (2) the payload agrees with value on every
+ *              masked bit, (3) #{ i < 174 : plain[i] != (L_n[i] > 0) } <= max_hard_errors, counted against
+ *              the UNCLAMPED L_n.
+ * The first accepted attempt in that order wins: the lowest hypothesis, and within it the first usable set.
+ * Its record gets ok = 1, the attempt's payload, crc_extracted, crc_calculated and ldpc_errors, and
+ * pass_index |= 2 | (h + 1) << 4, |= 4 more where the position's drift rate is not 0, |= 8 more where n > 0;
+ * score, slot, abs_time, abs_freq and cand_index do not change.  A position nothing rescues keeps its record,
+ * and the a-priori pass then runs unchanged on the STFT LLRs of what is still failed.  Attempts do not depend
+ * on one another, so the device makes all of them and picks the first accepted afterwards: five launches per
+ * chunk (a_n; the attempt lists; the clamp; one k_bp launch over every attempt, counted by ft8_get_counters
+ * with the others; the merge), whatever H and S are.  Under ft8_set_subtract(ctx, n, 1) the stage runs in
+ * every pass.  Scratch (context-owned, grow-only) for n_slots * M * H * S attempts: per attempt 174 * 8 bytes
+ * of clamped LLRs, 174 bytes of hard decisions and 64 bytes of lists and records, and 8 S bytes per list
+ * position; more than 2^31 - 1 attempts: FT8_E_RANGE.
+ *
+ * The setting: on = 0 or 1 (default 0); any other value: FT8_E_ARG, the setting unchanged.  It takes effect
+ * only in a batch with both flags; in any other batch it is ignored and is no error, and every other check
+ * and refusal of ft8_decode_batch stays as it is. */
+int ft8_set_coherent_ap(ft8_ctx* ctx, int32_t on);
+/* The stage call: d_llr[n][n_sets][174] as ft8_coherent_nsym_llr writes it (n_sets 1 .. 3), d_valid[n]
+ * (nullable: every set usable) its validity bytes, d_res[n] records as ft8_bp left them, treated as one
+ * list with every fit valid and no drift.  Records with ok == 0 are tried per the contract above with the
+ * context's hypotheses and max_hard_errors and updated in place (pass_index |= 2 | (h + 1) << 4, and 8 where
+ * the winning set is not the first).  d_hard[n] (nullable): the accepted attempt's hard-error count, -1
+ * elsewhere.  n = 0 does nothing; no hypotheses set, or n_sets outside [1, 3]: FT8_E_ARG.  Uses the
+ * context's scratch, so it takes part in the cross-stream order. */
+int ft8_coherent_ap_decode(ft8_ctx* ctx, const double* d_llr, int32_t n_sets, const uint8_t* d_valid,
+                           ft8_result* d_res, int32_t n, int32_t max_iterations, int16_t* d_hard, void* stream);
+
 /* Per-slot flags of the last selection (copied device->device into d_out[n_slots]):
  * bit 0: an exact score tie reached a heap comparison (the reference raises TypeError there,
  *        ftx_types.py:37-47; here ties are ordered by scan index), bit 1: unused (0), bit 2
