@@ -162,6 +162,26 @@ def ap_decode(llrs, records, max_iterations):
     return res.cpu().numpy()[: n * _lib.RESULT_DTYPE.itemsize].view(_lib.RESULT_DTYPE).copy(), hard.cpu().numpy()[:n]
 
 
+def osd_decode(llrs, records):
+    """ft8_osd_decode: LLRs [n, 174] and the records ft8_bp wrote from them -> (records updated by
+    ordered-statistics decoding with the context's setting (Context.set_osd), info _lib.OSD_DTYPE [n],
+    codewords uint8 [n, 22])."""
+    torch = _lib.require_gpu()
+    ctx = _lib.context()
+    a = _llr_rows(llrs)
+    n = a.shape[0]
+    rec = np.ascontiguousarray(np.asarray(records, dtype=_lib.RESULT_DTYPE).reshape(-1))
+    if len(rec) != n:
+        raise ValueError(f"{n} LLR vectors but {len(rec)} records")
+    res = torch.from_numpy(np.concatenate([rec.view(np.uint8), np.zeros(8, np.uint8)])).to(a.device)
+    info = torch.zeros(max(n, 1) * _lib.OSD_DTYPE.itemsize, dtype=torch.uint8, device=a.device)
+    cw = torch.zeros(max(n, 1), 22, dtype=torch.uint8, device=a.device)
+    ctx.check(_lib.lib().ft8_osd_decode(ctx.handle, _lib.ptr(a), _lib.ptr(res), n, _lib.ptr(info), _lib.ptr(cw),
+                                        _lib.stream_handle()), "ft8_osd_decode")
+    return (res.cpu().numpy()[: n * _lib.RESULT_DTYPE.itemsize].view(_lib.RESULT_DTYPE).copy(),
+            info.cpu().numpy()[: n * _lib.OSD_DTYPE.itemsize].view(_lib.OSD_DTYPE).copy(), cw.cpu().numpy()[:n])
+
+
 def coherent_ap_decode(llrs, records, max_iterations, valid=None):
     """ft8_coherent_ap_decode: coherent LLRs [n, 174] or [n, S, 174], the records ft8_bp left and the validity
     bytes uint8 [n] (None: every set usable) -> (records updated by the context's a-priori hypotheses

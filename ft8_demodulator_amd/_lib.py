@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("FT8HIP_LIB", os.path.join(_HERE, "lib", "libft8hip.so
 
 FT8_F32, FT8_F64, FT8_C64, FT8_C128, FT8_I16 = 0, 1, 2, 3, 4
 FT8_OK, FT8_E_ARG, FT8_E_HIP, FT8_E_UNSUPPORTED, FT8_E_NOMEM, FT8_E_RANGE = 0, -1, -2, -3, -4, -5
-FT8_FLAG_TOPK, FT8_FLAG_SUBTRACT, FT8_FLAG_AP, FT8_FLAG_COHERENT = 1, 2, 4, 8
+FT8_FLAG_TOPK, FT8_FLAG_SUBTRACT, FT8_FLAG_AP, FT8_FLAG_COHERENT, FT8_FLAG_OSD = 1, 2, 4, 8, 16
 FT8_AP_MAX_HYP = 8
 FT8_SUBTRACT_MAX_PASSES = 4
 FT8_TX_PROTOCOL, FT8_TX_REFERENCE = 0, 1
@@ -98,6 +98,14 @@ SNR_DTYPE = np.dtype({
     "formats": ["<f8", "<f4", "<f4", "i1", "i1", "u1", "u1", ("u1", (4,))],
     "offsets": [0, 8, 12, 16, 17, 18, 19, 20],
     "itemsize": 24,
+})
+
+# ft8_osd_rec (12 bytes)
+OSD_DTYPE = np.dtype({
+    "names": ["weight", "n_hard", "flip", "n_flips", "status"],
+    "formats": ["<i4", "<i2", ("<i2", (2,)), "u1", "u1"],
+    "offsets": [0, 4, 6, 10, 11],
+    "itemsize": 12,
 })
 
 _lib = None
@@ -183,6 +191,8 @@ def lib():
             "ft8_set_coherent_ap": ([vp, i32], ctypes.c_int),
             "ft8_coherent_ap_decode": ([vp, vp, i32, vp, vp, i32, i32, vp, vp], ctypes.c_int),
             "ft8_subtract_counts": ([vp, vp, i32, i32, vp], ctypes.c_int),
+            "ft8_set_osd": ([vp, i32, i32, i32], ctypes.c_int),
+            "ft8_osd_decode": ([vp, vp, vp, i32, vp, vp, vp], ctypes.c_int),
         }
         stale_ok = os.environ.get("FT8HIP_ALLOW_STALE") == "1"
         for name, (args, res) in sig.items():
@@ -204,7 +214,7 @@ def lib():
 
 # csrc files hashed into FT8_BUILD_ID, in the Makefile's ID_FILES order
 _ID_FILES = ("capi.hip", "stft.hip", "stft3840.hip", "sync.hip", "bp.hip", "tx.hip", "subtract.hip", "drift.hip",
-             "msg.hip", "snr.hip", "ap.hip", "coherent.hip", "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "baseband.h", "heap_replay.h", "msg77.h",
+             "msg.hip", "snr.hip", "ap.hip", "coherent.hip", "osd.hip", "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "baseband.h", "heap_replay.h", "msg77.h",
              "div_shared.h",
              "../../include/ft8hip.h",
              "Makefile")
@@ -236,7 +246,8 @@ EXPORTED_SYMBOLS = (
     "ft8_unpack77", "ft8_unpack77_host", "ft8_hash_call", "ft8_noise_floor", "ft8_snr", "ft8_snr_last",
     "ft8_set_ap", "ft8_ap_decode", "ft8_set_coherent", "ft8_coherent_llr",
     "ft8_set_coherent_drift", "ft8_coherent_drift_llr", "ft8_set_coherent_nsym", "ft8_coherent_nsym_llr",
-    "ft8_set_subtract", "ft8_subtract_counts", "ft8_set_coherent_ap", "ft8_coherent_ap_decode")
+    "ft8_set_subtract", "ft8_subtract_counts", "ft8_set_coherent_ap", "ft8_coherent_ap_decode",
+    "ft8_set_osd", "ft8_osd_decode")
 
 
 def limits():
@@ -346,6 +357,12 @@ class Context:
         """ft8_set_coherent_ap: a batch with both FT8_FLAG_COHERENT and FT8_FLAG_AP also retries the candidates
         the coherent pass listed and left failed with the a-priori hypotheses clamped on the coherent LLRs."""
         self.check(lib().ft8_set_coherent_ap(self.handle, int(bool(on))), "ft8_set_coherent_ap")
+
+    def set_osd(self, order: int = 2, max_per_slot: int = 0, max_hard_errors: int = 36):
+        """ft8_set_osd: the order (0 .. 2) of the ordered-statistics decoding of an FT8_FLAG_OSD batch or an
+        ft8_osd_decode call, how many failed candidates per slot a batch tries (0: every one), and the
+        hard-error limit of an accepted decode (174: none)."""
+        self.check(lib().ft8_set_osd(self.handle, int(order), int(max_per_slot), int(max_hard_errors)), "ft8_set_osd")
 
     def set_subtract(self, n_passes: int = 2, retry: bool = False):
         """ft8_set_subtract: the passes (2..4) of an FT8_FLAG_SUBTRACT batch and whether every pass runs the

@@ -228,7 +228,7 @@ class SlotDecoder:
                  min_score=10, max_iterations=20, freq_min=None, freq_max=None, time_min=None,
                  time_max=None, device=None, flags=0, max_results_per_slot=None, context=None, ap=None,
                  ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1, subtract=None,
-                 coherent_ap=False):
+                 coherent_ap=False, osd=None, osd_max_hard_errors=None):
         """subtract: True or a pass count in [2, 4] (True: 2) -- sets FT8_FLAG_SUBTRACT: what each pass decodes is
         subtracted and the residual decoded again, that many passes in all, every pass with the ap / coherent
         retries asked for below (ft8_set_subtract(n, 1)); the default capacity holds n * max_candidates rows.
@@ -248,10 +248,21 @@ class SlotDecoder:
         for every listed candidate (ft8_set_coherent_nsym); more than 1 needs coherent.  1: off.
         coherent_ap: True -- the candidates the coherent pass listed and left failed are also retried with the
         ap patterns clamped on their coherent LLRs, before the a-priori pass sees the STFT LLRs
-        (ft8_set_coherent_ap); needs both ap and coherent.  False: off."""
+        (ft8_set_coherent_ap); needs both ap and coherent.  False: off.
+        osd: True, an order in [0, 2] or (order, max_per_slot) -- sets FT8_FLAG_OSD: per slot the first
+        max_per_slot candidates (True: order 2 of 32; 0: every one) that every retry above left failed are
+        decoded by ordered-statistics decoding of their STFT LLRs (osd.py; ft8_set_osd); None / False: off.
+        osd_max_hard_errors: the most hard decisions of an accepted OSD decode that may contradict the received
+        LLRs' signs (default osd.DEFAULT_MAX_HARD_ERRORS = 36; 174: no limit)."""
         from . import ap as _ap
         from . import coherent as _coh
+        from . import osd as _osd
         from . import subtract as _sub
+        self.osd = _osd.parse_option(osd)   # ValueError for what the library refuses
+        self.osd_max_hard_errors = _osd.check_max_hard_errors(
+            _osd.DEFAULT_MAX_HARD_ERRORS if osd_max_hard_errors is None else osd_max_hard_errors)
+        if self.osd is not None:
+            flags |= _lib.FT8_FLAG_OSD
         self.subtract = _sub.passes_of(subtract)   # ValueError for what the library refuses
         if self.subtract is not None:
             flags |= _lib.FT8_FLAG_SUBTRACT
@@ -353,6 +364,8 @@ class SlotDecoder:
             self.ctx.set_coherent_drift(*(self.coherent_drift or (0.0, 1)))
             self.ctx.set_coherent_nsym(self.coherent_nsym)
             self.ctx.set_coherent_ap(self.coherent_ap)
+        if self.osd is not None:
+            self.ctx.set_osd(self.osd[0], self.osd[1], self.osd_max_hard_errors)
         if self.flags & _lib.FT8_FLAG_SUBTRACT:
             # every batch states its own setting, so a shared context never carries the opt-in over to a
             # decoder built with the flag alone (whose two passes refuse the retries)
@@ -493,7 +506,7 @@ def decode_slots(samples, sample_rate=12000, **kwargs):
 def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_candidates=20, min_score=10,
                max_iterations=20, freq_min=None, freq_max=None, time_min=None, time_max=None, *, flags=0, snr=False,
                ap=None, ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1, subtract=None,
-               pass_counts=False, coherent_ap=False):
+               pass_counts=False, coherent_ap=False, osd=None, osd_max_hard_errors=None):
     """One slot, x [N] on the GPU with its ft8 dtype code, through a SlotDecoder of its own:
     -> (decode_ft8_message's 5-tuples, with snr the ft8_snr_rec records aligned with them else None,
     the ft8_result records) and, with pass_counts (a subtract decode), the slot's row of
@@ -507,7 +520,8 @@ def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_ca
         dec = SlotDecoder(sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score, max_iterations,
                           freq_min, freq_max, time_min, time_max, device=x.device, flags=flags, ap=ap,
                           ap_max_hard_errors=ap_max_hard_errors, coherent=coherent, coherent_drift=coherent_drift,
-                          coherent_nsym=coherent_nsym, subtract=subtract, coherent_ap=coherent_ap)
+                          coherent_nsym=coherent_nsym, subtract=subtract, coherent_ap=coherent_ap, osd=osd,
+                          osd_max_hard_errors=osd_max_hard_errors)
         recs, _, reps = (v if v is None else v[0] for v in dec._fetch(x.unsqueeze(0), code, snr=snr))
         if pass_counts:
             per_pass = dec.pass_counts()[0]

@@ -105,8 +105,10 @@ def ap_accept(ok, payload, plain, llr, mask, value, max_hard_errors):
 
 
 def ap_index(record) -> int:
-    """Which attempt produced a record: 0 plain BP, h + 1 hypothesis h."""
-    return int(record["pass_index"]) >> 4
+    """Which attempt produced a record: 0 plain BP, h + 1 hypothesis h (0 as well for high nibble 15, the
+    ordered-statistics pass's mark: osd.osd_index)."""
+    h = int(record["pass_index"]) >> 4
+    return 0 if h == 15 else h
 
 
 def ap_restate(llrs, records, hyps, max_iterations, max_hard_errors, bp_decode, decode_tail):

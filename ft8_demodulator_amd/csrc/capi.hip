@@ -226,6 +226,10 @@ struct ft8_ctx {
   int coh_ap = 0;
   RetryScratch cohap;
   DevBuf cohap_amax, cohap_where, cohap_plain;
+  // ordered-statistics decoding (ft8_set_osd): the order, the per-slot cap (0: every failed candidate), the
+  // hard-error limit, and the pass's lists of the cap, sized for one ft8_decode_batch
+  int osd_order = 2, osd_max = 0, osd_max_hard = 36;
+  DevBuf osd_list, osd_count, osd_cand, osd_score;
   // the stream of the last entry point that enqueued work, and an event recorded on it after that
   // work (StreamOrder): a call on another stream first waits for it
   hipStream_t last_stream = nullptr;
@@ -801,7 +805,7 @@ SelScratch sel_scratch_at(const ft8_ctx* c, int slot0, const Grid& g, int N, boo
 int check_search_params(ft8_ctx* c, const ft8_params* p, bool limit_first) {
   if (p->steps_per_symbol <= 0 || p->bins_per_tone <= 0) return fail(c, FT8_E_ARG, "bad oversampling factors");
   const bool over = p->max_candidates > kMaxCandidates;
-  if ((p->flags & ~(FT8_FLAG_TOPK | FT8_FLAG_SUBTRACT | FT8_FLAG_AP | FT8_FLAG_COHERENT)) && !(limit_first && over))
+  if ((p->flags & ~(FT8_FLAG_TOPK | FT8_FLAG_SUBTRACT | FT8_FLAG_AP | FT8_FLAG_COHERENT | FT8_FLAG_OSD)) && !(limit_first && over))
     return fail(c, FT8_E_ARG, "unknown bits in ft8_params.flags");
   if (over) return fail(c, FT8_E_RANGE, "max_candidates > " + std::to_string(kMaxCandidates) + " is not supported");
   return FT8_OK;
@@ -1101,6 +1105,48 @@ int coherent_ap_pass(ft8_ctx* c, CohApLaunch A, int slot0, int max_iterations, i
   return FT8_OK;
 }
 
+// ---- ordered-statistics decoding ----------------------------------------------------------------
+// listed candidates per slot of an FT8_FLAG_OSD batch
+int osd_cap(const ft8_ctx* c, int N) { return c->osd_max > 0 ? std::min(c->osd_max, N) : N; }
+
+// the OSD pass's scratch for n_slots lists of M candidates (ft8hip.h states the sizes)
+int ensure_osd_scratch(ft8_ctx* c, size_t n_slots, int M) {
+  const size_t n = n_slots * (size_t)M;
+  int rc = ensure(c, c->osd_list, sizeof(int32_t) * n);
+  if (!rc) rc = ensure(c, c->osd_count, sizeof(int32_t) * n_slots);
+  if (!rc) rc = ensure(c, c->osd_cand, sizeof(int32_t) * 2 * n);
+  if (!rc) rc = ensure(c, c->osd_score, sizeof(double) * n);
+  return rc;
+}
+
+// The OSD pass over the records `failed` describes, one chunk's (osd.hip): the list of the first M records
+// still failed, then k_osd on llr[n_slots][N][174].  Like ap_pass, its scratch starts at slot `slot0` of the
+// buffers ensure_osd_scratch sized.
+int osd_pass(ft8_ctx* c, RetryLists failed, const double* llr, int slot0, hipStream_t s) {
+  const int M = osd_cap(c, failed.N);
+  const size_t r0 = (size_t)slot0 * M;
+  failed.M = M;
+  failed.gate = nullptr;
+  failed.list = c->osd_list.as<int32_t>() + r0;
+  failed.count = c->osd_count.as<int32_t>() + slot0;
+  failed.cand = c->osd_cand.as<int32_t>() + 2 * r0;
+  failed.score = c->osd_score.as<double>() + r0;
+  hipError_t e = launch_retry_list(failed, s);
+  if (e != hipSuccess) return hipfail(c, e, "osd launch");
+  OsdLaunch A{};
+  A.res = failed.res;
+  A.llr = llr;
+  A.n_slots = failed.n_slots;
+  A.N = failed.N;
+  A.M = M;
+  A.list = failed.list;
+  A.count = failed.count;
+  A.order = c->osd_order;
+  A.max_hard = c->osd_max_hard;
+  if ((e = launch_osd(A, s)) != hipSuccess) return hipfail(c, e, "osd launch");
+  return FT8_OK;
+}
+
 int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
                 int64_t slot_stride, const ft8_params* p, ft8_result* d_out, int32_t* d_counts, int32_t cap,
                 hipStream_t s) {
@@ -1120,6 +1166,7 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
   const bool ap = (p->flags & FT8_FLAG_AP) != 0;
   const bool coh = (p->flags & FT8_FLAG_COHERENT) != 0;
   const bool coh_ap = coherent_ap_on(c, p->flags);
+  const bool osd = (p->flags & FT8_FLAG_OSD) != 0;
   if ((rc = ensure_work(c, bp_counters(ap, coh, coh_ap, n_chunks), s))) return rc;
   hipError_t e = hipSuccess;
   if (n_str > 0) {
@@ -1215,6 +1262,8 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     }
     if (ap && (rc = ap_pass(c, failed, B.llr_in, c0, p->max_iterations, nullptr, bp_counter(kChunkAp, k, n_chunks), cs)))
       return rc;
+    // last: what every other retry left failed, on the STFT LLRs
+    if (osd && (rc = osd_pass(c, failed, B.llr_in, c0, cs))) return rc;
     CompactLaunch C{};
     C.res = B.res;
     C.cand_count = cand_count;
@@ -1233,7 +1282,7 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     if ((e = hipEventRecord(c->joins[i], c->streams[i])) != hipSuccess) return hipfail(c, e, "join");
     if ((e = hipStreamWaitEvent(s, c->joins[i], 0)) != hipSuccess) return hipfail(c, e, "join wait");
   }
-  c->replay_ok = n_chunks == 1 && !ap && !coh;  // a replayed k_bp would overwrite the rescued records
+  c->replay_ok = n_chunks == 1 && !ap && !coh && !osd;  // a replayed k_bp would overwrite the rescued records
   return FT8_OK;
 }
 
@@ -1655,6 +1704,38 @@ int ft8_ap_decode(ft8_ctx* c, const double* d_llr, ft8_result* d_res, int32_t n,
   return ap_pass(c, failed, d_llr, 0, max_iterations, d_hard, bp_counter(kCallerBp, 0, 0), s);
 }
 
+int ft8_set_osd(ft8_ctx* c, int32_t order, int32_t max_per_slot, int32_t max_hard_errors) {
+  if (!c) return FT8_E_ARG;
+  if (order < 0 || order > 2) return fail(c, FT8_E_ARG, "osd: order must be in [0, 2]");
+  if (max_per_slot < 0) return fail(c, FT8_E_ARG, "osd: max_per_slot must be >= 0");
+  if (max_hard_errors < 0 || max_hard_errors > FT8_LDPC_N) return fail(c, FT8_E_ARG, "osd: max_hard_errors outside [0, 174]");
+  c->osd_order = order;
+  c->osd_max = max_per_slot;
+  c->osd_max_hard = max_hard_errors;
+  return FT8_OK;
+}
+
+int ft8_osd_decode(ft8_ctx* c, const double* d_llr, ft8_result* d_res, int32_t n, ft8_osd_rec* d_info,
+                   uint8_t* d_codeword, void* stream) {
+  StreamOrder order_(c, (hipStream_t)stream);
+  if (c) c->replay_ok = c->snr_ok = false;
+  if (!c || n < 0 || (n > 0 && (!d_llr || !d_res))) return fail(c, FT8_E_ARG, "bad argument");
+  if (n == 0) return FT8_OK;
+  DeviceGuard dg(c->device);
+  // records without slot structure: one list of every record
+  OsdLaunch A{};
+  A.res = d_res;
+  A.llr = d_llr;
+  A.n_slots = 1;
+  A.N = A.M = n;
+  A.order = c->osd_order;
+  A.max_hard = c->osd_max_hard;
+  A.info = d_info;
+  A.codeword = d_codeword;
+  const hipError_t e = launch_osd(A, (hipStream_t)stream);
+  return e == hipSuccess ? FT8_OK : hipfail(c, e, "osd launch");
+}
+
 int ft8_set_coherent(ft8_ctx* c, int32_t max_per_slot) {
   if (!c || max_per_slot < 0) return fail(c, FT8_E_ARG, "bad argument");
   c->coh_max = max_per_slot;
@@ -1797,6 +1878,8 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
     if ((rc = coherent_setup(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, c->coh_nsym > 1, &probe)))
       return rc;
   }
+  if ((p->flags & FT8_FLAG_OSD) && (p->flags & FT8_FLAG_SUBTRACT) && !c->sub_retry)  // also where there is nothing to search
+    return fail(c, FT8_E_UNSUPPORTED, "FT8_FLAG_OSD with FT8_FLAG_SUBTRACT is not supported");
   const int T = p->t_hi - p->t_lo, F = p->f_hi - p->f_lo;
   const bool f64 = is_f64_dtype(dtype);
   const int N = p->max_candidates;
@@ -1823,6 +1906,7 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   if (coherent_ap_on(c, p->flags) &&
       (rc = ensure_cohap_scratch(c, (size_t)n_slots, coherent_cap(c, N), (int)c->ap_hyps.size(), c->coh_nsym)))
     return rc;
+  if ((p->flags & FT8_FLAG_OSD) && (rc = ensure_osd_scratch(c, (size_t)n_slots, osd_cap(c, N)))) return rc;
   if (!(p->flags & FT8_FLAG_SUBTRACT)) {
     if ((rc = decode_pass(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, d_out, d_counts, cap, s))) return rc;
     remember_snr_batch(c, p, g, n_slots, T, F, cap, f64);

@@ -427,6 +427,22 @@ hipError_t launch_cohap_list(const CohApLaunch& a, hipStream_t s);
 hipError_t launch_cohap_clamp(const CohApLaunch& a, hipStream_t s);
 hipError_t launch_cohap_merge(const CohApLaunch& a, hipStream_t s);
 
+// ---- ordered-statistics decoding (osd.hip; ft8hip.h, "ordered-statistics decoding") ------------
+// k_osd, one workgroup per list position: positions [n_slots][M] over records [n_slots][N].  The stage
+// call has one list of every record (list and count null: position j is record j, and a record that is
+// ok already gets status 3); the pass inside ft8_decode_batch gives launch_retry_list's lists.
+struct OsdLaunch {
+  ft8_result* res;             // in / out [n_slots][N]
+  const double* llr;           // [n_slots][N][174] the LLRs plain BP consumed
+  int n_slots, N, M;
+  const int32_t* list;         // [n_slots][M] original indices of the positions; null: position j is record j
+  const int32_t* count;        // [n_slots] positions per slot; null: M
+  int order, max_hard;
+  ft8_osd_rec* info;           // nullable [n_slots * N], by original index
+  uint8_t* codeword;           // nullable [n_slots * N][22], by original index
+};
+hipError_t launch_osd(const OsdLaunch& a, hipStream_t s);
+
 // ft8_pack_decodes (bp.hip): one workgroup packs a batch's decodes for the all-gather
 inline __host__ __device__ int64_t pack_header_bytes(int n_slots) { return 8 + ((4 * (int64_t)n_slots + 7) & ~7ll); }
 hipError_t launch_pack(const ft8_result* rec, const int32_t* counts, int n_slots, int cap, int capacity,

@@ -52,7 +52,8 @@ def read_wave_file(wave_path: str, verbose: bool = False) -> tuple:
 
 def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_errors: int = None, coherent=None,
                  coherent_drift=None, coherent_nsym: int = 1, selection: str = "reference", subtract=None,
-                 coherent_ap: bool = False, device=None, verbose: bool = False, **decode_kw) -> tuple:
+                 coherent_ap: bool = False, osd=None, osd_max_hard_errors: int = None, device=None,
+                 verbose: bool = False, **decode_kw) -> tuple:
     """One file, any PCM width, as one slot through _pipeline.decode_one -> (results, snr_db, patterns)
     and, with coherent, a fourth entry.  snr_db (with snr, else None): one SNR in 2500 Hz per result.
     patterns (with ap, else None): per result the a-priori pattern that rescued it, None for a plain
@@ -63,12 +64,16 @@ def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_erro
     and coherent) a result may carry both marks: its pattern and its fit.
     selection: "reference" or "topk".  subtract (True or a pass count in [2, 4]; not with snr): subtract-and-
     redecode with the retries above in every pass, and a last entry passes: per result the 1-based pass that
-    appended it.  A decode from a residual has no fit entry (the stage call would fit it on the samples)."""
+    appended it.  A decode from a residual has no fit entry (the stage call would fit it on the samples).
+    osd (True, an order or (order, max_per_slot)): ordered-statistics decoding of what every other retry left
+    failed, and a last entry orders: per result the configured order where that pass produced it, else None
+    (such a result has no pattern)."""
     import torch
     from . import _lib
     from ._pipeline import decode_one
     from .ap import ap_index
     from .ft8_decode import selection_flags
+    from .osd import osd_index, parse_option
     from .snr import snr_db_or_nan
     from .subtract import pass_of, passes_of, subtract_index
     flags = selection_flags(selection)
@@ -88,7 +93,8 @@ def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_erro
     results, reports, recs, *per_pass = decode_one(
         x, code, sample_rate, snr=snr, ap=ap, ap_max_hard_errors=ap_max_hard_errors, coherent=coherent,
         coherent_drift=coherent_drift, coherent_nsym=coherent_nsym, flags=flags, subtract=subtract,
-        pass_counts=subtract is not None, coherent_ap=coherent_ap, **decode_kw)
+        pass_counts=subtract is not None, coherent_ap=coherent_ap, osd=osd, osd_max_hard_errors=osd_max_hard_errors,
+        **decode_kw)
     out = (results, snr_db_or_nan(reports) if snr else None,
            None if ap is None else [ap[ap_index(r) - 1] if ap_index(r) else None for r in recs])
     if coherent is not None:
@@ -96,6 +102,9 @@ def _decode_file(wave_path: str, *, snr: bool = False, ap=None, ap_max_hard_erro
         out += ([None if subtract_index(r) else f for r, f in zip(recs, fits)],)
     if subtract is not None:
         out += ([pass_of(per_pass[0], i) for i in range(len(recs))],)
+    if osd is not None and osd is not False:
+        order = parse_option(osd)[0]
+        out += ([order if osd_index(r) else None for r in recs],)
     return out
 
 
@@ -177,14 +186,15 @@ def decode_ft8_from_wave_ap(wave_path: str, ap, ap_max_hard_errors: int = None, 
     return results, patterns, snr_db
 
 
-def _print_results(results, text: bool = False, snr=None, ap=None, coherent=None, passes=None):
+def _print_results(results, text: bool = False, snr=None, ap=None, coherent=None, passes=None, osd=None):
     """text: one extra `Message:` line per result, the payload unpacked to message text.  snr (one
     value per result): one extra `SNR:` line per result, dB in 2500 Hz.  ap (one pattern or None per
     result): one extra `AP: <pattern>` line for every a-priori decode.  coherent (one (dt_s, df_hz) or
     None per result): one extra `Coherent:` line for every decode from the coherent LLRs; a third entry
     (the drift search's rate, Hz/s) ends the line with `, drift +0.50 Hz/s`, and a last entry MULTI_SYMBOL
     with `, multi-symbol` after that.  passes (one 1-based pass per result): one extra `Pass: k` line for
-    every decode a later pass of a subtract decode appended (k >= 2)."""
+    every decode a later pass of a subtract decode appended (k >= 2).  osd (one order or None per result): one
+    extra `OSD: order k` line for every decode the ordered-statistics pass produced."""
     if not results:
         print("No FT8 messages decoded")
         return
@@ -205,6 +215,8 @@ def _print_results(results, text: bool = False, snr=None, ap=None, coherent=None
             print(f"Message: {texts.pop(0)}")
         if ap is not None and ap[k] is not None:
             print(f"AP: {ap[k]}")
+        if osd is not None and osd[k] is not None:
+            print(f"OSD: order {osd[k]}")
         if coherent is not None and coherent[k] is not None:
             multi = coherent[k][-1] == MULTI_SYMBOL
             fit = coherent[k][:-1] if multi else coherent[k]
@@ -244,6 +256,13 @@ def _drift_arg(text: str):
     return float(a), int(n) if n else DEFAULT_DRIFT[1]
 
 
+def _osd_arg(text: str):
+    """--osd ORDER[:N] -> (ORDER, N candidates per slot); N defaults to 32."""
+    from .osd import DEFAULT_MAX_PER_SLOT
+    a, _, n = text.partition(":")
+    return int(a), int(n) if n else DEFAULT_MAX_PER_SLOT
+
+
 def main(argv=None):
     """from_wave.py:180-229 (same flags).  Several wave files may be given (decoded as batches)."""
     parser = argparse.ArgumentParser(description="Decode FT8 signals from a wave file (MI355X GPU path)")
@@ -278,6 +297,12 @@ def main(argv=None):
     parser.add_argument("--coherent-ap", action="store_true",
                         help="with --ap and --coherent: also retry those candidates with the --ap patterns on their "
                              "coherent LLRs (such a decode carries both marks)")
+    parser.add_argument("--osd", nargs="?", type=_osd_arg, const=True, default=None, metavar="ORDER[:N]",
+                        help="ordered-statistics decoding, order 0 to 2, of the first N candidates of the slot that "
+                             "every other retry left failed (default 2:32, N = 0: all; such a decode is marked "
+                             "with the order)")
+    parser.add_argument("--osd-max-hard-errors", type=int, default=None,
+                        help="most hard decisions of an OSD decode that may contradict the received bits (default 36)")
     parser.add_argument("--selection", choices=("reference", "topk"), default="reference",
                         help="candidate selection: the reference's, or the max-candidates highest scores")
     parser.add_argument("--subtract", nargs="?", type=int, const=2, default=None, metavar="PASSES",
@@ -300,6 +325,16 @@ def main(argv=None):
         parser.error("--coherent-nsym needs --coherent")
     if args.coherent_ap and (not args.ap or coherent is None):
         parser.error("--coherent-ap needs --ap and --coherent")
+    if args.osd is not None:
+        from .osd import check_max_hard_errors, parse_option
+        try:
+            parse_option(args.osd)
+            if args.osd_max_hard_errors is not None:
+                check_max_hard_errors(args.osd_max_hard_errors)
+        except ValueError as e:
+            parser.error(f"--osd: {e}")
+    elif args.osd_max_hard_errors is not None:
+        parser.error("--osd-max-hard-errors needs --osd")
     paths = args.wave_file
     for path in paths:
         if not os.path.exists(path):
@@ -309,7 +344,8 @@ def main(argv=None):
               bins_per_tone=args.bins_per_tone, steps_per_symbol=args.steps_per_symbol,
               max_candidates=args.max_candidates, min_score=args.min_score, max_iterations=args.max_iterations)
     many = len(paths) > 1
-    if args.ap or args.snr or coherent is not None or args.subtract is not None or args.selection != "reference":
+    if (args.ap or args.snr or coherent is not None or args.subtract is not None or args.osd is not None
+            or args.selection != "reference"):
         # the report comes from the decode's own waterfall, an AP decode's mark from its own record:
         # one file at a time, each decoded once (lazily: a file is printed before the next is decoded)
         if args.correction:
@@ -326,6 +362,10 @@ def main(argv=None):
             kw = dict(kw, selection=args.selection)
         if args.subtract is not None:
             kw = dict(kw, subtract=args.subtract)
+        if args.osd is not None:
+            kw = dict(kw, osd=args.osd)
+            if args.osd_max_hard_errors is not None:
+                kw = dict(kw, osd_max_hard_errors=args.osd_max_hard_errors)
         decoded = (_decode_file(path, snr=args.snr, ap=args.ap, ap_max_hard_errors=args.ap_max_hard_errors, **kw)
                    for path in paths)
     elif many:
@@ -338,7 +378,8 @@ def main(argv=None):
             print(f"\n== {path}")
         fits = more.pop(0) if coherent is not None and more else None
         passes = more.pop(0) if args.subtract is not None and more else None
-        _print_results(results, args.text, snr, patterns, fits, passes)
+        orders = more.pop(0) if args.osd is not None and more else None
+        _print_results(results, args.text, snr, patterns, fits, passes, orders)
         per_file.append(results)
     return per_file if many else per_file[0]
 

@@ -38,6 +38,15 @@ def ap_decode_batch(llrs: np.ndarray, records: np.ndarray, max_iterations: int):
     return _device.ap_decode(llrs, records, max_iterations)
 
 
+def osd_decode_batch(llrs: np.ndarray, records: np.ndarray):
+    """Ordered-statistics retry (ft8_osd_decode) of the failed records ft8_bp wrote from llrs [n, 174], with
+    the order and hard-error limit of the thread's context (_lib.context().set_osd): -> (updated records,
+    info _lib.OSD_DTYPE [n]: weight, hard errors, flips and status of every attempt, codewords uint8 [n, 22]:
+    the winning codewords, MSB first).  The contract is in include/ft8hip.h; osd.osd_pass_restate is its NumPy
+    restatement."""
+    return _device.osd_decode(llrs, records)
+
+
 def coherent_ap_decode_batch(llrs: np.ndarray, records: np.ndarray, max_iterations: int, valid=None):
     """A-priori retry on coherent LLRs (ft8_coherent_ap_decode) of the failed records among `records`, with
     the hypotheses of the thread's context (_lib.context().set_ap): llrs [n, 174] or [n, S, 174] as

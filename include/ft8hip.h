@@ -94,11 +94,17 @@ typedef struct ft8_params {
  *                      among the plain decodes with pass_index bit 1 set.  F32 and I16 samples only; with
  *                      FT8_FLAG_SUBTRACT only after ft8_set_subtract(ctx, n, 1).  ft8_set_coherent_drift adds a search over linear
  *                      frequency drift to it, ft8_set_coherent_nsym joint LLRs over 2 and 3 symbols
- *                      (both off by default). */
+ *                      (both off by default).
+ *   FT8_FLAG_OSD       ft8_decode_batch decodes the first candidates of every slot that are still failed
+ *                      after the passes above by ordered-statistics decoding of their STFT LLRs
+ *                      ("ordered-statistics decoding" below; ft8_set_osd: order, cap per slot, hard-error
+ *                      limit).  Rescued candidates come out in candidate order among the other decodes with
+ *                      pass_index >> 4 = 15.  With FT8_FLAG_SUBTRACT only after ft8_set_subtract(ctx, n, 1). */
 #define FT8_FLAG_TOPK 1
 #define FT8_FLAG_SUBTRACT 2
 #define FT8_FLAG_AP 4
 #define FT8_FLAG_COHERENT 8
+#define FT8_FLAG_OSD 16
 
 /* One decoded (or attempted) candidate, 40 bytes, 8-byte aligned. */
 typedef struct ft8_result {
@@ -117,7 +123,8 @@ typedef struct ft8_result {
                               bit 1: decoded from the coherent LLRs (FT8_FLAG_COHERENT);
                               bit 2: ... at a drift rate other than 0 (ft8_set_coherent_drift);
                               bit 3: ... from a joint metric over 2 or 3 symbols (ft8_set_coherent_nsym);
-                              high nibble 0: plain BP; h + 1: a-priori hypothesis h (FT8_FLAG_AP, ft8_ap_decode) */
+                              high nibble 0: plain BP; h + 1 (1 .. 8): a-priori hypothesis h (FT8_FLAG_AP, ft8_ap_decode);
+                              15: ordered-statistics decoding (FT8_FLAG_OSD, ft8_osd_decode) */
 } ft8_result;
 
 /* One transmitted FT8 signal for ft8_synthesize, 40 bytes. */
@@ -568,6 +575,56 @@ int ft8_set_coherent_ap(ft8_ctx* ctx, int32_t on);
 int ft8_coherent_ap_decode(ft8_ctx* ctx, const double* d_llr, int32_t n_sets, const uint8_t* d_valid,
                            ft8_result* d_res, int32_t n, int32_t max_iterations, int16_t* d_hard, void* stream);
 
+/* ---- ordered-statistics decoding (OSD) of failed candidates -------------------------------------------
+ * Opt-in and build-defined like the a-priori and coherent passes (the reference has no counterpart);
+ * osd.py restates it in NumPy: osd_restate, osd_pass_restate.  All arithmetic is in integers, the echelon
+ * form is the unique reduced one and the candidates have a fixed order, so the restatement and the device
+ * agree bit for bit.  For one candidate with the LLRs L[174] as BP consumed them (positive = bit 1):
+ *   1. q[i] = min(floor(|L[i]| * 256), 65535) (+-inf: 65535), hard[i] = L[i] > 0.  A NaN among L, or every
+ *      q[i] == 0: not attempted (status 2).
+ *   2. perm: the indices sorted by q descending, equal q by index ascending.
+ *   3. G = [I | P] is the 91 x 174 systematic generator (column 91 + m: parity row m of FT8_GEN_ROWS_INIT).
+ *      Going through G's columns in perm order, a column is a basis column when it is independent of the
+ *      basis columns before it, until there are 91.  M is the reduced row echelon form for those pivots:
+ *      row k is the one row with a 1 in the k-th basis column and 0 in the other 90.
+ *   4. Candidates, in this order: c0 = the XOR of the rows k whose basis column has hard = 1; c0 ^ M[k],
+ *      k = 0 .. 90 (order >= 1); c0 ^ M[k1] ^ M[k2], k1 < k2 in lexicographic order (order 2):
+ *      1 + 91 + 4095 candidates.
+ *   5. weight(c) = the sum of q[i] over the positions where c differs from hard (int32).  The first
+ *      candidate of the smallest weight wins.
+ *   6. The winner, in natural bit order, goes through the reference tail as ft8_bp runs it on
+ *      plain = codeword with ldpc_errors = 0.  It is accepted when the tail says ok, its hard errors
+ *      n_hard = #{i : c[i] != hard[i]} <= max_hard_errors, and the 77 payload bits are not all zero.
+ *   7. An accepted candidate's record gets ok = 1, the payload, crc_extracted, crc_calculated,
+ *      ldpc_errors = 0 and pass_index |= 0xF0; score, slot, abs_time, abs_freq and cand_index stay, and
+ *      every other record stays as it was.
+ * One kernel, one 256-thread workgroup per candidate (csrc/osd.hip); no k_bp launch.
+ *
+ * The setting: order in [0, 2], max_per_slot >= 0 (0: every failed candidate; ft8_decode_batch only),
+ * max_hard_errors in [0, 174]; anything else: FT8_E_ARG, the setting unchanged.  Defaults: 2, 0, 36. */
+int ft8_set_osd(ft8_ctx* ctx, int32_t order, int32_t max_per_slot, int32_t max_hard_errors);
+typedef struct ft8_osd_rec {   /* 12 bytes */
+  int32_t weight;          /* the winner's weight; 0 for status 2 and 3 */
+  int16_t n_hard;          /* its hard errors; -1 for status 2 and 3 */
+  int16_t flip[2];         /* the rows k flipped against c0, -1 where none */
+  uint8_t n_flips;         /* 0 .. 2 */
+  uint8_t status;          /* 0 accepted; 1 attempted, not accepted; 2 not attempted (rule 1); 3 the record was ok */
+} ft8_osd_rec;
+/* The stage call, shaped like ft8_ap_decode: d_llr[n][174], d_res[n] records as ft8_bp left them, one list
+ * without a per-slot cap.  Every record with ok == 0 is tried with the context's order and max_hard_errors and
+ * updated in place.  d_info[n] (nullable): what the attempt found; d_codeword[n][22] (nullable): the winning
+ * codeword, MSB first, zeros for status 2 and 3.  n = 0 does nothing.  Caller-owned buffers, no context
+ * scratch; the call still takes part in the cross-stream order.
+ *
+ * FT8_FLAG_OSD inside ft8_decode_batch: last in every chunk, after the coherent passes and the a-priori
+ * pass, per slot on the first max_per_slot records still ok == 0 in candidate order, from the STFT LLRs
+ * (those the a-priori pass sees).  FT8_E_UNSUPPORTED together with FT8_FLAG_SUBTRACT unless
+ * ft8_set_subtract(ctx, n, 1); then it runs in every pass.  ft8_replay_stage refuses after such a batch.
+ * Scratch (context-owned, grow-only): 24 bytes per listed candidate (the list, and the compacted positions
+ * and scores the list kernel writes) and 4 per slot. */
+int ft8_osd_decode(ft8_ctx* ctx, const double* d_llr, ft8_result* d_res, int32_t n, ft8_osd_rec* d_info,
+                   uint8_t* d_codeword, void* stream);
+
 /* Per-slot flags of the last selection (copied device->device into d_out[n_slots]):
  * bit 0: an exact score tie reached a heap comparison (the reference raises TypeError there,
  *        ftx_types.py:37-47; here ties are ordered by scan index), bit 1: unused (0), bit 2
@@ -749,8 +806,8 @@ const char* ft8_build_flags(void);
  * (same buffers, same arguments; every stage is idempotent on its inputs), so a kernel's duration
  * can be measured by wall clock over back-to-back launches, without events between stages.  Valid
  * while the caller's buffers of that call are alive and until any other entry point of this
- * context runs (FT8_E_ARG otherwise, and after an FT8_FLAG_SUBTRACT, FT8_FLAG_AP or FT8_FLAG_COHERENT
- * batch, whose stages are not idempotent).  No reference counterpart. */
+ * context runs (FT8_E_ARG otherwise, and after an FT8_FLAG_SUBTRACT, FT8_FLAG_AP, FT8_FLAG_COHERENT
+ * or FT8_FLAG_OSD batch, whose stages are not idempotent).  No reference counterpart. */
 int ft8_replay_stage(ft8_ctx* ctx, int32_t stage, int32_t reps, void* stream);
 
 /* ---- per-stage device timing (HIP events on the caller's stream) --------------------------- */
