@@ -1320,7 +1320,6 @@ int subtract_core(ft8_ctx* c, const void* x, int dtype, float* resid, int64_t n_
   SubLaunch L{};
   int rc = baseband_setup(c, x, dtype, n_samples, n_slots, x_stride, p, "subtraction", &L.b);
   if (rc) return rc;
-  L.b.fs = (double)(int)rate_of(p);  // SubLaunch.fs was an int: a fractional rate stays truncated here, bit for bit
   c->sub_slots = c->sub_cap = -1;  // no valid fits until this subtraction has been launched
   if ((rc = gfsk_tables(c, L.b.nsps))) return rc;
   if ((rc = ensure(c, c->sub_est, sub_est_bytes() * (size_t)n_slots * (size_t)(cap > 0 ? cap : 1)))) return rc;

@@ -13,16 +13,16 @@ from ft8_demodulator_amd import ap as _ap
 ITERS = A.ITERS
 
 
-def stage_records(x, fs, max_candidates, min_score, flags):
-    """The device half: samples x [n_slots, n] (float32) through ft8_stft, ft8_sync_select and ft8_llr on a
-    context of its own -> (STFT LLRs [k, 174], rows [(slot, abs_time, abs_freq)] * k, the plain records [k] the
+def stage_records(x, fs, max_candidates, min_score, flags, bpt=2, sps=2):
+    """The device half: samples x [n_slots, n] (float32) through ft8_stft, ft8_sync_select and ft8_llr (at bpt
+    bins per tone and sps steps per symbol) on a context of its own -> (STFT LLRs [k, 174], rows [(slot, abs_time, abs_freq)] * k, the plain records [k] the
     oracle's BP decodes from the LLRs, with score, slot, cand_index, abs_time and abs_freq filled)."""
     from ft8_demodulator_amd._pipeline import make_params, make_plan
     torch = _lib.require_gpu()
     n_slots, n = x.shape
     ctx = _lib.Context(0)
     L, st = _lib.lib(), _lib.stream_handle(0)
-    plan = make_plan(n, fs)
+    plan = make_plan(n, fs, bins_per_tone=bpt, steps_per_symbol=sps)
     N = max_candidates
     p = make_params(plan, N, min_score, ITERS, flags)
     d_x = torch.from_numpy(x).cuda()
@@ -39,7 +39,7 @@ def stage_records(x, fs, max_candidates, min_score, flags):
     rows = [(s, int(cand[s, i, 0]), int(cand[s, i, 1])) for s in range(n_slots) for i in range(int(cnt[s]))]
     d_c3 = torch.tensor(rows, dtype=torch.int32, device="cuda")
     d_llr = torch.empty(len(rows), 174, dtype=torch.float64, device="cuda")
-    ctx.check(L.ft8_llr(ctx.handle, _lib.ptr(d_wf), 0, T, F, 2, 2, _lib.ptr(d_c3), len(rows), 1, _lib.ptr(d_llr), st),
+    ctx.check(L.ft8_llr(ctx.handle, _lib.ptr(d_wf), 0, T, F, sps, bpt, _lib.ptr(d_c3), len(rows), 1, _lib.ptr(d_llr), st),
               "ft8_llr")
     llr = d_llr.cpu().numpy()
     rec0 = A.plain_records(llr)
@@ -57,17 +57,17 @@ def _bp(x, iters):
         return A.oracle_lib().bp_decode(x, iters)
 
 
-def expectation(x, fs, search, cap=None, drift=None, nsym=1, ap=None):
+def expectation(x, fs, search, cap=None, drift=None, nsym=1, ap=None, bpt=2, sps=2):
     """The records ft8_decode_batch must return for the slots x under the TOPK selection `search`
     (max_candidates, min_score), from stage_records: each slot's first `cap` (a number, or a function of the
     plain records that returns (slot, cap) as late_cap does; None: no coherent pass) failed candidates get the
     stage call's coherent LLRs -- with the drift search `drift` and up to `nsym` symbols per metric where
-    given -- and coherent_pass_restate applies them; with the patterns `ap`, ap_cases.restate follows on the STFT
+    given, at bpt bins per tone and sps steps per symbol -- and coherent_pass_restate applies them; with the patterns `ap`, ap_cases.restate follows on the STFT
     LLRs.  -> dict: x, the plain records, those after the coherent pass, `both` after coherent + AP (None
     without ap), the listed indices, cap and late_cap's slot; the arrays are read-only."""
     from ft8_demodulator_amd.ldpc_decoder import coherent_llr_batch
     x = np.array(x)
-    llr, rows, rec0 = stage_records(x, fs, search["max_candidates"], search["min_score"], _lib.FT8_FLAG_TOPK)
+    llr, rows, rec0 = stage_records(x, fs, search["max_candidates"], search["min_score"], _lib.FT8_FLAG_TOPK, bpt, sps)
     slot = None
     if callable(cap):
         slot, cap = cap(rec0)
@@ -80,7 +80,8 @@ def expectation(x, fs, search, cap=None, drift=None, nsym=1, ap=None):
             kw["drift"] = drift
         if nsym > 1:
             kw["nsym"] = nsym
-        out = coherent_llr_batch(x, [rows[i][1:] for i in listed], [rows[i][0] for i in listed], fs, **kw)
+        out = coherent_llr_batch(x, [rows[i][1:] for i in listed], [rows[i][0] for i in listed], fs,
+                                 bins_per_tone=bpt, steps_per_symbol=sps, **kw)
         drifts = out[2] if drift is not None else None
         valid = out[-1] if nsym > 1 else None
         if valid is not None:
@@ -110,7 +111,8 @@ def per_slot(rec, s):
     return rec[(rec["slot"] == s) & (rec["ok"] == 1)]
 
 
-def decoder(fs, search, **kw):
+def decoder(fs, search, bpt=2, sps=2, **kw):
     """A SlotDecoder under the TOPK selection `search` (flags= replaces the flags)."""
     from ft8_demodulator_amd._pipeline import SlotDecoder
-    return SlotDecoder(fs, max_iterations=ITERS, flags=kw.pop("flags", _lib.FT8_FLAG_TOPK), **search, **kw)
+    return SlotDecoder(fs, bins_per_tone=bpt, steps_per_symbol=sps, max_iterations=ITERS,
+                       flags=kw.pop("flags", _lib.FT8_FLAG_TOPK), **search, **kw)

@@ -11,40 +11,16 @@ import retry_cases as R
 pytestmark = pytest.mark.gpu
 
 ITERS = C.ITERS
-# max |LLR_device - LLR_restate| over the stage test's candidates, measured once on an MI355X against
-# the float64 restatement: 1.65e-5 (12 kHz float32), 1.86e-5 (int16), 1.11e-5 (10 kHz); the LLRs are scaled
-# to a variance of 24.  The bound is 8 x the largest (float32 summation order varies by a small factor
-# from input to input); 1 % of sqrt(24) would be 4.9e-2.
-LLR_MEASURED = 1.86e-5
-LLR_BOUND = 8 * LLR_MEASURED
+# the stage comparison and its bound live beside the cases (coherent_cases.check_stage), shared with
+# test_gpu_baseband_geometry.py
+LLR_MEASURED = C.LLR_MEASURED
+LLR_BOUND = C.LLR_BOUND
+_check_stage = C.check_stage
 
 
 def _L():
     from ft8_demodulator_amd import _lib
     return _lib
-
-
-def _check_stage(name, got, ref, fs, D, binw):
-    from ft8_demodulator_amd import coherent
-    llr, fits = got
-    rllr, rfits, grids = ref
-    assert np.array_equal(fits["status"], rfits["status"])
-    assert np.array_equal(fits["n_sync"], rfits["n_sync"])
-    measured = fits["status"] == 0
-    tie = np.array([g is not None and coherent.near_tie(g) for g in grids])
-    cmp_ = measured & ~tie
-    assert int((measured & tie).sum()) * 20 <= int(measured.sum())
-    assert np.array_equal(fits["dt_index"][cmp_], rfits["dt_index"][cmp_])
-    assert np.array_equal(fits["df_index"][cmp_], rfits["df_index"][cmp_])
-    assert np.abs(fits["df_hz"][cmp_].astype(np.float64) - rfits["df_hz"][cmp_]).max() <= 0.01
-    assert np.array_equal(fits["dt_s"][cmp_], (rfits["dt_index"][cmp_] * (D / fs)).astype(np.float32))
-    assert np.allclose(fits["metric"][cmp_], rfits["metric"][cmp_], rtol=1e-4)
-    # status 2 / 3: zeros
-    assert (llr[~measured] == 0.0).all()
-    err = float(np.abs(llr[cmp_] - rllr[cmp_]).max())
-    print(f"{name}: {int(cmp_.sum())} candidates compared, {int((measured & tie).sum())} near ties left out, "
-          f"max |LLR_device - LLR_restate| = {err:.3e} (bound {LLR_BOUND:.3e})")
-    assert err <= LLR_BOUND
 
 
 @pytest.mark.parametrize("key", ["f32", "i16"])
@@ -167,6 +143,42 @@ def test_e2e_pipelined_chunks_and_int16(gpu, e2e):
     pcm = gpu.from_numpy(np.array(C.stage_case_12k()["pcm"])).cuda()
     got16 = _decoder(coherent=CAP).records(pcm, code=_L().FT8_I16)
     assert sum(int((r["pass_index"] == 2).sum()) for r in got16) >= 2
+
+
+# ---- the construction at bins_per_tone != steps_per_symbol ----------------------------------------------
+FACTORS = [(3, 2), (2, 4)]
+
+
+@pytest.fixture(scope="module", params=FACTORS, ids=["3x2", "2x4"])
+def e2e_factors(request, gpu, oracle):
+    """The e2e fixture's construction (three slots, coherent=4, ap=["CQ ? ?"]) with every stage call, the
+    restatements and the decoder at (bpt, sps) -> (bpt, sps, expectation)."""
+    bpt, sps = request.param
+    return bpt, sps, R.expectation(C.stage_case_12k()["x"], C.FS, E2E, CAP, ap=AP, bpt=bpt, sps=sps)
+
+
+def test_e2e_factors_expectation_shows_every_outcome(e2e_factors):
+    """On the expectation alone, at each pair: a plain decode, a rescue of a transmitted payload, a listed
+    candidate that stays failed."""
+    bpt, sps, e = e2e_factors
+    plain, coh = e["plain"], e["coherent"]
+    sent = set(C.stage_case_12k()["payloads"])
+    rescued = coh[coh["pass_index"] == 2]
+    print(f"({bpt}, {sps}): plain decodes {int(plain['ok'].sum())}, rescues {len(rescued)}, listed {len(e['listed'])}")
+    assert int(plain["ok"].sum()) >= 1
+    assert len(rescued) >= 1 and all(bytes(r["payload"]) in sent for r in rescued)
+    assert len(rescued) < len(e["listed"]) <= 3 * CAP
+
+
+def test_e2e_factors_records_equal_construction(gpu, e2e_factors):
+    """Coherent alone and coherent + AP: the batch's records equal the construction's field for field."""
+    bpt, sps, e = e2e_factors
+    x = gpu.from_numpy(e["x"]).cuda()
+    for kw, key in ((dict(coherent=CAP), "coherent"), (dict(coherent=CAP, ap=AP), "both")):
+        got = R.decoder(C.FS, E2E, bpt, sps, **kw).records(x)
+        assert len(got) == 3
+        for s in range(3):
+            A.records_equal(got[s], _per_slot(e[key], s))
 
 
 def test_late_cap_expectation_fills_the_list_in_the_second_round(e2e_late):

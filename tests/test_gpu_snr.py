@@ -27,9 +27,11 @@ def _random_wf(torch, seed, T, F, f64, n_slots=N_SLOTS):
     return wf, torch.from_numpy(wf).cuda()
 
 
-def _random_records(seed, T, F, n_slots=N_SLOTS, cap=CAP):
+def _random_records(seed, T, F, n_slots=N_SLOTS, cap=CAP, bpt=BPT, sps=SPS):
     """Random payloads; abs_time from -20 to T + 5 with both ends present, abs_freq over every
-    admissible tone-0 bin with both edges present (F = 15: only 0); record [2, 1] is not ok."""
+    admissible tone-0 bin with both edges present (F = 15: only 0); record [2, 1] is not ok.  Records
+    [0, 0] and [2, 3] put symbol 78's row at T (in range only at dt = -1), records at the last admissible
+    bin put tone 7's bin at F - 1 (df = +1 is skipped): both straddles occur at every (bpt, sps)."""
     _lib = _L()
     rng = np.random.default_rng(seed)
     r = np.zeros((n_slots, cap), dtype=_lib.RESULT_DTYPE)
@@ -38,12 +40,17 @@ def _random_records(seed, T, F, n_slots=N_SLOTS, cap=CAP):
     r["payload"] = pay
     r["ok"] = 1
     r["ok"][2, 1] = 0
-    f_max = F - 1 - 7 * BPT
+    f_max = F - 1 - 7 * bpt
     r["abs_time"] = rng.integers(-20, T + 6, size=(n_slots, cap))
     r["abs_freq"] = rng.integers(0, f_max + 1, size=(n_slots, cap))
     r["abs_time"][1, 0], r["abs_time"][1, 1], r["abs_time"][2, 0] = -20, T + 5, min(T - 1, 3)
     r["abs_freq"][1, 0], r["abs_freq"][1, 1], r["abs_freq"][2, 0], r["abs_freq"][2, 2] = 0, f_max, f_max, 0
+    r["abs_time"][0, 0] = r["abs_time"][2, 3] = T - 78 * sps
     r["slot"] = np.arange(n_slots)[:, None]
+    ok = r["ok"] != 0
+    last_row, top_bin = r["abs_time"] + 78 * sps, r["abs_freq"] + 7 * bpt
+    assert (ok & (last_row - 1 < T) & (last_row + 1 >= T) & (last_row - 1 >= 0)).any()      # straddles T
+    assert (ok & (top_bin - 1 <= F - 1) & (top_bin + 1 > F - 1)).any()                       # straddles F - 1
     return r
 
 
@@ -61,13 +68,13 @@ def _noise_floor(torch, d_wf, q, ctx=None):
     return d_n0, d_A
 
 
-def _params(n_samples=180000):
+def _params(n_samples=180000, bpt=BPT, sps=SPS):
     from ft8_demodulator_amd._pipeline import make_params, make_plan
-    plan = make_plan(n_samples, FS, BPT, SPS)
+    plan = make_plan(n_samples, FS, bpt, sps)
     return plan, make_params(plan, 20, 10, 20)
 
 
-def _snr(torch, d_wf, recs, counts, d_n0, radius=1, ctx=None):
+def _snr(torch, d_wf, recs, counts, d_n0, radius=1, ctx=None, bpt=BPT, sps=SPS):
     """ft8_snr -> ft8_snr_rec [n_slots, cap]; the output starts as 0xA5 bytes."""
     import ctypes
     _lib = _L()
@@ -77,7 +84,8 @@ def _snr(torch, d_wf, recs, counts, d_n0, radius=1, ctx=None):
     d_rec = torch.from_numpy(recs.reshape(-1).view(np.uint8).copy()).cuda()
     d_cnt = None if counts is None else torch.as_tensor(np.asarray(counts, dtype=np.int32)).cuda()
     d_out = torch.full((n_slots * cap * 24,), 0xA5, dtype=torch.uint8, device="cuda")
-    _, p = _params()
+    _, p = _params(bpt=bpt, sps=sps)
+    assert (p.bins_per_tone, p.steps_per_symbol) == (bpt, sps)
     rc = _lib.lib().ft8_snr(ctx.handle, _lib.ptr(d_wf), int(d_wf.dtype == torch.float64), n_slots, T, F,
                             ctypes.byref(p), 180000, _lib.ptr(d_rec), None if d_cnt is None else _lib.ptr(d_cnt), cap,
                             _lib.ptr(d_n0), radius, _lib.ptr(d_out), _lib.stream_handle(0))
@@ -105,33 +113,47 @@ def _check_reports(got, want, info):
 
 
 # ---- the two kernels against the restatement ----------------------------------------------------------
-@pytest.mark.parametrize("f64", [False, True], ids=["f32", "f64"])
-@pytest.mark.parametrize("F", [15, 63, 65, 1920, 3840])
-@pytest.mark.parametrize("T", [1, 7, 100])
-def test_kernels_equal_restatement(gpu, T, F, f64):
+def _kernels_equal_restatement(gpu, T, F, f64, bpt=BPT, sps=SPS):
     from ft8_demodulator_amd.snr import noise_floor_reference, snr_reference
-    seed = 1000 * T + F + int(f64)
+    seed = 1000 * T + F + int(f64) + (0 if (bpt, sps) == (BPT, SPS) else 100000 * (10 * bpt + sps))
     wf, d_wf = _random_wf(gpu, seed, T, F, f64)
     n0_ref, A_ref = noise_floor_reference(wf, 0.25)
     d_n0, d_A = _noise_floor(gpu, d_wf, 0.25)
     np.testing.assert_allclose(d_A.cpu().numpy(), A_ref, rtol=1e-12, atol=0)
     np.testing.assert_allclose(d_n0.cpu().numpy(), n0_ref, rtol=1e-12, atol=0)
-    recs = _random_records(seed, T, F)
+    recs = _random_records(seed, T, F, bpt=bpt, sps=sps)
     for counts in (COUNTS, None):
-        want, info = snr_reference(wf, recs, counts, FS, BPT, SPS, q=0.25, radius=1, details=True)
-        got = _snr(gpu, d_wf, recs, counts, d_n0)
+        want, info = snr_reference(wf, recs, counts, FS, bpt, sps, q=0.25, radius=1, details=True)
+        got = _snr(gpu, d_wf, recs, counts, d_n0, bpt=bpt, sps=sps)
         _check_reports(got, want, info)
     live = want["status"] < 2
-    print(f"T={T} F={F}: max |snr_db - restatement| = "
+    print(f"T={T} F={F} bpt={bpt} sps={sps}: max |snr_db - restatement| = "
           f"{np.nanmax(np.abs(got['snr_db'][live] - want['snr_db'][live])) if live.any() else 0:.3g} dB, "
           f"max rel colmean error = {np.max(np.abs(d_A.cpu().numpy() / A_ref - 1)):.3g}")
     if T >= 7 and F > 15:
         assert (want["status"] == 0).any()
     # radius 0: the record's own grid point
-    want0, info0 = snr_reference(wf, recs, COUNTS, FS, BPT, SPS, q=0.25, radius=0, details=True)
-    got0 = _snr(gpu, d_wf, recs, COUNTS, d_n0, radius=0)
+    want0, info0 = snr_reference(wf, recs, COUNTS, FS, bpt, sps, q=0.25, radius=0, details=True)
+    got0 = _snr(gpu, d_wf, recs, COUNTS, d_n0, radius=0, bpt=bpt, sps=sps)
     _check_reports(got0, want0, info0)
     assert not got0["dt"].any() and not got0["df"].any()
+
+
+@pytest.mark.parametrize("f64", [False, True], ids=["f32", "f64"])
+@pytest.mark.parametrize("F", [15, 63, 65, 1920, 3840])
+@pytest.mark.parametrize("T", [1, 7, 100])
+def test_kernels_equal_restatement(gpu, T, F, f64):
+    _kernels_equal_restatement(gpu, T, F, f64)
+
+
+@pytest.mark.parametrize("f64", [False, True], ids=["f32", "f64"])
+@pytest.mark.parametrize("F", [65, 1920])
+@pytest.mark.parametrize("T", [7, 100])
+@pytest.mark.parametrize("bpt,sps", [(3, 2), (1, 2), (2, 1), (2, 4), (5, 5)])
+def test_kernels_equal_restatement_other_factors(gpu, bpt, sps, T, F, f64):
+    """bins_per_tone != steps_per_symbol (a transposed pair between ft8_params and launch_snr reads other
+    rows and bins: tests/test_baseband_geometry_cases.py) and a pair the decode chain does not use."""
+    _kernels_equal_restatement(gpu, T, F, f64, bpt, sps)
 
 
 def test_counts_ok_and_status(gpu):

@@ -23,6 +23,7 @@ pytestmark = pytest.mark.gpu
 
 N_SLOTS, SIGNALS, SEED = 6, 50, 777
 K, MIN_SCORE, ITERS = 300, 2, 20
+SEED_3x2, SNR_3x2 = 780, (-24.0, -10.0)      # the batch at (3, 2): see its test
 
 
 def test_subtract_pass2_matches_oracle(gpu, oracle):
@@ -110,6 +111,38 @@ def test_subtract_pass2_matches_oracle(gpu, oracle):
     print(f"subtract oracle: {n_fits} fits, {n_start_off} with start +-1, {n_new} rows appended by the merge")
 
 
+def test_subtract_batch_at_3_bins_2_steps_matches_oracle(gpu, oracle):
+    """One FT8_FLAG_SUBTRACT batch at bins_per_tone 3, steps_per_symbol 2 (nfft 5760, hop 960): two slots
+    of eight signals, K = 40.  Pass 1 decodes the oracle's top-k payload set; the rows the batch appends
+    carry the payloads the oracle decodes anew from its own residual of its own fits, as the six-slot test
+    above states at (2, 2)."""
+    from ft8_demodulator_amd import SlotDecoder, _lib, synth
+    from oracle import subtract as OS
+    BPT, SPS, K2 = 3, 2, 40
+    x, _ = synth.make_slots(2, 8, snr_db=SNR_3x2, seed=SEED_3x2, device="cuda")
+    xs = x.cpu().numpy()
+    dec = SlotDecoder(12000, BPT, SPS, K2, MIN_SCORE, ITERS, flags=_lib.FT8_FLAG_TOPK)
+    recs = dec.records(x)
+    plan = dec.plan(x.shape[1])
+    assert (plan.nperseg, plan.hop, plan.nfft) == (1920, 960, 5760)
+    one_call = SlotDecoder(12000, BPT, SPS, K2, MIN_SCORE, ITERS,
+                           flags=_lib.FT8_FLAG_TOPK | _lib.FT8_FLAG_SUBTRACT).records(x)
+    n_new = 0
+    for s in range(2):
+        p1 = {bytes(r["payload"]) for r in recs[s]}
+        o1 = {pay for pay, _, _ in OS.decode_topk(xs[s], 12000, K2, MIN_SCORE, ITERS, bpt=BPT, sps=SPS)}
+        assert p1 == o1 and len(p1) >= 3, s
+        ofit = OS.fits(xs[s], recs[s], 12000, plan.nperseg, plan.hop, plan.nfft, plan.t_lo, plan.f_lo)
+        ores = OS.residual(xs[s], ofit, plan.nperseg, 12000)
+        new_o = {pay for pay, _, _ in OS.decode_topk(ores.astype(np.float32), 12000, K2, MIN_SCORE, ITERS, bpt=BPT,
+                                                     sps=SPS)} - o1
+        assert {bytes(r["payload"]) for r in one_call[s] if r["pass_index"] == 0} == p1, s
+        assert {bytes(r["payload"]) for r in one_call[s] if r["pass_index"] == 1} == new_o, s
+        n_new += len(new_o)
+    print(f"subtract batch at (3, 2): {n_new} payloads decoded anew from the residual")
+    assert n_new >= 1
+
+
 # ---- the paths of the baseband front end (csrc/baseband.h) that a crowded slot does not take ----------
 # one slot each; the tolerances are the test's above
 
@@ -146,8 +179,9 @@ def _check_fits(gfit, ofit):
 
 def _window(plan, rec):
     """[first, last) input sample of the baseband k_sub_est decimates for a record."""
-    Q = 32
-    assert plan.nperseg % Q == 0
+    from oracle import subtract as OS
+    Q = OS.sub_q(plan.nperseg)
+    assert Q >= 8 and plan.nperseg % Q == 0
     D, sps = plan.nperseg // Q, plan.nperseg // plan.hop
     Mg = (Q + 2 * sps - 1) // (2 * sps) + 1
     nb = (plan.t_lo + int(rec["abs_time"])) * plan.hop - Mg * D
