@@ -18,6 +18,57 @@ namespace {
 
 constexpr int kApWaves = 4;  // candidates per 256-thread workgroup
 
+// bit i (< 80) of a 10-byte MSB-first field
+__device__ __forceinline__ bool bit77(const uint8_t* b, int i) { return (b[i >> 3] >> (7 - (i & 7))) & 1; }
+
+// The three blocks the AP kernels and the coherent-AP kernels share; a wave works on one LLR vector L[174].
+// a = 1.01 max |L| (one multiply in double after the reduction), 0 where any of L is NaN (NumPy's max
+// then is NaN); the same value in every lane
+__device__ __forceinline__ double wave_amax(const double* L, int lane) {
+  double m = 0.0;
+  bool nan = false;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int i = lane + kWave * j;
+    if (i < FT8_LDPC_N) {
+      const double v = L[i];
+      nan |= v != v;
+      m = fmax(m, fabs(v));
+    }
+  }
+  for (int d = kWave / 2; d > 0; d >>= 1) m = fmax(m, __shfl_xor(m, d));
+  const bool any_nan = __ballot(nan) != 0;
+  return any_nan ? 0.0 : 1.01 * m;
+}
+// out = L with the hypothesis' masked bits at +amp / -amp
+__device__ __forceinline__ void wave_clamp(const double* L, const ft8_ap_hyp& hyp, double amp, double* out, int lane) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int i = lane + kWave * k;
+    if (i < FT8_LDPC_N) {
+      double v = L[i];
+      if (i < 77 && bit77(hyp.mask, i)) v = bit77(hyp.value, i) ? amp : -amp;
+      out[i] = v;
+    }
+  }
+}
+// acceptance tests 2 and 3 of an attempt that decoded to `got` with the hard decisions `plain`: -1 where
+// the payload differs from the hypothesis on a masked bit, else the hard errors of the decisions against
+// the signs of the unclamped L (three ballots); the same value in every lane
+__device__ __forceinline__ int wave_hard_errors(const ft8_result& got, const ft8_ap_hyp& hyp, const double* L,
+                                                const uint8_t* plain, int lane) {
+  const bool differ = lane < 10 && ((got.payload[lane] ^ hyp.value[lane]) & hyp.mask[lane]) != 0;
+  if (__ballot(differ) != 0) return -1;
+  int hard = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int i = lane + kWave * k;
+    const bool err = i < FT8_LDPC_N && (plain[i] != 0) != (L[i] > 0.0);
+    hard += __popcll(__ballot(err));
+  }
+  return hard;
+}
+
 // one wave per candidate: amax[item] = 1.01 max |L| (one multiply in double), or 0 where the candidate
 // is not to be retried: past the slot's count, already ok, a NaN among its LLRs (NumPy's max then is
 // NaN), or all LLRs zero
@@ -32,20 +83,8 @@ __global__ __launch_bounds__(kApWaves* kWave) void k_ap_amax(ApLaunch a) {
     return;
   }
   const double* L = a.llr + item * FT8_LDPC_N;
-  double m = 0.0;
-  bool nan = false;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int i = lane + kWave * j;
-    if (i < FT8_LDPC_N) {
-      const double v = L[i];
-      nan |= v != v;
-      m = fmax(m, fabs(v));
-    }
-  }
-  for (int d = kWave / 2; d > 0; d >>= 1) m = fmax(m, __shfl_xor(m, d));
-  const bool any_nan = __ballot(nan) != 0;
-  if (lane == 0) a.amax[item] = any_nan ? 0.0 : 1.01 * m;
+  const double amp = wave_amax(L, lane);
+  if (lane == 0) a.amax[item] = amp;
 }
 
 // one wave per slot: the first M candidates to retry, in candidate order (ballot / popcount scan as
@@ -72,9 +111,6 @@ __global__ __launch_bounds__(kWave) void k_retry_list(RetryLists r) {
   if (lane == 0) r.count[slot] = min(base, r.M);
 }
 
-// bit i (< 80) of a 10-byte MSB-first field
-__device__ __forceinline__ bool bit77(const uint8_t* b, int i) { return (b[i >> 3] >> (7 - (i & 7))) & 1; }
-
 // one wave per list position: llr_h = the candidate's LLRs, masked bits at +a / -a
 __global__ __launch_bounds__(kApWaves* kWave) void k_ap_clamp(ApLaunch a) {
   const RetryLists& r = a.r;
@@ -87,15 +123,7 @@ __global__ __launch_bounds__(kApWaves* kWave) void k_ap_clamp(ApLaunch a) {
   const double amp = a.amax[src];
   const double* L = a.llr + src * FT8_LDPC_N;
   double* out = a.llr_h + pos * FT8_LDPC_N;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int i = lane + kWave * k;
-    if (i < FT8_LDPC_N) {
-      double v = L[i];
-      if (i < 77 && bit77(a.hyp.mask, i)) v = bit77(a.hyp.value, i) ? amp : -amp;
-      out[i] = v;
-    }
-  }
+  wave_clamp(L, a.hyp, amp, out, lane);
 }
 
 // one wave per list position: the acceptance test of the attempt k_bp just made
@@ -108,21 +136,11 @@ __global__ __launch_bounds__(kApWaves* kWave) void k_ap_merge(ApLaunch a) {
   if (j >= r.count[slot]) return;
   const ft8_result& got = a.res_h[pos];
   if (!got.ok) return;  // 1. the tail says ok
-  // 2. the decoded payload agrees with the hypothesis on every masked bit
-  const bool differ = lane < 10 && ((got.payload[lane] ^ a.hyp.value[lane]) & a.hyp.mask[lane]) != 0;
-  if (__ballot(differ) != 0) return;
-  // 3. hard errors of the attempt's decisions against the signs of the unclamped LLRs
+  // 2. the decoded payload agrees with the hypothesis on every masked bit; 3. hard errors of the attempt's
+  // decisions against the signs of the unclamped LLRs
   const int64_t src = (int64_t)slot * r.N + r.list[pos];
-  const double* L = a.llr + src * FT8_LDPC_N;
-  const uint8_t* plain = a.plain + pos * FT8_LDPC_N;
-  int hard = 0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int i = lane + kWave * k;
-    const bool err = i < FT8_LDPC_N && (plain[i] != 0) != (L[i] > 0.0);
-    hard += __popcll(__ballot(err));
-  }
-  if (hard > a.max_hard) return;
+  const int hard = wave_hard_errors(got, a.hyp, a.llr + src * FT8_LDPC_N, a.plain + pos * FT8_LDPC_N, lane);
+  if (hard < 0 || hard > a.max_hard) return;
   if (lane == 0) {
     retry_accept(r.res + src, got, (a.h + 1) << 4);
     if (a.hard) a.hard[src] = (int16_t)hard;
@@ -147,13 +165,16 @@ hipError_t launch_retry_list(const RetryLists& r, hipStream_t s) {
   return hipGetLastError();
 }
 
+// k_ap_clamp and k_ap_merge walk the lists with the records' stride: M = N (ApLaunch, ft8_internal.h)
 hipError_t launch_ap_clamp(const ApLaunch& a, hipStream_t s) {
+  if (a.r.M != a.r.N) return hipErrorInvalidValue;
   if (a.r.n_slots <= 0 || a.r.N <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_ap_clamp, dim3(item_blocks(a)), dim3(kApWaves * kWave), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_ap_merge(const ApLaunch& a, hipStream_t s) {
+  if (a.r.M != a.r.N) return hipErrorInvalidValue;
   if (a.r.n_slots <= 0 || a.r.N <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_ap_merge, dim3(item_blocks(a)), dim3(kApWaves * kWave), 0, s, a);
   return hipGetLastError();
@@ -196,20 +217,8 @@ __global__ __launch_bounds__(kApWaves* kWave) void k_cohap_amax(CohApLaunch a) {
     return;
   }
   const double* L = a.llr + pos * a.pos_stride + n * a.set_stride;
-  double m = 0.0;
-  bool nan = false;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int i = lane + kWave * k;
-    if (i < FT8_LDPC_N) {
-      const double v = L[i];
-      nan |= v != v;
-      m = fmax(m, fabs(v));
-    }
-  }
-  for (int d = kWave / 2; d > 0; d >>= 1) m = fmax(m, __shfl_xor(m, d));
-  const bool any_nan = __ballot(nan) != 0;
-  if (lane == 0) a.amax[item] = any_nan ? 0.0 : 1.01 * m;
+  const double amp = wave_amax(L, lane);
+  if (lane == 0) a.amax[item] = amp;
 }
 
 __global__ __launch_bounds__(kWave) void k_cohap_list(CohApLaunch a) {
@@ -251,15 +260,7 @@ __global__ __launch_bounds__(kApWaves* kWave) void k_cohap_clamp(CohApLaunch a) 
   const double amp = a.amax[pos * a.S + n];
   const double* L = a.llr + pos * a.pos_stride + n * a.set_stride;
   double* out = a.llr_a + ap * FT8_LDPC_N;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int i = lane + kWave * k;
-    if (i < FT8_LDPC_N) {
-      double v = L[i];
-      if (i < 77 && bit77(a.hyp[h].mask, i)) v = bit77(a.hyp[h].value, i) ? amp : -amp;
-      out[i] = v;
-    }
-  }
+  wave_clamp(L, a.hyp[h], amp, out, lane);
 }
 
 __global__ __launch_bounds__(kApWaves* kWave) void k_cohap_merge(CohApLaunch a) {
@@ -277,20 +278,11 @@ __global__ __launch_bounds__(kApWaves* kWave) void k_cohap_merge(CohApLaunch a) 
       if (w < 0 || w >= a.att.count[slot]) continue;   // not listed: the (position, set) is not tried
       const ft8_result& got = a.res_a[l0 + w];
       if (!got.ok) continue;  // 1. the tail says ok
-      // 2. the decoded payload agrees with the hypothesis on every masked bit
-      const bool differ = lane < 10 && ((got.payload[lane] ^ a.hyp[h].value[lane]) & a.hyp[h].mask[lane]) != 0;
-      if (__ballot(differ) != 0) continue;
-      // 3. hard errors of the attempt's decisions against the signs of set n's unclamped LLRs
-      const double* L = a.llr + pos * a.pos_stride + n * a.set_stride;
-      const uint8_t* plain = a.plain + (l0 + w) * FT8_LDPC_N;
-      int hard = 0;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int i = lane + kWave * k;
-        const bool err = i < FT8_LDPC_N && (plain[i] != 0) != (L[i] > 0.0);
-        hard += __popcll(__ballot(err));
-      }
-      if (hard > a.max_hard) continue;
+      // 2. the decoded payload agrees with the hypothesis on every masked bit; 3. hard errors of the attempt's
+      // decisions against the signs of set n's unclamped LLRs
+      const int hard = wave_hard_errors(got, a.hyp[h], a.llr + pos * a.pos_stride + n * a.set_stride,
+                                        a.plain + (l0 + w) * FT8_LDPC_N, lane);
+      if (hard < 0 || hard > a.max_hard) continue;
       if (lane == 0) {
         const int bits = (a.drift && a.drift[pos].rate_hz_per_s != 0.f ? 6 : 2) | (n > 0 ? 8 : 0) | ((h + 1) << 4);
         retry_accept(rec, got, bits);

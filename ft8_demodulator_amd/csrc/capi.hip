@@ -111,11 +111,16 @@ hipError_t lds_opt_in(const void* kernel, size_t dyn_bytes) {
 
 namespace {
 int ensure(ft8_ctx* c, DevBuf& b, size_t bytes);  // grow-only scratch, below
+int fail(ft8_ctx* c, int code, const std::string& msg);
 }
-// The buffers the two retry passes of ft8_decode_batch have in common (RetryLists, ft8_internal.h): the
-// lists and, per list position, the LLRs k_bp decodes and the records it writes.  ensure: n_slots
-// lists of M positions; at: the scratch of the chunk that starts at slot `slot0`, with the chunk's
-// records and candidates (`in`: everything but M and the list arrays).
+// ---- the retry passes' settings and scratch (ft8_internal.h, "retry pass") -------------------------
+// Each pass of ft8_decode_batch owns one struct below: its settings (ft8_set_*), its scratch, `ensure`
+// (the scratch for n_slots lists; ft8hip.h states the sizes) and `at` (every pointer of the chunk that
+// starts at slot `slot0`, offset there and nowhere else, so the chunks of a pipelined batch share none).
+//
+// What the passes have in common (RetryLists): the lists and, per list position, `sets` LLR vectors and
+// records for k_bp, set-major (the coherent pass's multi-symbol sets; 0: the pass decodes without k_bp).
+// at: `in` is the chunk's records and candidates (everything but M and the list arrays).
 struct RetryView {
   RetryLists lists;
   double* llr;
@@ -125,7 +130,6 @@ struct RetryScratch {
   DevBuf list, count, cand, score, llr, res;
   int M = 0;
   size_t n_all = 0;  // list positions of all chunks: the distance between two sets' LLRs and records
-  // sets: LLR vectors and records per list position (the coherent pass's multi-symbol sets), set-major
   int ensure(ft8_ctx* c, size_t n_slots, int M_, int sets = 1) {
     const size_t n = n_slots * (size_t)M_;
     M = M_;
@@ -134,7 +138,7 @@ struct RetryScratch {
     if ((rc = ::ensure(c, list, sizeof(int32_t) * n))) return rc;
     if ((rc = ::ensure(c, count, sizeof(int32_t) * n_slots))) return rc;
     if ((rc = ::ensure(c, cand, sizeof(int32_t) * 2 * n))) return rc;
-    if ((rc = ::ensure(c, score, sizeof(double) * n))) return rc;
+    if ((rc = ::ensure(c, score, sizeof(double) * n)) || sets == 0) return rc;
     if ((rc = ::ensure(c, llr, sizeof(double) * FT8_LDPC_N * n * sets))) return rc;
     return ::ensure(c, res, sizeof(ft8_result) * n * sets);
   }
@@ -145,8 +149,100 @@ struct RetryScratch {
     in.count = count.as<int32_t>() + slot0;
     in.cand = cand.as<int32_t>() + 2 * r0;
     in.score = score.as<double>() + r0;
-    return {in, llr.as<double>() + (size_t)FT8_LDPC_N * r0, res.as<ft8_result>() + r0};
+    return {in, llr.p ? llr.as<double>() + (size_t)FT8_LDPC_N * r0 : nullptr, res.p ? res.as<ft8_result>() + r0 : nullptr};
   }
+};
+
+// a-priori decoding (ft8_set_ap): the hypotheses and the hard-error limit; lists of M = N, amax per
+// record, plain per list position
+struct ApRetry {
+  std::vector<ft8_ap_hyp> hyps;
+  int max_hard = FT8_LDPC_N;
+  RetryScratch lists;
+  DevBuf amax, plain;
+  struct View : RetryView { double* amax; uint8_t* plain; };
+  int ensure(ft8_ctx* c, size_t n_slots, int N) {
+    int rc = lists.ensure(c, n_slots, N);
+    if (!rc) rc = ::ensure(c, amax, sizeof(double) * n_slots * N);
+    if (!rc) rc = ::ensure(c, plain, (size_t)FT8_LDPC_N * n_slots * N);
+    return rc;
+  }
+  View at(const RetryLists& in, int slot0) const {
+    const size_t r0 = (size_t)slot0 * lists.M;
+    return {lists.at(in, slot0), amax.as<double>() + r0, plain.as<uint8_t>() + (size_t)FT8_LDPC_N * r0};
+  }
+};
+
+// coherent re-demodulation (ft8_set_coherent, _drift, _nsym): the per-slot cap (0: every failed
+// candidate), the drift search (off: 0, 1) and the set count (off: 1); lists of the cap with nsym sets,
+// and per list position a fit, the winning rate (drift search only) and the validity byte (nsym > 1 only)
+struct CoherentRetry {
+  int max = 0, drift_n = 1, nsym = 1;
+  float drift_rate = 0.f;
+  RetryScratch lists;
+  DevBuf fit, drift, valid;
+  struct View : RetryView {  // llr / res: set 0; set n is n * set_stride doubles / n * n_all records further
+    ft8_coh_fit* fit;
+    ft8_coh_drift* drift;  // null without the drift search
+    uint8_t* valid;        // null with one set
+    int nsym;
+    size_t n_all;
+    int64_t set_stride;
+  };
+  bool drift_on() const { return coherent_drift_on(CohDrift{drift_rate, drift_n, nullptr}); }
+  int cap(int N) const { return max > 0 ? std::min(max, N) : N; }  // listed candidates per slot
+  int ensure(ft8_ctx* c, size_t n_slots, int N) {
+    const int M = cap(N);
+    int rc = lists.ensure(c, n_slots, M, nsym);
+    if (!rc) rc = ::ensure(c, fit, sizeof(ft8_coh_fit) * n_slots * M);
+    if (!rc && nsym > 1) rc = ::ensure(c, valid, n_slots * M);
+    if (!rc && drift_on()) rc = ::ensure(c, drift, sizeof(ft8_coh_drift) * n_slots * M);
+    return rc;
+  }
+  View at(const RetryLists& in, int slot0) const {
+    const size_t r0 = (size_t)slot0 * lists.M;
+    return {lists.at(in, slot0), fit.as<ft8_coh_fit>() + r0, drift_on() ? drift.as<ft8_coh_drift>() + r0 : nullptr,
+            nsym > 1 ? valid.as<uint8_t>() + r0 : nullptr, nsym, lists.n_all, (int64_t)(FT8_LDPC_N * lists.n_all)};
+  }
+};
+
+// a-priori retries on the coherent LLRs (ft8_set_coherent_ap; off: 0): lists of A = M * H * S attempts
+// per slot; a per (position, set), the place of every attempt, plain per attempt
+struct CoherentApRetry {
+  int on = 0;
+  RetryScratch lists;
+  DevBuf amax, where, plain;
+  struct View : RetryView { double* amax; int32_t* where; uint8_t* plain; };
+  // FT8_E_RANGE where the attempts do not fit k_bp's 32-bit item count
+  int ensure(ft8_ctx* c, size_t n_slots, int M, int H, int S) {
+    const uint64_t A = (uint64_t)M * (uint64_t)H * (uint64_t)S;
+    if (A * n_slots > (uint64_t)INT32_MAX)
+      return fail(c, FT8_E_RANGE, "coherent a-priori retries: more than 2^31 - 1 attempts");
+    int rc = lists.ensure(c, n_slots, (int)A);
+    if (!rc) rc = ::ensure(c, amax, sizeof(double) * n_slots * M * S);
+    if (!rc) rc = ::ensure(c, where, sizeof(int32_t) * n_slots * A);
+    if (!rc) rc = ::ensure(c, plain, (size_t)FT8_LDPC_N * n_slots * A);
+    return rc;
+  }
+  // the attempts of n_slots lists of M positions with S sets
+  View at(int n_slots, int M, int S, int slot0) const {
+    RetryLists in{};
+    in.n_slots = n_slots;
+    in.N = lists.M;
+    const size_t a0 = (size_t)slot0 * lists.M;
+    return {lists.at(in, slot0), amax.as<double>() + (size_t)slot0 * M * S, where.as<int32_t>() + a0,
+            plain.as<uint8_t>() + (size_t)FT8_LDPC_N * a0};
+  }
+};
+
+// ordered-statistics decoding (ft8_set_osd): the order, the per-slot cap (0: every failed candidate) and
+// the hard-error limit; lists of the cap, no LLRs or records of its own
+struct OsdRetry {
+  int order = 2, max = 0, max_hard = 36;
+  RetryScratch lists;
+  int cap(int N) const { return max > 0 ? std::min(max, N) : N; }
+  int ensure(ft8_ctx* c, size_t n_slots, int N) { return lists.ensure(c, n_slots, cap(N), 0); }
+  RetryLists at(const RetryLists& in, int slot0) const { return lists.at(in, slot0).lists; }
 };
 
 struct ft8_ctx {
@@ -203,33 +299,11 @@ struct ft8_ctx {
     int sps, bpt;
   } snr_batch{};
   DevBuf snr_A, snr_N0;
-  // a-priori decoding (ft8_set_ap): the hypotheses, the hard-error limit, and the AP pass's scratch
-  // (lists of N; amax and plain per record), sized for one ft8_decode_batch / ft8_ap_decode
-  std::vector<ft8_ap_hyp> ap_hyps;
-  int ap_max_hard = FT8_LDPC_N;
-  RetryScratch ap;
-  DevBuf ap_amax, ap_plain;
-  // coherent re-demodulation (ft8_set_coherent): the per-slot cap (0: every failed candidate) and the
-  // pass's scratch (lists of the cap; a fit per position), sized for one ft8_decode_batch
-  int coh_max = 0;
-  RetryScratch coh;
-  DevBuf coh_fit;
-  // its drift search (ft8_set_coherent_drift; off: 0, 1) and the winning rate per list position
-  float coh_drift_rate = 0.f;
-  int coh_drift_n = 1;
-  DevBuf coh_drift;
-  // its multi-symbol sets (ft8_set_coherent_nsym; off: 1) and the validity byte per list position
-  int coh_nsym = 1;
-  DevBuf coh_valid;
-  // a-priori retries on the coherent LLRs (ft8_set_coherent_ap; off: 0) and the stage's scratch: lists of
-  // M * H * S attempts per slot; a per (position, set), the place of every attempt, plain per attempt
-  int coh_ap = 0;
-  RetryScratch cohap;
-  DevBuf cohap_amax, cohap_where, cohap_plain;
-  // ordered-statistics decoding (ft8_set_osd): the order, the per-slot cap (0: every failed candidate), the
-  // hard-error limit, and the pass's lists of the cap, sized for one ft8_decode_batch
-  int osd_order = 2, osd_max = 0, osd_max_hard = 36;
-  DevBuf osd_list, osd_count, osd_cand, osd_score;
+  // the retry passes of ft8_decode_batch and their stage calls, each sized for one call
+  ApRetry ap;
+  CoherentRetry coh;
+  CoherentApRetry cohap;
+  OsdRetry osd;
   // the stream of the last entry point that enqueued work, and an event recorded on it after that
   // work (StreamOrder): a call on another stream first waits for it
   hipStream_t last_stream = nullptr;
@@ -914,41 +988,23 @@ int do_sync_select(ft8_ctx* c, const void* d_wf, int wf_f64, int n_slots, int T,
 }
 
 // ---- a-priori decoding ---------------------------------------------------------------------------
-// the AP pass's scratch for n_slots lists of N records (ft8hip.h states the sizes)
-int ensure_ap_scratch(ft8_ctx* c, size_t n_slots, int N) {
-  int rc;
-  if ((rc = c->ap.ensure(c, n_slots, N))) return rc;
-  if ((rc = ensure(c, c->ap_amax, sizeof(double) * n_slots * N))) return rc;
-  return ensure(c, c->ap_plain, (size_t)FT8_LDPC_N * n_slots * N);
-}
-
 // The AP pass over the records `failed` describes (everything but M, gate and the list arrays) and
-// llr[n_slots][N][174], the context's hypotheses one after another (ap.hip).  The pass's scratch starts
-// at slot `slot0` of the buffers ensure_ap_scratch sized, so the chunks of a pipelined batch do not
-// share any; `counter` is the k_bp claim counter the pass's launches draw their tickets from.
+// llr[n_slots][N][174], the context's hypotheses one after another (ap.hip), on the scratch of the chunk
+// that starts at slot `slot0`; `counter` is the k_bp claim counter the pass's launches draw their
+// tickets from.
 int ap_pass(ft8_ctx* c, const RetryLists& failed, const double* llr, int slot0, int max_iterations, int16_t* hard,
             int counter, hipStream_t s) {
-  const RetryView v = c->ap.at(failed, slot0);
-  const size_t r0 = (size_t)slot0 * failed.N;
-  uint8_t* plain = c->ap_plain.as<uint8_t>() + (size_t)FT8_LDPC_N * r0;
-  ApLaunch A{};
-  A.r = v.lists;
-  A.amax = c->ap_amax.as<double>() + r0;
+  const ApRetry::View v = c->ap.at(failed, slot0);
+  ApLaunch A{v.lists, llr, {}, 0, c->ap.max_hard, v.amax, v.llr, v.plain, v.res, hard};
   A.r.gate = A.amax;
-  A.llr = llr;
-  A.max_hard = c->ap_max_hard;
-  A.llr_h = v.llr;
-  A.plain = plain;
-  A.res_h = v.res;
-  A.hard = hard;
   hipError_t e = launch_ap_amax(A, s);
   if (e != hipSuccess) return hipfail(c, e, "ap launch");
-  for (size_t h = 0; h < c->ap_hyps.size(); ++h) {
-    A.hyp = c->ap_hyps[h];
+  for (size_t h = 0; h < c->ap.hyps.size(); ++h) {
+    A.hyp = c->ap.hyps[h];
     A.h = (int)h;
     if ((e = launch_retry_list(A.r, s)) != hipSuccess) return hipfail(c, e, "ap launch");
     if ((e = launch_ap_clamp(A, s)) != hipSuccess) return hipfail(c, e, "ap launch");
-    if ((e = bp_over_lists(c, A.r, v.llr, plain, v.res, max_iterations, counter, s)) != hipSuccess)
+    if ((e = bp_over_lists(c, A.r, v.llr, v.plain, v.res, max_iterations, counter, s)) != hipSuccess)
       return hipfail(c, e, "ap bp launch");
     if ((e = launch_ap_merge(A, s)) != hipSuccess) return hipfail(c, e, "ap launch");
   }
@@ -1007,28 +1063,12 @@ int check_coherent_nsym(ft8_ctx* c, int max_nsym) {
   return FT8_OK;
 }
 
-// listed candidates per slot of an FT8_FLAG_COHERENT batch
-int coherent_cap(const ft8_ctx* c, int N) { return c->coh_max > 0 ? std::min(c->coh_max, N) : N; }
-
-// the coherent pass's scratch for n_slots lists of M candidates (ft8hip.h states the sizes)
-int ensure_coh_scratch(ft8_ctx* c, size_t n_slots, int M) {
-  int rc = c->coh.ensure(c, n_slots, M, c->coh_nsym);
-  if (!rc) rc = ensure(c, c->coh_fit, sizeof(ft8_coh_fit) * n_slots * M);
-  if (!rc && c->coh_nsym > 1) rc = ensure(c, c->coh_valid, n_slots * M);
-  if (!rc && coherent_drift_on(CohDrift{c->coh_drift_rate, c->coh_drift_n, nullptr}))
-    rc = ensure(c, c->coh_drift, sizeof(ft8_coh_drift) * n_slots * M);
-  return rc;
-}
-
-// The coherent pass over the records `failed` describes, one chunk's (coherent.hip): list, k_coherent,
-// then per set k_bp over the lists and the merge, on one claim counter as ap_pass's hypotheses.  Like ap_pass, its scratch starts at slot `slot0` of the buffers
-// ensure_coh_scratch sized and `counter` is the k_bp claim counter its launch draws its tickets from.
-// L: coherent_setup's launch for the chunk's samples.
-int coherent_pass(ft8_ctx* c, CohLaunch L, const RetryLists& failed, int slot0, int max_iterations, int counter,
+// The coherent pass over one chunk, v = c->coh.at(the chunk's failed records, its first slot) (coherent.hip):
+// list, k_coherent, then per set k_bp over the lists and the merge, on one claim counter as ap_pass's
+// hypotheses.  L: coherent_setup's launch for the chunk's samples.
+int coherent_pass(ft8_ctx* c, CohLaunch L, const CoherentRetry::View& v, int max_iterations, int counter,
                   hipStream_t s) {
-  const RetryView v = c->coh.at(failed, slot0);
   const RetryLists& l = v.lists;
-  ft8_coh_fit* fit = c->coh_fit.as<ft8_coh_fit>() + (size_t)slot0 * l.M;
   hipError_t e = launch_retry_list(l, s);
   if (e != hipSuccess) return hipfail(c, e, "coherent launch");
   L.cand = l.cand;
@@ -1037,21 +1077,16 @@ int coherent_pass(ft8_ctx* c, CohLaunch L, const RetryLists& failed, int slot0, 
   L.n = l.n_slots * l.M;
   L.M = l.M;
   L.llr = v.llr;
-  L.fit = fit;
-  CohDrift G{c->coh_drift_rate, c->coh_drift_n, nullptr};
-  if (coherent_drift_on(G)) G.out = c->coh_drift.as<ft8_coh_drift>() + (size_t)slot0 * l.M;
-  // set n of the chunk's positions: n_all positions after set n - 1's, in the LLRs and in the records
-  const int S = c->coh_nsym;
-  const size_t n_all = c->coh.n_all;
-  CohMulti Ms{S, FT8_LDPC_N, (int64_t)(FT8_LDPC_N * n_all), nullptr};
-  if (S > 1) Ms.valid = c->coh_valid.as<uint8_t>() + (size_t)slot0 * l.M;
+  L.fit = v.fit;
+  const CohDrift G{c->coh.drift_rate, c->coh.drift_n, v.drift};
+  const CohMulti Ms{v.nsym, FT8_LDPC_N, v.set_stride, v.valid};
   if ((e = launch_coherent(L, G, Ms, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
-  for (int n = 0; n < S; ++n) {
-    const double* llr_n = v.llr + (size_t)n * Ms.set_stride;
-    ft8_result* res_n = v.res + (size_t)n * n_all;
+  for (int n = 0; n < v.nsym; ++n) {
+    const double* llr_n = v.llr + (size_t)n * v.set_stride;
+    ft8_result* res_n = v.res + (size_t)n * v.n_all;
     if ((e = bp_over_lists(c, l, llr_n, nullptr, res_n, max_iterations, counter, s)) != hipSuccess)
       return hipfail(c, e, "coherent bp launch");
-    const CohPass A{l, fit, res_n, G.out, Ms.valid, n};
+    const CohPass A{l, v.fit, res_n, v.drift, v.valid, n};
     if ((e = launch_coh_merge(A, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
   }
   return FT8_OK;
@@ -1060,91 +1095,125 @@ int coherent_pass(ft8_ctx* c, CohLaunch L, const RetryLists& failed, int slot0, 
 // ---- a-priori retries on the coherent LLRs ------------------------------------------------------
 // whether a batch with these flags runs the stage (ft8_set_coherent_ap)
 bool coherent_ap_on(const ft8_ctx* c, int flags) {
-  return c->coh_ap && (flags & FT8_FLAG_AP) && (flags & FT8_FLAG_COHERENT);
+  return c->cohap.on && (flags & FT8_FLAG_AP) && (flags & FT8_FLAG_COHERENT);
 }
 
-// the stage's scratch for n_slots lists of M positions, H hypotheses and S sets (ft8hip.h states the
-// sizes); FT8_E_RANGE where the attempts do not fit k_bp's 32-bit item count
-int ensure_cohap_scratch(ft8_ctx* c, size_t n_slots, int M, int H, int S) {
-  const uint64_t A = (uint64_t)M * (uint64_t)H * (uint64_t)S;
-  if (A * n_slots > (uint64_t)INT32_MAX)
-    return fail(c, FT8_E_RANGE, "coherent a-priori retries: more than 2^31 - 1 attempts");
-  int rc = c->cohap.ensure(c, n_slots, (int)A);
-  if (!rc) rc = ensure(c, c->cohap_amax, sizeof(double) * n_slots * M * S);
-  if (!rc) rc = ensure(c, c->cohap_where, sizeof(int32_t) * n_slots * A);
-  if (!rc) rc = ensure(c, c->cohap_plain, (size_t)FT8_LDPC_N * n_slots * A);
-  return rc;
+// the stage's input inside ft8_decode_batch: what the coherent pass listed in the chunk of v and left failed
+CohApLaunch coherent_ap_input(const CoherentRetry::View& v) {
+  const RetryLists& l = v.lists;  // CohApLaunch's members through set_stride, in order; H is the pass's
+  return CohApLaunch{l.res,  l.n_slots, l.N,     l.M,     0,       v.nsym,  l.list,      l.count,
+                     l.cand, l.score,   v.fit,   v.drift, v.valid, v.llr, FT8_LDPC_N,  v.set_stride};
 }
 
 // The stage over one chunk (ap.hip): A.res / n_slots / N / M / S and the coherent list, fits, validity
-// bytes, drift records and LLRs are the caller's; the hypotheses, the limit and the scratch, which starts
-// at slot `slot0` of the buffers ensure_cohap_scratch sized, are filled in here.  Five launches.
+// bytes, drift records and LLRs are the caller's; the hypotheses, the limit and the scratch of the chunk
+// that starts at slot `slot0` are filled in here.  Five launches.
 int coherent_ap_pass(ft8_ctx* c, CohApLaunch A, int slot0, int max_iterations, int counter, hipStream_t s) {
-  A.H = (int)c->ap_hyps.size();
-  for (int h = 0; h < A.H; ++h) A.hyp[h] = c->ap_hyps[h];
-  A.max_hard = c->ap_max_hard;
-  RetryLists in{};
-  in.n_slots = A.n_slots;
-  in.N = A.M * A.H * A.S;
-  const RetryView v = c->cohap.at(in, slot0);
-  const size_t a0 = (size_t)slot0 * v.lists.M;
-  uint8_t* plain = c->cohap_plain.as<uint8_t>() + (size_t)FT8_LDPC_N * a0;
-  A.amax = c->cohap_amax.as<double>() + (size_t)slot0 * A.M * A.S;
+  A.H = (int)c->ap.hyps.size();
+  for (int h = 0; h < A.H; ++h) A.hyp[h] = c->ap.hyps[h];
+  A.max_hard = c->ap.max_hard;
+  const CoherentApRetry::View v = c->cohap.at(A.n_slots, A.M, A.S, slot0);
+  A.amax = v.amax;
   A.att = v.lists;
-  A.where = c->cohap_where.as<int32_t>() + a0;
+  A.where = v.where;
   A.llr_a = v.llr;
-  A.plain = plain;
+  A.plain = v.plain;
   A.res_a = v.res;
   hipError_t e = launch_cohap_amax(A, s);
   if (e == hipSuccess) e = launch_cohap_list(A, s);
   if (e == hipSuccess) e = launch_cohap_clamp(A, s);
   if (e != hipSuccess) return hipfail(c, e, "coherent ap launch");
-  if ((e = bp_over_lists(c, A.att, v.llr, plain, v.res, max_iterations, counter, s)) != hipSuccess)
+  if ((e = bp_over_lists(c, A.att, v.llr, v.plain, v.res, max_iterations, counter, s)) != hipSuccess)
     return hipfail(c, e, "coherent ap bp launch");
   if ((e = launch_cohap_merge(A, s)) != hipSuccess) return hipfail(c, e, "coherent ap launch");
   return FT8_OK;
 }
 
 // ---- ordered-statistics decoding ----------------------------------------------------------------
-// listed candidates per slot of an FT8_FLAG_OSD batch
-int osd_cap(const ft8_ctx* c, int N) { return c->osd_max > 0 ? std::min(c->osd_max, N) : N; }
+// The OSD pass over the records `failed` describes, one chunk's (osd.hip): the list of the first M records
+// still failed, on the scratch of the chunk that starts at slot `slot0`, then k_osd on llr[n_slots][N][174].
+int osd_pass(ft8_ctx* c, const RetryLists& failed, const double* llr, int slot0, hipStream_t s) {
+  const RetryLists l = c->osd.at(failed, slot0);
+  hipError_t e = launch_retry_list(l, s);
+  if (e != hipSuccess) return hipfail(c, e, "osd launch");
+  const OsdLaunch A{l.res, llr, l.n_slots, l.N, l.M, l.list, l.count, c->osd.order, c->osd.max_hard};  // no info
+  if ((e = launch_osd(A, s)) != hipSuccess) return hipfail(c, e, "osd launch");
+  return FT8_OK;
+}
 
-// the OSD pass's scratch for n_slots lists of M candidates (ft8hip.h states the sizes)
-int ensure_osd_scratch(ft8_ctx* c, size_t n_slots, int M) {
-  const size_t n = n_slots * (size_t)M;
-  int rc = ensure(c, c->osd_list, sizeof(int32_t) * n);
-  if (!rc) rc = ensure(c, c->osd_count, sizeof(int32_t) * n_slots);
-  if (!rc) rc = ensure(c, c->osd_cand, sizeof(int32_t) * 2 * n);
-  if (!rc) rc = ensure(c, c->osd_score, sizeof(double) * n);
+// ---- the retries of ft8_decode_batch ------------------------------------------------------------
+// What the retry flags need before anything is searched.  Under FT8_FLAG_SUBTRACT without the setting that
+// lets the retries run (ft8_set_subtract) the first of AP, coherent, OSD is refused; then AP needs
+// hypotheses and the coherent pass samples it can take.
+int check_retry_flags(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int n_slots,
+                      int64_t slot_stride, const ft8_params* p) {
+  const int f = p->flags;
+  const char* refused = !(f & FT8_FLAG_SUBTRACT) || c->sub_retry ? nullptr
+                        : (f & FT8_FLAG_AP)                      ? "FT8_FLAG_AP"
+                        : (f & FT8_FLAG_COHERENT)                ? "FT8_FLAG_COHERENT"
+                        : (f & FT8_FLAG_OSD)                     ? "FT8_FLAG_OSD"
+                                                                 : nullptr;
+  if (refused) return fail(c, FT8_E_UNSUPPORTED, std::string(refused) + " with FT8_FLAG_SUBTRACT is not supported");
+  if ((f & FT8_FLAG_AP) && c->ap.hyps.empty()) return fail(c, FT8_E_ARG, "FT8_FLAG_AP without hypotheses (ft8_set_ap)");
+  if (!(f & FT8_FLAG_COHERENT)) return FT8_OK;
+  CohLaunch probe;
+  return coherent_setup(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, c->coh.nsym > 1, &probe);
+}
+
+// the scratch of every retry the flags ask for, for n_slots slots of N candidates
+int ensure_retry_scratch(ft8_ctx* c, int flags, size_t n_slots, int N) {
+  int rc = FT8_OK;
+  if (flags & FT8_FLAG_AP) rc = c->ap.ensure(c, n_slots, N);
+  if (!rc && (flags & FT8_FLAG_COHERENT)) rc = c->coh.ensure(c, n_slots, N);
+  if (!rc && coherent_ap_on(c, flags))
+    rc = c->cohap.ensure(c, n_slots, c->coh.cap(N), (int)c->ap.hyps.size(), c->coh.nsym);
+  if (!rc && (flags & FT8_FLAG_OSD)) rc = c->osd.ensure(c, n_slots, N);
   return rc;
 }
 
-// The OSD pass over the records `failed` describes, one chunk's (osd.hip): the list of the first M records
-// still failed, then k_osd on llr[n_slots][N][174].  Like ap_pass, its scratch starts at slot `slot0` of the
-// buffers ensure_osd_scratch sized.
-int osd_pass(ft8_ctx* c, RetryLists failed, const double* llr, int slot0, hipStream_t s) {
-  const int M = osd_cap(c, failed.N);
-  const size_t r0 = (size_t)slot0 * M;
-  failed.M = M;
-  failed.gate = nullptr;
-  failed.list = c->osd_list.as<int32_t>() + r0;
-  failed.count = c->osd_count.as<int32_t>() + slot0;
-  failed.cand = c->osd_cand.as<int32_t>() + 2 * r0;
-  failed.score = c->osd_score.as<double>() + r0;
-  hipError_t e = launch_retry_list(failed, s);
-  if (e != hipSuccess) return hipfail(c, e, "osd launch");
-  OsdLaunch A{};
-  A.res = failed.res;
-  A.llr = llr;
-  A.n_slots = failed.n_slots;
-  A.N = failed.N;
-  A.M = M;
-  A.list = failed.list;
-  A.count = failed.count;
-  A.order = c->osd_order;
-  A.max_hard = c->osd_max_hard;
-  if ((e = launch_osd(A, s)) != hipSuccess) return hipfail(c, e, "osd launch");
+// The retries of chunk k of n_chunks over the records `failed` describes, in order: the coherent pass on
+// the chunk's samples xs, the known bits on its LLRs of what it listed and left failed, then on the STFT
+// LLRs `llr` (the coherent pass leaves them alone) the AP pass and last, over what every other retry left
+// failed, OSD.  Each k_bp user draws its tickets from a claim counter of its own.
+int retry_passes(ft8_ctx* c, const RetryLists& failed, const double* llr, const void* xs, int dtype, int64_t n_samples,
+                 int64_t slot_stride, const ft8_params* p, int slot0, int k, int n_chunks, hipStream_t s) {
+  int rc;
+  if (p->flags & FT8_FLAG_COHERENT) {
+    CohLaunch L;
+    if ((rc = coherent_setup(c, xs, dtype, n_samples, failed.n_slots, slot_stride, p, c->coh.nsym > 1, &L))) return rc;
+    const CoherentRetry::View v = c->coh.at(failed, slot0);
+    if ((rc = coherent_pass(c, L, v, p->max_iterations, bp_counter(kChunkCoherent, k, n_chunks), s))) return rc;
+    if (coherent_ap_on(c, p->flags) &&
+        (rc = coherent_ap_pass(c, coherent_ap_input(v), slot0, p->max_iterations,
+                               bp_counter(kChunkCoherentAp, k, n_chunks), s)))
+      return rc;
+  }
+  if ((p->flags & FT8_FLAG_AP) &&
+      (rc = ap_pass(c, failed, llr, slot0, p->max_iterations, nullptr, bp_counter(kChunkAp, k, n_chunks), s)))
+    return rc;
+  if ((p->flags & FT8_FLAG_OSD) && (rc = osd_pass(c, failed, llr, slot0, s))) return rc;
   return FT8_OK;
+}
+
+// ft8_ap_decode and ft8_coherent_ap_decode: records without slot structure, one list of n, retried with the
+// context's hypotheses on n_sets LLR sets each.  The checks, the caller's claim counter, the stage's
+// scratch (`scratch`), hard = -1 throughout, then `pass`.
+template <typename Scratch, typename Pass>
+int ap_stage_call(ft8_ctx* c, const double* d_llr, int n_sets, ft8_result* d_res, int n, int16_t* d_hard, hipStream_t s,
+                  Scratch&& scratch, Pass&& pass) {
+  if (!c || n < 0 || (n > 0 && (!d_llr || !d_res))) return fail(c, FT8_E_ARG, "bad argument");
+  if (n_sets < 1 || n_sets > 3) return fail(c, FT8_E_ARG, "coherent ap: n_sets must be in [1, 3]");
+  if (c->ap.hyps.empty()) return fail(c, FT8_E_ARG, "no hypotheses set (ft8_set_ap)");
+  if (n == 0) return FT8_OK;
+  DeviceGuard dg(c->device);
+  int rc;
+  if ((rc = ensure_work(c, 1, s))) return rc;
+  if ((rc = scratch())) return rc;
+  if (d_hard) {
+    const hipError_t e = hipMemsetAsync(d_hard, 0xFF, sizeof(int16_t) * (size_t)n, s);  // -1 throughout
+    if (e != hipSuccess) return hipfail(c, e, "memset");
+  }
+  return pass();
 }
 
 int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
@@ -1163,11 +1232,9 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
   const int csz = (c->n_streams > 0 && c->chunk_slots > 0) ? c->chunk_slots : n_slots;
   const int n_chunks = (n_slots + csz - 1) / csz;
   const int n_str = (c->n_streams > 0 && n_chunks > 1) ? std::min(c->n_streams, n_chunks) : 0;
-  const bool ap = (p->flags & FT8_FLAG_AP) != 0;
-  const bool coh = (p->flags & FT8_FLAG_COHERENT) != 0;
-  const bool coh_ap = coherent_ap_on(c, p->flags);
-  const bool osd = (p->flags & FT8_FLAG_OSD) != 0;
-  if ((rc = ensure_work(c, bp_counters(ap, coh, coh_ap, n_chunks), s))) return rc;
+  const int f = p->flags;
+  if ((rc = ensure_work(c, bp_counters(f & FT8_FLAG_AP, f & FT8_FLAG_COHERENT, coherent_ap_on(c, f), n_chunks), s)))
+    return rc;
   hipError_t e = hipSuccess;
   if (n_str > 0) {
     while ((int)c->streams.size() < n_str) {
@@ -1232,38 +1299,7 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     failed.score_in = cand_score;
     failed.n_slots = ns;
     failed.N = N;
-    if (coh) {
-      CohLaunch L;
-      if ((rc = coherent_setup(c, xs, dtype, n_samples, ns, slot_stride, p, c->coh_nsym > 1, &L))) return rc;
-      if ((rc = coherent_pass(c, L, failed, c0, p->max_iterations, bp_counter(kChunkCoherent, k, n_chunks), cs)))
-        return rc;
-      if (coh_ap) {  // the known bits on the coherent LLRs of what that pass listed and left failed
-        const RetryView v = c->coh.at(failed, c0);
-        CohApLaunch A{};
-        A.res = failed.res;
-        A.n_slots = ns;
-        A.N = N;
-        A.M = v.lists.M;
-        A.S = c->coh_nsym;
-        A.list = v.lists.list;
-        A.count = v.lists.count;
-        A.cand = v.lists.cand;
-        A.score = v.lists.score;
-        A.fit = c->coh_fit.as<ft8_coh_fit>() + (size_t)c0 * A.M;
-        if (coherent_drift_on(CohDrift{c->coh_drift_rate, c->coh_drift_n, nullptr}))
-          A.drift = c->coh_drift.as<ft8_coh_drift>() + (size_t)c0 * A.M;
-        if (A.S > 1) A.valid = c->coh_valid.as<uint8_t>() + (size_t)c0 * A.M;
-        A.llr = v.llr;
-        A.pos_stride = FT8_LDPC_N;
-        A.set_stride = (int64_t)(FT8_LDPC_N * c->coh.n_all);
-        if ((rc = coherent_ap_pass(c, A, c0, p->max_iterations, bp_counter(kChunkCoherentAp, k, n_chunks), cs)))
-          return rc;
-      }
-    }
-    if (ap && (rc = ap_pass(c, failed, B.llr_in, c0, p->max_iterations, nullptr, bp_counter(kChunkAp, k, n_chunks), cs)))
-      return rc;
-    // last: what every other retry left failed, on the STFT LLRs
-    if (osd && (rc = osd_pass(c, failed, B.llr_in, c0, cs))) return rc;
+    if ((rc = retry_passes(c, failed, B.llr_in, xs, dtype, n_samples, slot_stride, p, c0, k, n_chunks, cs))) return rc;
     CompactLaunch C{};
     C.res = B.res;
     C.cand_count = cand_count;
@@ -1282,7 +1318,8 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     if ((e = hipEventRecord(c->joins[i], c->streams[i])) != hipSuccess) return hipfail(c, e, "join");
     if ((e = hipStreamWaitEvent(s, c->joins[i], 0)) != hipSuccess) return hipfail(c, e, "join wait");
   }
-  c->replay_ok = n_chunks == 1 && !ap && !coh && !osd;  // a replayed k_bp would overwrite the rescued records
+  // a replayed k_bp would overwrite the rescued records
+  c->replay_ok = n_chunks == 1 && !(f & (FT8_FLAG_AP | FT8_FLAG_COHERENT | FT8_FLAG_OSD));
   return FT8_OK;
 }
 
@@ -1674,8 +1711,8 @@ int ft8_set_ap(ft8_ctx* c, const ft8_ap_hyp* hyps, int32_t n, int32_t max_hard_e
   if (max_hard_errors < 0 || max_hard_errors > FT8_LDPC_N) return fail(c, FT8_E_ARG, "max_hard_errors outside [0, 174]");
   for (int i = 0; i < n; ++i)
     if ((hyps[i].mask[9] | hyps[i].value[9]) & 7) return fail(c, FT8_E_ARG, "a hypothesis bit outside the 77 message bits");
-  c->ap_hyps.assign(hyps, hyps + n);
-  c->ap_max_hard = max_hard_errors;
+  c->ap.hyps.assign(hyps, hyps + n);
+  c->ap.max_hard = max_hard_errors;
   return FT8_OK;
 }
 
@@ -1683,24 +1720,16 @@ int ft8_ap_decode(ft8_ctx* c, const double* d_llr, ft8_result* d_res, int32_t n,
                   int16_t* d_hard, void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
   if (c) c->replay_ok = c->snr_ok = false;
-  if (!c || n < 0 || (n > 0 && (!d_llr || !d_res))) return fail(c, FT8_E_ARG, "bad argument");
-  if (c->ap_hyps.empty()) return fail(c, FT8_E_ARG, "no hypotheses set (ft8_set_ap)");
-  if (n == 0) return FT8_OK;
-  DeviceGuard dg(c->device);
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if ((rc = ensure_work(c, 1, s))) return rc;
-  if ((rc = ensure_ap_scratch(c, 1, n))) return rc;
-  if (d_hard) {
-    hipError_t e = hipMemsetAsync(d_hard, 0xFF, sizeof(int16_t) * (size_t)n, s);  // -1 throughout
-    if (e != hipSuccess) return hipfail(c, e, "memset");
-  }
-  // records without slot structure: one list of n, no candidate positions or scores
-  RetryLists failed{};
-  failed.res = d_res;
-  failed.n_slots = 1;
-  failed.N = n;
-  return ap_pass(c, failed, d_llr, 0, max_iterations, d_hard, bp_counter(kCallerBp, 0, 0), s);
+  return ap_stage_call(
+      c, d_llr, 1, d_res, n, d_hard, s, [&] { return c->ap.ensure(c, 1, n); },
+      [&] {  // no candidate positions or scores
+        RetryLists failed{};
+        failed.res = d_res;
+        failed.n_slots = 1;
+        failed.N = n;
+        return ap_pass(c, failed, d_llr, 0, max_iterations, d_hard, bp_counter(kCallerBp, 0, 0), s);
+      });
 }
 
 int ft8_set_osd(ft8_ctx* c, int32_t order, int32_t max_per_slot, int32_t max_hard_errors) {
@@ -1708,9 +1737,9 @@ int ft8_set_osd(ft8_ctx* c, int32_t order, int32_t max_per_slot, int32_t max_har
   if (order < 0 || order > 2) return fail(c, FT8_E_ARG, "osd: order must be in [0, 2]");
   if (max_per_slot < 0) return fail(c, FT8_E_ARG, "osd: max_per_slot must be >= 0");
   if (max_hard_errors < 0 || max_hard_errors > FT8_LDPC_N) return fail(c, FT8_E_ARG, "osd: max_hard_errors outside [0, 174]");
-  c->osd_order = order;
-  c->osd_max = max_per_slot;
-  c->osd_max_hard = max_hard_errors;
+  c->osd.order = order;
+  c->osd.max = max_per_slot;
+  c->osd.max_hard = max_hard_errors;
   return FT8_OK;
 }
 
@@ -1727,8 +1756,8 @@ int ft8_osd_decode(ft8_ctx* c, const double* d_llr, ft8_result* d_res, int32_t n
   A.llr = d_llr;
   A.n_slots = 1;
   A.N = A.M = n;
-  A.order = c->osd_order;
-  A.max_hard = c->osd_max_hard;
+  A.order = c->osd.order;
+  A.max_hard = c->osd.max_hard;
   A.info = d_info;
   A.codeword = d_codeword;
   const hipError_t e = launch_osd(A, (hipStream_t)stream);
@@ -1737,7 +1766,7 @@ int ft8_osd_decode(ft8_ctx* c, const double* d_llr, ft8_result* d_res, int32_t n
 
 int ft8_set_coherent(ft8_ctx* c, int32_t max_per_slot) {
   if (!c || max_per_slot < 0) return fail(c, FT8_E_ARG, "bad argument");
-  c->coh_max = max_per_slot;
+  c->coh.max = max_per_slot;
   return FT8_OK;
 }
 
@@ -1745,8 +1774,8 @@ int ft8_set_coherent_drift(ft8_ctx* c, float max_rate_hz_per_s, int32_t n_rates)
   if (!c) return FT8_E_ARG;
   const int rc = check_coherent_drift(c, max_rate_hz_per_s, n_rates);
   if (rc) return rc;
-  c->coh_drift_rate = max_rate_hz_per_s;
-  c->coh_drift_n = n_rates;
+  c->coh.drift_rate = max_rate_hz_per_s;
+  c->coh.drift_n = n_rates;
   return FT8_OK;
 }
 
@@ -1754,14 +1783,14 @@ int ft8_set_coherent_nsym(ft8_ctx* c, int32_t max_nsym) {
   if (!c) return FT8_E_ARG;
   const int rc = check_coherent_nsym(c, max_nsym);
   if (rc) return rc;
-  c->coh_nsym = max_nsym;
+  c->coh.nsym = max_nsym;
   return FT8_OK;
 }
 
 int ft8_set_coherent_ap(ft8_ctx* c, int32_t on) {
   if (!c) return FT8_E_ARG;
   if (on != 0 && on != 1) return fail(c, FT8_E_ARG, "coherent ap: on must be 0 or 1");
-  c->coh_ap = on;
+  c->cohap.on = on;
   return FT8_OK;
 }
 
@@ -1769,31 +1798,22 @@ int ft8_coherent_ap_decode(ft8_ctx* c, const double* d_llr, int32_t n_sets, cons
                            int32_t n, int32_t max_iterations, int16_t* d_hard, void* stream) {
   StreamOrder order_(c, (hipStream_t)stream);
   if (c) c->replay_ok = c->snr_ok = false;
-  if (!c || n < 0 || (n > 0 && (!d_llr || !d_res))) return fail(c, FT8_E_ARG, "bad argument");
-  if (n_sets < 1 || n_sets > 3) return fail(c, FT8_E_ARG, "coherent ap: n_sets must be in [1, 3]");
-  if (c->ap_hyps.empty()) return fail(c, FT8_E_ARG, "no hypotheses set (ft8_set_ap)");
-  if (n == 0) return FT8_OK;
-  DeviceGuard dg(c->device);
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if ((rc = ensure_work(c, 1, s))) return rc;
-  if ((rc = ensure_cohap_scratch(c, 1, n, (int)c->ap_hyps.size(), n_sets))) return rc;
-  if (d_hard) {
-    const hipError_t e = hipMemsetAsync(d_hard, 0xFF, sizeof(int16_t) * (size_t)n, s);  // -1 throughout
-    if (e != hipSuccess) return hipfail(c, e, "memset");
-  }
-  // records without slot structure: one list of n, position j is record j, every fit valid, no drift
-  CohApLaunch A{};
-  A.res = d_res;
-  A.n_slots = 1;
-  A.N = A.M = n;
-  A.S = n_sets;
-  A.valid = d_valid;
-  A.llr = d_llr;
-  A.pos_stride = (int64_t)n_sets * FT8_LDPC_N;
-  A.set_stride = FT8_LDPC_N;
-  A.hard = d_hard;
-  return coherent_ap_pass(c, A, 0, max_iterations, bp_counter(kCallerBp, 0, 0), s);
+  return ap_stage_call(
+      c, d_llr, n_sets, d_res, n, d_hard, s, [&] { return c->cohap.ensure(c, 1, n, (int)c->ap.hyps.size(), n_sets); },
+      [&] {  // position j is record j, every fit valid, no drift
+        CohApLaunch A{};
+        A.res = d_res;
+        A.n_slots = 1;
+        A.N = A.M = n;
+        A.S = n_sets;
+        A.valid = d_valid;
+        A.llr = d_llr;
+        A.pos_stride = (int64_t)n_sets * FT8_LDPC_N;
+        A.set_stride = FT8_LDPC_N;
+        A.hard = d_hard;
+        return coherent_ap_pass(c, A, 0, max_iterations, bp_counter(kCallerBp, 0, 0), s);
+      });
 }
 
 int ft8_coherent_llr(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
@@ -1865,20 +1885,8 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   std::string why;
   int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
   if (rc) return fail(c, rc, why);
-  if (p->flags & FT8_FLAG_AP) {  // also where there is nothing to search
-    if ((p->flags & FT8_FLAG_SUBTRACT) && !c->sub_retry)
-      return fail(c, FT8_E_UNSUPPORTED, "FT8_FLAG_AP with FT8_FLAG_SUBTRACT is not supported");
-    if (c->ap_hyps.empty()) return fail(c, FT8_E_ARG, "FT8_FLAG_AP without hypotheses (ft8_set_ap)");
-  }
-  if (p->flags & FT8_FLAG_COHERENT) {  // also where there is nothing to search
-    if ((p->flags & FT8_FLAG_SUBTRACT) && !c->sub_retry)
-      return fail(c, FT8_E_UNSUPPORTED, "FT8_FLAG_COHERENT with FT8_FLAG_SUBTRACT is not supported");
-    CohLaunch probe;
-    if ((rc = coherent_setup(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, c->coh_nsym > 1, &probe)))
-      return rc;
-  }
-  if ((p->flags & FT8_FLAG_OSD) && (p->flags & FT8_FLAG_SUBTRACT) && !c->sub_retry)  // also where there is nothing to search
-    return fail(c, FT8_E_UNSUPPORTED, "FT8_FLAG_OSD with FT8_FLAG_SUBTRACT is not supported");
+  // also where there is nothing to search
+  if ((rc = check_retry_flags(c, d_samples, dtype, n_samples, n_slots, slot_stride, p))) return rc;
   const int T = p->t_hi - p->t_lo, F = p->f_hi - p->f_lo;
   const bool f64 = is_f64_dtype(dtype);
   const int N = p->max_candidates;
@@ -1899,13 +1907,7 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   if ((rc = ensure(c, c->res_all, sizeof(ft8_result) * (size_t)n_slots * N))) return rc;
   if ((rc = ensure(c, c->llr, sizeof(double) * FT8_LDPC_N * (size_t)n_slots * N))) return rc;
   if ((rc = ensure_sel_scratch(c, n_slots, gr, N, f64))) return rc;
-  if ((p->flags & FT8_FLAG_AP) && (rc = ensure_ap_scratch(c, (size_t)n_slots, N))) return rc;
-  if ((p->flags & FT8_FLAG_COHERENT) && (rc = ensure_coh_scratch(c, (size_t)n_slots, coherent_cap(c, N))))
-    return rc;
-  if (coherent_ap_on(c, p->flags) &&
-      (rc = ensure_cohap_scratch(c, (size_t)n_slots, coherent_cap(c, N), (int)c->ap_hyps.size(), c->coh_nsym)))
-    return rc;
-  if ((p->flags & FT8_FLAG_OSD) && (rc = ensure_osd_scratch(c, (size_t)n_slots, osd_cap(c, N)))) return rc;
+  if ((rc = ensure_retry_scratch(c, p->flags, (size_t)n_slots, N))) return rc;
   if (!(p->flags & FT8_FLAG_SUBTRACT)) {
     if ((rc = decode_pass(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, d_out, d_counts, cap, s))) return rc;
     remember_snr_batch(c, p, g, n_slots, T, F, cap, f64);

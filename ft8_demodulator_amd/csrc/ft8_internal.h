@@ -293,11 +293,13 @@ struct Baseband {
   int Q;                       // decimated samples per symbol (nsps % Q == 0)
 };
 
-// ---- retry pass: the failed candidates of a chunk, tried again (ap.hip, coherent.hip) --------------
-// Both retries of ft8_decode_batch take the records plain BP left with ok == 0: launch_retry_list lists
-// them per slot in candidate order, the pass builds new LLRs for the list positions, launch_bp runs in
-// mode 0 over the compacted lists (cand / score / count as its candidate lists), and the pass's merge
-// kernel lets retry_accept rewrite the record of every attempt it accepts.
+// ---- retry pass: the failed candidates of a chunk, tried again (ap.hip, coherent.hip, osd.hip) -----
+// The four retries of ft8_decode_batch (coherent, a-priori on the coherent LLRs, a-priori, OSD, in that
+// order) take the records plain BP left with ok == 0.  launch_retry_list lists them per slot in candidate
+// order; the coherent and the AP pass build new LLRs for the list positions and launch_bp runs in mode 0
+// over the compacted lists (cand / score / count as its candidate lists); the stage on the coherent LLRs
+// lists attempts on that pass's positions (CohApLaunch) and decodes them the same way; OSD decodes the
+// listed records' own LLRs in k_osd.  Every pass accepts an attempt through retry_accept and nowhere else.
 struct RetryLists {
   ft8_result* res;             // in / out [n_slots][N]: the records plain BP wrote
   const int32_t* cand_count;   // [n_slots], null: every slot holds N records
@@ -317,7 +319,8 @@ __device__ inline int slot_count(const RetryLists& r, int slot) {
 // in candidate order; count = min(found, M)
 hipError_t launch_retry_list(const RetryLists& r, hipStream_t s);
 // an accepted attempt `got` rewrites the record it retried; pass_bits: (h + 1) << 4 for AP hypothesis
-// h, 2 for the coherent pass (6 at a drift rate other than 0, and 8 more from a multi-symbol set)
+// h, 2 for the coherent pass (6 at a drift rate other than 0, and 8 more from a multi-symbol set), both
+// for hypothesis h on the coherent LLRs, 0xF0 for OSD
 __device__ inline void retry_accept(ft8_result* rec, const ft8_result& got, int pass_bits) {
   ft8_result w = *rec;
   w.ok = 1;
@@ -331,9 +334,10 @@ __device__ inline void retry_accept(ft8_result* rec, const ft8_result& got, int 
 
 // ---- a-priori decoding (ap.hip) ----------------------------------------------------------------
 // The AP retry (ft8hip.h, "a-priori decoding"): k_ap_amax once (amax is the lists' gate), then per
-// hypothesis the list (M = N), k_ap_clamp -> llr_h, launch_bp -> plain and res_h, k_ap_merge.
+// hypothesis the list, k_ap_clamp -> llr_h, launch_bp -> plain and res_h, k_ap_merge.
 struct ApLaunch {
-  RetryLists r;
+  RetryLists r;                // M == N: k_ap_clamp and k_ap_merge index the lists with the records' stride
+                               // (launch_ap_clamp / launch_ap_merge: hipErrorInvalidValue otherwise)
   const double* llr;           // [n_slots][N][174] the LLRs plain BP consumed
   ft8_ap_hyp hyp;              // the hypothesis of this attempt, by value
   int h, max_hard;
