@@ -34,7 +34,7 @@ class ft8_params(ctypes.Structure):
                 ("max_iterations", ctypes.c_int32), ("min_score_f64", ctypes.c_int32),
                 ("min_score", ctypes.c_double), ("f_lo", ctypes.c_int32), ("f_hi", ctypes.c_int32),
                 ("t_lo", ctypes.c_int32), ("t_hi", ctypes.c_int32), ("flags", ctypes.c_int32),
-                ("reserved", ctypes.c_int32), ("sample_rate_hz", ctypes.c_double)]
+                ("protocol", ctypes.c_int32), ("sample_rate_hz", ctypes.c_double)]
 
 
 FT8HIP_ABI_VERSION = 2   # include/ft8hip.h: ft8_params carries sample_rate_hz since ABI 2

@@ -26,3 +26,4 @@ from .message import CallsignTable, hash_call, pack77, pack_telemetry, unpack77 
 from .snr import snr_reference  # noqa: E402,F401
 from .ap import ap_hypothesis, ap_index  # noqa: E402,F401
 from .coherent import coherent_index, coherent_restate, drift_index, multisymbol_index  # noqa: E402,F401
+from .ft4 import decode_ft4_message, ft4_itones  # noqa: E402,F401  (FT4: ft4.py; SlotDecoder(protocol="ft4"))

@@ -327,3 +327,99 @@ def stft(wave_data, sample_rate, bins_per_tone, steps_per_symbol, f_lo=None, f_h
                              _lib.stream_handle(x.device))
     ctx.check(rc, "ft8_stft")
     return out, plan, f64
+
+
+# ---- FT4 stage calls (ft4.py restates each of them) ---------------------------------------------------
+def _wf_slots(wf):
+    """A waterfall [T, F] or [n_slots, T, F] (time-major, NumPy or a GPU tensor) -> (device tensor
+    [n_slots, T, F], is float64)."""
+    torch = _lib.require_gpu()
+    t = wf if isinstance(wf, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(wf))
+    if t.dtype not in (torch.float32, torch.float64):
+        t = t.to(torch.float64)
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    return t.cuda().contiguous(), t.dtype == torch.float64
+
+
+def ft4_stft(samples, sample_rate=12000, bins_per_tone=2, steps_per_symbol=2, code=None):
+    """ft8_stft with FT8_PROTO_FT4: samples [n_slots, n] (NumPy, or a GPU tensor with its ft8 dtype code) ->
+    (waterfall tensor [n_slots, T, F] on the device, plan)."""
+    torch = _lib.require_gpu()
+    from ._pipeline import device_samples, make_params, make_plan
+    x = samples
+    if code is None:
+        x, code, _ = device_samples(samples, int16_is_pcm=True)
+    if x.dim() == 1:
+        x = x.unsqueeze(0)
+    x = x.contiguous()
+    n_slots, n = int(x.shape[0]), int(x.shape[1])
+    plan = make_plan(n, sample_rate, bins_per_tone, steps_per_symbol, protocol="ft4")
+    ctx = _lib.context(x.device)
+    p = make_params(plan, 0, 0, 0)
+    f64 = code in (_lib.FT8_F64, _lib.FT8_C128)
+    out = torch.empty(n_slots, plan.T, plan.F, dtype=torch.float64 if f64 else torch.float32, device=x.device)
+    ctx.check(_lib.lib().ft8_stft(ctx.handle, _lib.ptr(x), int(code), n, n_slots, n, ctypes.byref(p), _lib.ptr(out),
+                                  _lib.stream_handle(x.device)), "ft8_stft")
+    return out, plan
+
+
+def ft4_sync_select(wf, sps, bpt, max_candidates, min_score, flags=0, want_grid=False):
+    """ft8_sync_select with FT8_PROTO_FT4 on wf [n_slots, T, F] -> (per slot [(abs_time, abs_freq, score)],
+    score grids [n_slots, NT, NF] or None, warning flags [n_slots])."""
+    torch = _lib.require_gpu()
+    from ._pipeline import min_score_is_f64
+    from .ft4 import ft4_grid_shape
+    ctx = _lib.context()
+    d, f64 = _wf_slots(wf)
+    S, T, F = (int(v) for v in d.shape)
+    N = int(max_candidates)
+    _, NT, NF = ft4_grid_shape(T, F, sps, bpt)
+    p = _lib.Ft8Params()
+    p.protocol, p.flags, p.sample_rate = _lib.FT8_PROTO_FT4, int(flags), 1
+    p.bins_per_tone, p.steps_per_symbol, p.max_candidates = int(bpt), int(sps), N
+    p.min_score_f64, p.min_score = int(min_score_is_f64(min_score)), float(min_score)
+    cand = torch.zeros(S * max(N, 1) * 2, dtype=torch.int32, device=d.device)
+    cs = torch.zeros(S * max(N, 1), dtype=torch.float64, device=d.device)
+    cnt = torch.zeros(S, dtype=torch.int32, device=d.device)
+    grid = torch.empty(max(S * NT * NF, 1), dtype=d.dtype, device=d.device) if want_grid else None
+    ctx.check(_lib.lib().ft8_sync_select(ctx.handle, _lib.ptr(d), int(f64), S, T, F, ctypes.byref(p), _lib.ptr(cand),
+                                         _lib.ptr(cs), _lib.ptr(cnt), _lib.ptr(grid) if want_grid else None,
+                                         _lib.stream_handle()), "ft8_sync_select")
+    warn = torch.zeros(S, dtype=torch.int32, device=d.device)
+    if NT > 0 and NF > 0 and N > 0:
+        ctx.check(_lib.lib().ft8_select_warnings(ctx.handle, _lib.ptr(warn), S, _lib.stream_handle()),
+                  "ft8_select_warnings")
+    c = cand.cpu().numpy().reshape(S, max(N, 1), 2)
+    s = cs.cpu().numpy().reshape(S, max(N, 1))
+    k = cnt.cpu().numpy()
+    out = [[(int(c[b, i, 0]), int(c[b, i, 1]), float(s[b, i])) for i in range(int(k[b]))] for b in range(S)]
+    g = grid[: S * NT * NF].cpu().numpy().reshape(S, NT, NF) if want_grid else None
+    return out, g, warn.cpu().numpy()
+
+
+def ft4_llr(wf, sps, bpt, cand_list, normalize=True):
+    """ft8_ft4_llr: wf [n_slots, T, F], cand_list [(slot, abs_time, abs_freq)] -> LLRs [n, 174] (float64)."""
+    torch = _lib.require_gpu()
+    ctx = _lib.context()
+    d, f64 = _wf_slots(wf)
+    n = len(cand_list)
+    if n == 0:
+        return np.zeros((0, 174))
+    c = torch.tensor([[int(s), int(a), int(b)] for s, a, b in cand_list], dtype=torch.int32, device=d.device)
+    out = torch.empty(n, 174, dtype=torch.float64, device=d.device)
+    ctx.check(_lib.lib().ft8_ft4_llr(ctx.handle, _lib.ptr(d), int(f64), int(d.shape[1]), int(d.shape[2]), int(sps),
+                                     int(bpt), _lib.ptr(c), n, int(bool(normalize)), _lib.ptr(out),
+                                     _lib.stream_handle()), "ft8_ft4_llr")
+    return out.cpu().numpy()
+
+
+def ft4_unscramble(records):
+    """ft8_ft4_unscramble on a copy of `records` (_lib.RESULT_DTYPE) -> the updated records."""
+    torch = _lib.require_gpu()
+    ctx = _lib.context()
+    rec = np.ascontiguousarray(np.asarray(records, dtype=_lib.RESULT_DTYPE).reshape(-1))
+    n = len(rec)
+    res = torch.from_numpy(np.concatenate([rec.view(np.uint8), np.zeros(8, np.uint8)])).cuda()
+    ctx.check(_lib.lib().ft8_ft4_unscramble(ctx.handle, _lib.ptr(res), n, _lib.stream_handle()), "ft8_ft4_unscramble")
+    return res.cpu().numpy()[: n * _lib.RESULT_DTYPE.itemsize].view(_lib.RESULT_DTYPE).copy()

@@ -18,6 +18,8 @@ FT8_F32, FT8_F64, FT8_C64, FT8_C128, FT8_I16 = 0, 1, 2, 3, 4
 FT8_OK, FT8_E_ARG, FT8_E_HIP, FT8_E_UNSUPPORTED, FT8_E_NOMEM, FT8_E_RANGE = 0, -1, -2, -3, -4, -5
 FT8_FLAG_TOPK, FT8_FLAG_SUBTRACT, FT8_FLAG_AP, FT8_FLAG_COHERENT, FT8_FLAG_OSD = 1, 2, 4, 8, 16
 FT8_AP_MAX_HYP = 8
+FT8_PROTO_FT8, FT8_PROTO_FT4 = 0, 1
+FT8_FT4_SYMBOLS = 103
 FT8_SUBTRACT_MAX_PASSES = 4
 FT8_TX_PROTOCOL, FT8_TX_REFERENCE = 0, 1
 FT8_STFT_STOCKHAM, FT8_STFT_PACKED3840, FT8_STFT_CHIRPZ, FT8_STFT_DFT = 0, 1, 2, 3
@@ -36,7 +38,7 @@ class Ft8Params(ctypes.Structure):
                 ("max_iterations", ctypes.c_int32), ("min_score_f64", ctypes.c_int32),
                 ("min_score", ctypes.c_double), ("f_lo", ctypes.c_int32), ("f_hi", ctypes.c_int32),
                 ("t_lo", ctypes.c_int32), ("t_hi", ctypes.c_int32), ("flags", ctypes.c_int32),
-                ("reserved", ctypes.c_int32), ("sample_rate_hz", ctypes.c_double)]
+                ("protocol", ctypes.c_int32), ("sample_rate_hz", ctypes.c_double)]
 
 
 class Ft8DriftParams(ctypes.Structure):
@@ -193,6 +195,11 @@ def lib():
             "ft8_subtract_counts": ([vp, vp, i32, i32, vp], ctypes.c_int),
             "ft8_set_osd": ([vp, i32, i32, i32], ctypes.c_int),
             "ft8_osd_decode": ([vp, vp, vp, i32, vp, vp, vp], ctypes.c_int),
+            "ft8_geometry_proto": ([i32, dbl, i32, i32, i64, vp, vp, vp, vp], ctypes.c_int),
+            "ft8_ft4_llr": ([vp, vp, ctypes.c_int, i32, i32, i32, i32, vp, i32, ctypes.c_int, vp, vp], ctypes.c_int),
+            "ft8_ft4_unscramble": ([vp, vp, i32, vp], ctypes.c_int),
+            "ft8_ft4_encode": ([vp, vp, i32, vp, vp, vp, vp], ctypes.c_int),
+            "ft8_ft4_synthesize": ([vp, vp, vp, i32, i32, vp, ctypes.c_int, i64, i32, i64, vp], ctypes.c_int),
         }
         stale_ok = os.environ.get("FT8HIP_ALLOW_STALE") == "1"
         for name, (args, res) in sig.items():
@@ -214,8 +221,8 @@ def lib():
 
 # csrc files hashed into FT8_BUILD_ID, in the Makefile's ID_FILES order
 _ID_FILES = ("capi.hip", "stft.hip", "stft3840.hip", "sync.hip", "bp.hip", "tx.hip", "subtract.hip", "drift.hip",
-             "msg.hip", "snr.hip", "ap.hip", "coherent.hip", "osd.hip", "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "baseband.h", "heap_replay.h", "msg77.h",
-             "div_shared.h",
+             "msg.hip", "snr.hip", "ap.hip", "coherent.hip", "osd.hip", "ft4.hip", "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "baseband.h", "heap_replay.h", "msg77.h",
+             "div_shared.h", "ft4_device.h", "llr_shared.h", "score_shared.h",
              "../../include/ft8hip.h",
              "Makefile")
 
@@ -247,7 +254,8 @@ EXPORTED_SYMBOLS = (
     "ft8_set_ap", "ft8_ap_decode", "ft8_set_coherent", "ft8_coherent_llr",
     "ft8_set_coherent_drift", "ft8_coherent_drift_llr", "ft8_set_coherent_nsym", "ft8_coherent_nsym_llr",
     "ft8_set_subtract", "ft8_subtract_counts", "ft8_set_coherent_ap", "ft8_coherent_ap_decode",
-    "ft8_set_osd", "ft8_osd_decode")
+    "ft8_set_osd", "ft8_osd_decode",
+    "ft8_geometry_proto", "ft8_ft4_llr", "ft8_ft4_unscramble", "ft8_ft4_encode", "ft8_ft4_synthesize")
 
 
 def limits():
@@ -265,12 +273,19 @@ def sample_rate_hz(sample_rate) -> float:
     return fs
 
 
-def geometry(sample_rate, bins_per_tone: int, steps_per_symbol: int, n_samples: int):
+def geometry(sample_rate, bins_per_tone: int, steps_per_symbol: int, n_samples: int, protocol: int = FT8_PROTO_FT8):
     """(nperseg, hop, nfft, frames) of calculate_spectrogram (spectrogram_analyse.py:31-43), computed
-    by the library from the float sample rate."""
+    by the library from the float sample rate; protocol FT8_PROTO_FT4: the FT4 geometry (ft8_geometry_proto;
+    NotImplementedError for a sample rate FT4 does not take)."""
     v = [ctypes.c_int32() for _ in range(4)]
-    rc = lib().ft8_geometry_hz(sample_rate_hz(sample_rate), int(bins_per_tone), int(steps_per_symbol),
-                               int(n_samples), *[ctypes.byref(x) for x in v])
+    if protocol != FT8_PROTO_FT8:
+        rc = lib().ft8_geometry_proto(int(protocol), sample_rate_hz(sample_rate), int(bins_per_tone),
+                                      int(steps_per_symbol), int(n_samples), *[ctypes.byref(x) for x in v])
+        if rc == FT8_E_UNSUPPORTED:
+            raise NotImplementedError("FT4 needs a sample rate whose 0.048-s symbol is a whole number of samples")
+    else:
+        rc = lib().ft8_geometry_hz(sample_rate_hz(sample_rate), int(bins_per_tone), int(steps_per_symbol),
+                                   int(n_samples), *[ctypes.byref(x) for x in v])
     if rc != FT8_OK:
         raise ValueError("invalid spectrogram geometry (nfft must be greater than or equal to nperseg, "
                          "positive sample rate and oversampling factors)")

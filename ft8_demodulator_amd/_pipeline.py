@@ -39,6 +39,7 @@ class Plan:
     t_hi: int
     f: np.ndarray  # kept frequencies (Hz)
     t: np.ndarray  # kept frame-centre times (s)
+    protocol: int = _lib.FT8_PROTO_FT8  # FT8_PROTO_FT4: the FT4 geometry and receive path (ft4.py)
 
     @property
     def empty(self) -> bool:
@@ -62,11 +63,14 @@ def spectrogram_axes(sample_rate, nperseg, hop, nfft, n_samples):
 
 
 def make_plan(n_samples, sample_rate, bins_per_tone=2, steps_per_symbol=2, freq_min=None, freq_max=None,
-              time_min=None, time_max=None) -> Plan:
-    nperseg, hop, nfft, frames = _lib.geometry(sample_rate, bins_per_tone, steps_per_symbol, n_samples)
+              time_min=None, time_max=None, protocol="ft8") -> Plan:
+    from .ft4 import protocol_code
+    proto = protocol_code(protocol)
+    nperseg, hop, nfft, frames = _lib.geometry(sample_rate, bins_per_tone, steps_per_symbol, n_samples, proto)
     if frames == 0:  # len(wave_data) < nperseg: empty spectrogram (spectrogram_analyse.py:37-39)
         z = np.zeros(0)
-        return Plan(sample_rate, bins_per_tone, steps_per_symbol, n_samples, nperseg, hop, nfft, 0, 0, 0, 0, 0, z, z)
+        return Plan(sample_rate, bins_per_tone, steps_per_symbol, n_samples, nperseg, hop, nfft, 0, 0, 0, 0, 0, z, z,
+                    proto)
     f_all, t = spectrogram_axes(sample_rate, nperseg, hop, nfft, n_samples)
     npos = (nfft + 1) // 2            # fftshift then f >= 0 keeps natural bins 0..npos-1
     f = f_all[:npos]
@@ -83,7 +87,7 @@ def make_plan(n_samples, sample_rate, bins_per_tone=2, steps_per_symbol=2, freq_
         idx = np.nonzero((t >= lo) & (t <= hi))[0]
         t_lo, t_hi = (int(idx[0]), int(idx[-1]) + 1) if idx.size else (0, 0)
     return Plan(sample_rate, bins_per_tone, steps_per_symbol, n_samples, nperseg, hop, nfft, frames,
-                f_lo, f_hi, t_lo, t_hi, f[f_lo:f_hi], t[t_lo:t_hi])
+                f_lo, f_hi, t_lo, t_hi, f[f_lo:f_hi], t[t_lo:t_hi], proto)
 
 
 def min_score_is_f64(min_score) -> bool:
@@ -107,6 +111,7 @@ def make_params(plan: Plan, max_candidates, min_score, max_iterations, flags=0) 
     p.min_score = float(min_score)
     p.f_lo, p.f_hi, p.t_lo, p.t_hi = plan.f_lo, plan.f_hi, plan.t_lo, plan.t_hi
     p.flags = int(flags)
+    p.protocol = int(plan.protocol)
     return p
 
 
@@ -166,9 +171,19 @@ def record_columns(recs: np.ndarray, sample_rate, bins_per_tone: int, wf_f64: bo
     return tsec, fhz, recs["score"].astype(np.float64 if wf_f64 else np.float32)
 
 
-def records_to_results(recs: np.ndarray, sample_rate: int, bins_per_tone: int, wf_f64: bool):
+def ft4_record_columns(recs: np.ndarray, plan: "Plan", wf_f64: bool):
+    """record_columns for FT4 records: time_s = (t_lo + abs_time) hop / fs, the start of symbol 0, and
+    freq_hz = (f_lo + abs_freq) fs / nfft, the frequency of tone 0."""
+    fs = float(plan.sample_rate)
+    tsec = [(plan.t_lo + t) * plan.hop / fs for t in recs["abs_time"].tolist()]
+    fhz = [(plan.f_lo + f) * fs / plan.nfft for f in recs["abs_freq"].tolist()]
+    return tsec, fhz, recs["score"].astype(np.float64 if wf_f64 else np.float32)
+
+
+def records_to_results(recs: np.ndarray, sample_rate: int, bins_per_tone: int, wf_f64: bool, protocol="ft8", plan=None):
     """Device records (ok only, candidate order) -> [(FT8Message, FT8DecodeStatus, time_sec,
     freq_hz, score)] exactly as decode_ft8_message returns them (ft8_decode.py:383-391).
+    protocol "ft4" (with the decoder's plan): time and frequency are ft4_record_columns'.
 
     time_sec, freq_hz (Python floats) and score (the waterfall dtype's NumPy scalar) are
     record_columns': columns are converted once per call (the per-record work is only the object
@@ -181,6 +196,9 @@ def records_to_results(recs: np.ndarray, sample_rate: int, bins_per_tone: int, w
     crc_e = recs["crc_extracted"].tolist()
     errs = recs["ldpc_errors"].tolist()
     tsec, fhz, sc = record_columns(recs, sample_rate, bins_per_tone, wf_f64)
+    from .ft4 import protocol_code
+    if protocol_code(protocol) == _lib.FT8_PROTO_FT4:
+        tsec, fhz, sc = ft4_record_columns(recs, plan, wf_f64)
     out = []
     for i in range(n):
         msg = FT8Message(payload=bytearray(payload[10 * i: 10 * i + 10]), hash=crc_c[i])
@@ -228,7 +246,7 @@ class SlotDecoder:
                  min_score=10, max_iterations=20, freq_min=None, freq_max=None, time_min=None,
                  time_max=None, device=None, flags=0, max_results_per_slot=None, context=None, ap=None,
                  ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1, subtract=None,
-                 coherent_ap=False, osd=None, osd_max_hard_errors=None):
+                 coherent_ap=False, osd=None, osd_max_hard_errors=None, protocol="ft8"):
         """subtract: True or a pass count in [2, 4] (True: 2) -- sets FT8_FLAG_SUBTRACT: what each pass decodes is
         subtracted and the residual decoded again, that many passes in all, every pass with the ap / coherent
         retries asked for below (ft8_set_subtract(n, 1)); the default capacity holds n * max_candidates rows.
@@ -258,6 +276,15 @@ class SlotDecoder:
         from . import coherent as _coh
         from . import osd as _osd
         from . import subtract as _sub
+        from .ft4 import protocol_code
+        # protocol: "ft8" or "ft4" (ft4.py; decode, records, texts, messages, ap= and osd= work for FT4)
+        self.protocol = protocol_code(protocol)
+        if self.protocol == _lib.FT8_PROTO_FT4:
+            off = [n for n, v in (("coherent", coherent), ("subtract", subtract), ("coherent_drift", coherent_drift),
+                                  ("coherent_ap", coherent_ap)) if v not in (None, False)]
+            if off or coherent_nsym != 1 or flags & (_lib.FT8_FLAG_COHERENT | _lib.FT8_FLAG_SUBTRACT):
+                raise NotImplementedError("FT4 has no coherent re-demodulation and no subtraction yet: "
+                                          + ", ".join(off or ["flags"]) + " is not available with protocol='ft4'")
         self.osd = _osd.parse_option(osd)   # ValueError for what the library refuses
         self.osd_max_hard_errors = _osd.check_max_hard_errors(
             _osd.DEFAULT_MAX_HARD_ERRORS if osd_max_hard_errors is None else osd_max_hard_errors)
@@ -295,7 +322,8 @@ class SlotDecoder:
                 raise ValueError(f"ap takes 1..{_lib.FT8_AP_MAX_HYP} patterns")
             flags |= _lib.FT8_FLAG_AP
         self.kw = dict(sample_rate=sample_rate, bins_per_tone=bins_per_tone, steps_per_symbol=steps_per_symbol,
-                       freq_min=freq_min, freq_max=freq_max, time_min=time_min, time_max=time_max)
+                       freq_min=freq_min, freq_max=freq_max, time_min=time_min, time_max=time_max,
+                       protocol=self.protocol)
         self.max_candidates = int(max_candidates)
         self.min_score = min_score
         self.max_iterations = int(max_iterations)
@@ -416,6 +444,8 @@ class SlotDecoder:
         stream with no host sync in between; only then the copies to the host and the truncation
         warning: -> (records, ft8_text records, ft8_snr_rec records), each a list per slot, aligned,
         or None where it was not asked for."""
+        if snr and self.protocol == _lib.FT8_PROTO_FT4:
+            raise NotImplementedError("the signal report (snr, reports) is not available with protocol='ft4' yet")
         out, counts = self.run(samples, code, int16_is_pcm)
         n_slots = int(counts.shape[0])
         d_text = d_snr = None
@@ -442,7 +472,8 @@ class SlotDecoder:
         """-> list (per slot) of the reference's 5-tuples."""
         x, code, wf_f64 = device_samples(samples, self.device, int16_is_pcm=int16_is_pcm)
         per_slot = self.records(x, code)
-        return [records_to_results(r, self.kw["sample_rate"], self.kw["bins_per_tone"], wf_f64) for r in per_slot]
+        return [records_to_results(r, self.kw["sample_rate"], self.kw["bins_per_tone"], wf_f64, self.protocol,
+                                   self.plan(int(x.shape[-1]))) for r in per_slot]
 
     def texts(self, samples, code=None, int16_is_pcm=True):
         """Synchronous: -> list (per slot) of ft8_text arrays (_lib.TEXT_DTYPE) aligned with records():
@@ -464,7 +495,10 @@ class SlotDecoder:
         recs, txts, reps = self._fetch(x, code, text=True, snr=snr)
         out = []
         for s, (r, t) in enumerate(zip(recs, txts)):
-            tsec, fhz, sc = record_columns(r, self.kw["sample_rate"], self.kw["bins_per_tone"], wf_f64)
+            if self.protocol == _lib.FT8_PROTO_FT4:
+                tsec, fhz, sc = ft4_record_columns(r, self.plan(int(x.shape[-1])), wf_f64)
+            else:
+                tsec, fhz, sc = record_columns(r, self.kw["sample_rate"], self.kw["bins_per_tone"], wf_f64)
             db = snr_db_or_nan(reps[s]) if snr else None
             rows = []
             for i in range(len(r)):
@@ -506,7 +540,7 @@ def decode_slots(samples, sample_rate=12000, **kwargs):
 def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_candidates=20, min_score=10,
                max_iterations=20, freq_min=None, freq_max=None, time_min=None, time_max=None, *, flags=0, snr=False,
                ap=None, ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1, subtract=None,
-               pass_counts=False, coherent_ap=False, osd=None, osd_max_hard_errors=None):
+               pass_counts=False, coherent_ap=False, osd=None, osd_max_hard_errors=None, protocol="ft8"):
     """One slot, x [N] on the GPU with its ft8 dtype code, through a SlotDecoder of its own:
     -> (decode_ft8_message's 5-tuples, with snr the ft8_snr_rec records aligned with them else None,
     the ft8_result records) and, with pass_counts (a subtract decode), the slot's row of
@@ -515,16 +549,16 @@ def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_ca
     recs, reps = np.zeros(0, _lib.RESULT_DTYPE), np.zeros(0, _lib.SNR_DTYPE) if snr else None
     per_pass = np.zeros(0, np.int32)
     plan = make_plan(int(x.shape[0]), sample_rate, bins_per_tone, steps_per_symbol, freq_min, freq_max, time_min,
-                     time_max)
+                     time_max, protocol)
     if not plan.empty and max_candidates > 0:
         dec = SlotDecoder(sample_rate, bins_per_tone, steps_per_symbol, max_candidates, min_score, max_iterations,
                           freq_min, freq_max, time_min, time_max, device=x.device, flags=flags, ap=ap,
                           ap_max_hard_errors=ap_max_hard_errors, coherent=coherent, coherent_drift=coherent_drift,
                           coherent_nsym=coherent_nsym, subtract=subtract, coherent_ap=coherent_ap, osd=osd,
-                          osd_max_hard_errors=osd_max_hard_errors)
+                          osd_max_hard_errors=osd_max_hard_errors, protocol=protocol)
         recs, _, reps = (v if v is None else v[0] for v in dec._fetch(x.unsqueeze(0), code, snr=snr))
         if pass_counts:
             per_pass = dec.pass_counts()[0]
     wf_f64 = code in (_lib.FT8_F64, _lib.FT8_C128)
-    out = records_to_results(recs, sample_rate, bins_per_tone, wf_f64), reps, recs
+    out = records_to_results(recs, sample_rate, bins_per_tone, wf_f64, protocol, plan), reps, recs
     return out + (per_pass,) if pass_counts else out

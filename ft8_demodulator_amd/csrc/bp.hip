@@ -25,6 +25,7 @@
 #include "div_shared.h"
 #include "ft8_internal.h"
 #include "heap_replay.h"
+#include "llr_shared.h"
 
 namespace ft8 {
 namespace {
@@ -94,28 +95,6 @@ constexpr double kClip2 = 2.0 * 4.97;  // exact: twice fast_tanh's clip bound
 // LDS address-space view of a byte address (the product-factor reads compute raw LDS addresses)
 typedef __attribute__((address_space(3))) const double lds_f64;
 typedef __attribute__((address_space(3))) const uint64_t lds_u64;
-
-// correctly rounded sqrt (math.sqrt): hardware estimate + Tuckerman's test with exact fma residuals
-__device__ double sqrt_rn(double x) {
-  double y = __builtin_sqrt(x);
-  if (!(x > 0.0) || __builtin_isinf(x)) return y;
-  for (int it = 0; it < 4; ++it) {
-    const double lo = __longlong_as_double(__double_as_longlong(y) - 1);
-    const double hi = __longlong_as_double(__double_as_longlong(y) + 1);
-    if (__builtin_fma(y, lo, -x) >= 0.0) { y = lo; continue; }   // y*y^- >= x: too large
-    if (__builtin_fma(y, hi, -x) < 0.0) { y = hi; continue; }    // y*y^+ <  x: too small
-    break;
-  }
-  return y;
-}
-
-__device__ __forceinline__ double pymax4(double a, double b, double c, double d) {
-  double m = a;          // builtin max(): first maximum under '>'
-  m = b > m ? b : m;
-  m = c > m ? c : m;
-  m = d > m ? d : m;
-  return m;
-}
 
 // IEEE-754 double division, the exact instruction sequence hipcc emits for `x / y` on gfx950
 // (div_scale x2, rcp, two Newton steps, mul, fma, div_fmas, div_fixup), written with builtins so
@@ -521,39 +500,9 @@ __global__ __launch_bounds__(kWave) void k_tie_apply(TieArgs a, int32_t* cand, d
   }
 }
 
-constexpr int kLlrCpw = 4;                  // k_llr: candidates per wave
-constexpr int kLlrRow = FT8_LDPC_N + 2;     // LDS row of one candidate's 174 doubles (padded)
-
-// numpy pairwise sum (loops_utils.h.src) of x[u][0..174) for the wave's kLlrCpw candidates at once:
-// pw(0,80) + pw(80,94).  Lanes 16 u + l hold candidate u's 16 partial sums (l < 8: the 8
-// accumulators of [0, 80), l >= 8: those of [80, 168)), lane 16 u combines them with the tail
-// [168, 174) in numpy's order; every lane receives its candidate's sum.  (One candidate per wave,
-// as in round 4, kept 48 of the 64 lanes idle through both sums of the normalisation.)
-__device__ double pairwise174x4(const double (*x)[kLlrRow], double (*part)[16], int lane) {
-  const int u = lane >> 4, l = lane & 15;
-  const double* xu = x[u];
-  double r;
-  if (l < 8) {
-    r = xu[l];
-    for (int i = 8; i < 80; i += 8) r += xu[i + l];
-  } else {
-    const int j = l - 8;
-    r = xu[80 + j];
-    for (int i = 8; i < 88; i += 8) r += xu[80 + i + j];
-  }
-  part[u][l] = r;
-  __syncthreads();
-  double tot = 0.0;
-  if (l == 0) {
-    const double* pu = part[u];
-    const double s1 = ((pu[0] + pu[1]) + (pu[2] + pu[3])) + ((pu[4] + pu[5]) + (pu[6] + pu[7]));
-    double s2 = ((pu[8] + pu[9]) + (pu[10] + pu[11])) + ((pu[12] + pu[13]) + (pu[14] + pu[15]));
-    for (int i = 168; i < 174; ++i) s2 += xu[i];
-    tot = 0.0 + (s1 + s2);  // add.reduce starts from the identity
-  }
-  __syncthreads();
-  return __shfl(tot, lane & ~15);
-}
+// the deferred order alone, one wave per slot: for the LLR kernel that does not run it beside its own
+// workgroups (ft4.hip k_llr4); k_compact applies it as after k_llr
+__global__ __launch_bounds__(kWave) void k_tie_order(TieArgs a) { tie_order(a, blockIdx.x); }
 
 // ft8_extract_likelihood (ft8_decode.py:164-188) of the wave's candidates with the gathers spread over
 // the wave: lane 8 g + i fetches tone i of symbol 8 r + g in round r, so one load instruction covers
@@ -1396,6 +1345,12 @@ hipError_t launch_bp(const BpLaunch& L, hipStream_t s) {
 hipError_t launch_tie_apply(const TieArgs& a, int32_t* cand, double* cand_score, hipStream_t s) {
   if (a.n_slots <= 0 || !a.tie) return hipSuccess;
   hipLaunchKernelGGL(k_tie_apply, dim3(a.n_slots), dim3(kWave), 0, s, a, cand, cand_score);
+  return hipGetLastError();
+}
+
+hipError_t launch_tie_order(const TieArgs& a, hipStream_t s) {
+  if (a.n_slots <= 0 || !a.tie) return hipSuccess;
+  hipLaunchKernelGGL(k_tie_order, dim3(a.n_slots), dim3(kWave), 0, s, a);
   return hipGetLastError();
 }
 

@@ -268,6 +268,7 @@ struct ft8_ctx {
   int sub_slots = 0, sub_cap = 0;  // shape of the fits in sub_est (ft8_subtract_fits)
   // cumulative GFSK pulse of the transmit chain for one nsps (double and float)
   int gfsk_nsps = 0;
+  double gfsk_bt = 0.0;  // with gfsk_nsps the key of the tables below (FT8: 2.0, FT4: 1.0)
   DevBuf gfsk_P, gfsk_Pf;
   // frequency-drift correction: per-frame argmax, three-Costas correlation template (cached per
   // steps_per_symbol / nsync / ndata)
@@ -297,6 +298,7 @@ struct ft8_ctx {
     bool f64, subtract;
     double bw_db;  // 10 log10(enbw_hz / 2500) of the batch's geometry
     int sps, bpt;
+    bool ft4;      // an FT4 batch: the report's symbol layout is FT8's, so ft8_snr_last refuses
   } snr_batch{};
   DevBuf snr_A, snr_N0;
   // the retry passes of ft8_decode_batch and their stage calls, each sized for one call
@@ -758,6 +760,43 @@ int geometry(double fs, int bpt, int sps, int64_t n, Geo* g, std::string* why) {
   return FT8_OK;
 }
 
+// FT4's scrambling vector on the host (ft4_device.h holds the device's copy)
+constexpr uint8_t kFt4Rvec[10] = {0x4a, 0x5e, 0x89, 0xb4, 0xb0, 0x8a, 0x79, 0x55, 0xbe, 0x28};
+
+// FT4's samples per symbol, fs * 6 / 125 (T = 0.048 s), or 0 where that is no whole number >= 8
+int ft4_nsps(double fs) {
+  const double v = fs * 6.0 / 125.0;
+  return (v >= 8.0 && v < 1e9 && v == std::floor(v)) ? (int)v : 0;
+}
+
+// the geometry of a protocol (ft8hip.h, "FT4": nperseg = nsps, the reference's noverlap rule, nfft = nsps bpt)
+int geometry(int protocol, double fs, int bpt, int sps, int64_t n, Geo* g, std::string* why) {
+  if (protocol == FT8_PROTO_FT8) return geometry(fs, bpt, sps, n, g, why);
+  if (protocol != FT8_PROTO_FT4) { *why = "unknown ft8_params.protocol"; return FT8_E_ARG; }
+  if (!(fs > 0.0) || !(fs < 2e9) || bpt <= 0 || sps <= 0) { *why = "sample_rate, bins_per_tone and steps_per_symbol must be positive"; return FT8_E_ARG; }
+  const int nsps = ft4_nsps(fs);
+  if (nsps == 0) { *why = "FT4 needs a sample rate whose 0.048-s symbol is a whole number of samples (>= 8)"; return FT8_E_UNSUPPORTED; }
+  if ((int64_t)nsps * bpt > INT32_MAX) { *why = "nfft out of range"; return FT8_E_ARG; }
+  g->nperseg = nsps;
+  g->noverlap = nsps - nsps / sps;
+  if (g->noverlap >= g->nperseg) g->noverlap = g->nperseg - 1;
+  g->hop = g->nperseg - g->noverlap;
+  g->nfft = nsps * bpt;
+  g->frames = (n < g->nperseg) ? 0 : (int)((n - g->noverlap) / g->hop);
+  return FT8_OK;
+}
+int geometry(const ft8_params* p, int64_t n, Geo* g, std::string* why) {
+  return geometry(p->protocol, rate_of(p), p->bins_per_tone, p->steps_per_symbol, n, g, why);
+}
+
+// the entry points that take an ft8_params but no FT4: FT8_E_ARG for an unknown protocol, FT8_E_UNSUPPORTED
+// for FT4
+int ft8_only(ft8_ctx* c, const ft8_params* p, const char* who) {
+  if (p->protocol == FT8_PROTO_FT8) return FT8_OK;
+  if (p->protocol != FT8_PROTO_FT4) return fail(c, FT8_E_ARG, "unknown ft8_params.protocol");
+  return fail(c, FT8_E_UNSUPPORTED, std::string(who) + " does not take FT4");
+}
+
 bool is_f64_dtype(int dt) { return dt == FT8_F64 || dt == FT8_C128; }
 bool is_cplx_dtype(int dt) { return dt == FT8_C64 || dt == FT8_C128; }
 
@@ -773,7 +812,7 @@ int make_stft_launch(ft8_ctx* c, const ft8_params* p, int dtype, int64_t n_sampl
                      StftUse use, StftLaunch* L, bool* launch) {
   Geo g;
   std::string why;
-  int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
+  int rc = geometry(p, n_samples, &g, &why);
   if (rc) return fail(c, rc, why);
   if (dtype < FT8_F32 || dtype > FT8_I16) return fail(c, FT8_E_ARG, "unknown sample dtype");
   *launch = false;
@@ -827,15 +866,21 @@ int do_stft(ft8_ctx* c, const void* samples, int dtype, int64_t n_samples, int n
 struct Grid {
   int t0, NT, NF;
 };
-Grid grid_of(int T, int F, int sps, int bpt) {
-  // ft8_find_candidates ranges (ft8_decode.py:108-109)
+Grid grid_of(int T, int F, int sps, int bpt, int protocol) {
+  // ft8_find_candidates ranges (ft8_decode.py:108-109): a frame may start 10 symbols early and end 20
+  // late.  FT4: 103 symbols of 4 tones (ft8hip.h, "FT4") for FT8's 79 of 8.
+  const bool ft4 = protocol == FT8_PROTO_FT4;
   Grid g;
   const int nb = T / sps;
   g.t0 = -10 * sps;
-  const int t_end = nb * sps - sps * 59;
+  const int t_end = nb * sps - sps * (ft4 ? FT8_FT4_SYMBOLS - 20 : 59);
   g.NT = t_end > g.t0 ? t_end - g.t0 : 0;
-  g.NF = F - 7 * bpt > 0 ? F - 7 * bpt : 0;
+  const int tones = ft4 ? 3 : 7;
+  g.NF = F - tones * bpt > 0 ? F - tones * bpt : 0;
   return g;
+}
+Grid grid_of(int T, int F, const ft8_params* p) {
+  return grid_of(T, F, p->steps_per_symbol, p->bins_per_tone, p->protocol);
 }
 // score scratch per slot: elements (the full grid NT x NF, or the compact layout NT x nseg x 128)
 // and segment-mask words
@@ -878,6 +923,7 @@ SelScratch sel_scratch_at(const ft8_ctx* c, int slot0, const Grid& g, int N, boo
 // limit first, ft8_sync_select the flags (limit_first).
 int check_search_params(ft8_ctx* c, const ft8_params* p, bool limit_first) {
   if (p->steps_per_symbol <= 0 || p->bins_per_tone <= 0) return fail(c, FT8_E_ARG, "bad oversampling factors");
+  if (p->protocol != FT8_PROTO_FT8 && p->protocol != FT8_PROTO_FT4) return fail(c, FT8_E_ARG, "unknown ft8_params.protocol");
   const bool over = p->max_candidates > kMaxCandidates;
   if ((p->flags & ~(FT8_FLAG_TOPK | FT8_FLAG_SUBTRACT | FT8_FLAG_AP | FT8_FLAG_COHERENT | FT8_FLAG_OSD)) && !(limit_first && over))
     return fail(c, FT8_E_ARG, "unknown bits in ft8_params.flags");
@@ -891,7 +937,7 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
 int subtract_core(ft8_ctx* c, const void* x, int dtype, float* resid, int64_t n_samples, int n_slots,
                   int64_t x_stride, int64_t r_stride, const ft8_params* p, const ft8_result* res,
                   const int32_t* counts, int cap, hipStream_t s, const int32_t* first = nullptr, int first_stride = 0);
-int gfsk_tables(ft8_ctx* c, int nsps);
+int gfsk_tables(ft8_ctx* c, int nsps, double bt = 2.0);
 
 // the counter half of a k_bp launch: claim counter `counter` (ensure_work) and its host ticket base,
 // the work counters, the clock counters while timing is on (ft8_set_timing allocates them), and the
@@ -929,8 +975,9 @@ hipError_t bp_over_lists(ft8_ctx* c, const RetryLists& l, const double* llr_in, 
 int sync_select_core(ft8_ctx* c, const void* d_wf, int wf_f64, int n_slots, int T, int F, const ft8_params* p,
                      int32_t* cand, double* cand_score, int32_t* cand_count, const SelScratch& sc, int compact,
                      hipStream_t s) {
-  Grid g = grid_of(T, F, p->steps_per_symbol, p->bins_per_tone);
+  Grid g = grid_of(T, F, p);
   SyncLaunch L{};
+  L.protocol = p->protocol;
   L.wf = d_wf;
   L.wf_f64 = wf_f64;
   L.n_slots = n_slots;
@@ -965,7 +1012,7 @@ int do_sync_select(ft8_ctx* c, const void* d_wf, int wf_f64, int n_slots, int T,
   int rc = check_search_params(c, p, false);
   if (rc) return rc;
   const int N = p->max_candidates;
-  Grid g = grid_of(T, F, p->steps_per_symbol, p->bins_per_tone);
+  Grid g = grid_of(T, F, p);
   if (N <= 0 || g.NT == 0 || g.NF == 0 || n_slots == 0) {
     hipError_t e = hipMemsetAsync(cand_count, 0, sizeof(int32_t) * (size_t)(n_slots > 0 ? n_slots : 0), s);
     return e == hipSuccess ? FT8_OK : hipfail(c, e, "memset");
@@ -993,7 +1040,7 @@ int do_sync_select(ft8_ctx* c, const void* d_wf, int wf_f64, int n_slots, int T,
 // that starts at slot `slot0`; `counter` is the k_bp claim counter the pass's launches draw their
 // tickets from.
 int ap_pass(ft8_ctx* c, const RetryLists& failed, const double* llr, int slot0, int max_iterations, int16_t* hard,
-            int counter, hipStream_t s) {
+            int counter, hipStream_t s, int protocol = FT8_PROTO_FT8) {
   const ApRetry::View v = c->ap.at(failed, slot0);
   ApLaunch A{v.lists, llr, {}, 0, c->ap.max_hard, v.amax, v.llr, v.plain, v.res, hard};
   A.r.gate = A.amax;
@@ -1001,6 +1048,10 @@ int ap_pass(ft8_ctx* c, const RetryLists& failed, const double* llr, int slot0, 
   if (e != hipSuccess) return hipfail(c, e, "ap launch");
   for (size_t h = 0; h < c->ap.hyps.size(); ++h) {
     A.hyp = c->ap.hyps[h];
+    // FT4: the LLRs and the decoded payload are in scrambled bits, the context's hypotheses in message
+    // bits, so the launch's copy takes rvec on its value; clamp and acceptance then agree
+    if (protocol == FT8_PROTO_FT4)
+      for (int i = 0; i < 10; ++i) A.hyp.value[i] ^= kFt4Rvec[i];
     A.h = (int)h;
     if ((e = launch_retry_list(A.r, s)) != hipSuccess) return hipfail(c, e, "ap launch");
     if ((e = launch_ap_clamp(A, s)) != hipSuccess) return hipfail(c, e, "ap launch");
@@ -1025,7 +1076,9 @@ int baseband_setup(ft8_ctx* c, const void* x, int dtype, int64_t n_samples, int 
                    const ft8_params* p, const char* who, Baseband* B) {
   Geo g;
   std::string why;
-  int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
+  int rc = ft8_only(c, p, who);
+  if (rc) return rc;
+  rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
   if (rc) return fail(c, rc, why);
   if (dtype != FT8_F32 && dtype != FT8_I16)
     return fail(c, FT8_E_UNSUPPORTED, std::string(who) + " needs float32 or int16 samples");
@@ -1148,6 +1201,8 @@ int osd_pass(ft8_ctx* c, const RetryLists& failed, const double* llr, int slot0,
 int check_retry_flags(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples, int n_slots,
                       int64_t slot_stride, const ft8_params* p) {
   const int f = p->flags;
+  if (p->protocol == FT8_PROTO_FT4 && (f & FT8_FLAG_SUBTRACT))
+    return fail(c, FT8_E_UNSUPPORTED, "FT8_FLAG_SUBTRACT does not take FT4");
   const char* refused = !(f & FT8_FLAG_SUBTRACT) || c->sub_retry ? nullptr
                         : (f & FT8_FLAG_AP)                      ? "FT8_FLAG_AP"
                         : (f & FT8_FLAG_COHERENT)                ? "FT8_FLAG_COHERENT"
@@ -1189,7 +1244,8 @@ int retry_passes(ft8_ctx* c, const RetryLists& failed, const double* llr, const 
       return rc;
   }
   if ((p->flags & FT8_FLAG_AP) &&
-      (rc = ap_pass(c, failed, llr, slot0, p->max_iterations, nullptr, bp_counter(kChunkAp, k, n_chunks), s)))
+      (rc = ap_pass(c, failed, llr, slot0, p->max_iterations, nullptr, bp_counter(kChunkAp, k, n_chunks), s,
+                    p->protocol)))
     return rc;
   if ((p->flags & FT8_FLAG_OSD) && (rc = osd_pass(c, failed, llr, slot0, s))) return rc;
   return FT8_OK;
@@ -1223,7 +1279,7 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
   const bool f64 = is_f64_dtype(dtype);
   const size_t esz = f64 ? 8 : 4;
   const int N = p->max_candidates;
-  Grid gr = grid_of(T, F, p->steps_per_symbol, p->bins_per_tone);
+  Grid gr = grid_of(T, F, p);
   int rc;
 
   // slot chunks, each an independent STFT -> score/select -> LLR -> BP -> compact chain; chunks
@@ -1288,7 +1344,9 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     wire_bp_counters(c, B, bp_counter(kChunkBp, k, n_chunks), c->bp_waves);
     B.tie = sc.tie;
     B.warn = sc.warn;
-    if ((rc = timed_launch(c, kLlr, cs, "llr launch", [&] { return launch_llr(B, cs); }))) return rc;
+    const bool ft4 = p->protocol == FT8_PROTO_FT4;
+    if ((rc = timed_launch(c, kLlr, cs, "llr launch", [&] { return ft4 ? launch_llr4(B, cs) : launch_llr(B, cs); })))
+      return rc;
     if ((rc = timed_launch(c, kBp, cs, "bp launch", [&] { return launch_bp(B, cs); }))) return rc;
     // the tie order k_compact applies permutes positions, not records, so the coherent and AP passes
     // work on res_all as it is; the coherent pass leaves c->llr alone, so AP sees the STFT LLRs
@@ -1313,28 +1371,35 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     c->last_bp = B;
     c->last_compact = C;
     if ((rc = timed_launch(c, kCompact, cs, "compact launch", [&] { return launch_compact(C, cs); }))) return rc;
+    // FT4: BP, the retries and the tail worked on scrambled bits; the rows handed out carry the message
+    if (ft4 && C.out && (e = launch_ft4_unscramble(C.out, ns * cap, C.counts, cap, cs)) != hipSuccess)
+      return hipfail(c, e, "unscramble launch");
   }
   for (int i = 0; i < n_str; ++i) {
     if ((e = hipEventRecord(c->joins[i], c->streams[i])) != hipSuccess) return hipfail(c, e, "join");
     if ((e = hipStreamWaitEvent(s, c->joins[i], 0)) != hipSuccess) return hipfail(c, e, "join wait");
   }
   // a replayed k_bp would overwrite the rescued records
-  c->replay_ok = n_chunks == 1 && !(f & (FT8_FLAG_AP | FT8_FLAG_COHERENT | FT8_FLAG_OSD));
+  // (and the descramble of an FT4 batch is an involution, not idempotent)
+  c->replay_ok = n_chunks == 1 && !(f & (FT8_FLAG_AP | FT8_FLAG_COHERENT | FT8_FLAG_OSD)) && p->protocol == FT8_PROTO_FT8;
   return FT8_OK;
 }
 
 // cumulative GFSK frequency pulse P[0 .. 3 nsps] of the transmit chain (tx_device.h), double and
-// float, built once per nsps: p(i) = gauss_window_generator(2.0, (i - 1.5 nsps) / nsps)
-// (modulator.py:20-25, 33-34), P[i + 1] = P[i] + p(i)
-int gfsk_tables(ft8_ctx* c, int nsps) {
-  if (c->gfsk_nsps == nsps && c->gfsk_P.p) return FT8_OK;
+// float, built once per (nsps, BT): p(i) = gauss_window_generator(BT, (i - 1.5 nsps) / nsps)
+// (modulator.py:20-25, 33-34; BT = 2.0 for FT8, 1.0 for FT4), P[i + 1] = P[i] + p(i)
+int gfsk_tables(ft8_ctx* c, int nsps, double bt) {
+  if (c->gfsk_nsps == nsps && c->gfsk_bt == bt && c->gfsk_P.p) return FT8_OK;
+  // the tables are rewritten in place: whatever still reads the old ones (a protocol switch on one
+  // context) finishes first
+  if (c->gfsk_P.p && hipDeviceSynchronize() != hipSuccess) return fail(c, FT8_E_HIP, "gfsk table sync");
   const int n = 3 * nsps + 1;
   int rc;
   if ((rc = ensure(c, c->gfsk_P, sizeof(double) * n))) return rc;
   if ((rc = ensure(c, c->gfsk_Pf, sizeof(float) * n))) return rc;
   std::vector<double> P(n);
   std::vector<float> Pf(n);
-  const double k = M_PI * std::sqrt(2.0 / std::log(2.0)), bt = 2.0;
+  const double k = M_PI * std::sqrt(2.0 / std::log(2.0));
   P[0] = 0.0;
   for (int i = 0; i < 3 * nsps; ++i) {
     const double t = ((double)i - 1.5 * (double)nsps) / (double)nsps;
@@ -1346,6 +1411,7 @@ int gfsk_tables(ft8_ctx* c, int nsps) {
   if (e == hipSuccess) e = hipMemcpy(c->gfsk_Pf.p, Pf.data(), sizeof(float) * n, hipMemcpyHostToDevice);
   if (e != hipSuccess) return hipfail(c, e, "gfsk table upload");
   c->gfsk_nsps = nsps;
+  c->gfsk_bt = bt;
   return FT8_OK;
 }
 
@@ -1502,7 +1568,7 @@ double snr_bw_db(double fs, int nperseg) { return 10.0 * std::log10(1.5 * fs / (
 // ft8_decode_batch succeeded: c->wf holds the batch's waterfall [n_slots][T][F]
 void remember_snr_batch(ft8_ctx* c, const ft8_params* p, const Geo& g, int n_slots, int T, int F, int cap, bool f64) {
   c->snr_batch = {n_slots, T, F, cap, f64, (p->flags & FT8_FLAG_SUBTRACT) != 0, snr_bw_db(rate_of(p), g.nperseg),
-                  p->steps_per_symbol, p->bins_per_tone};
+                  p->steps_per_symbol, p->bins_per_tone, p->protocol == FT8_PROTO_FT4};
   c->snr_ok = true;
 }
 
@@ -1883,14 +1949,14 @@ int ft8_decode_batch(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_sam
   StageTimer whole(c, kDecodeBatch, s);
   Geo g;
   std::string why;
-  int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
+  int rc = geometry(p, n_samples, &g, &why);
   if (rc) return fail(c, rc, why);
   // also where there is nothing to search
   if ((rc = check_retry_flags(c, d_samples, dtype, n_samples, n_slots, slot_stride, p))) return rc;
   const int T = p->t_hi - p->t_lo, F = p->f_hi - p->f_lo;
   const bool f64 = is_f64_dtype(dtype);
   const int N = p->max_candidates;
-  Grid gr = grid_of(T > 0 ? T : 0, F > 0 ? F : 0, p->steps_per_symbol, p->bins_per_tone);
+  Grid gr = grid_of(T > 0 ? T : 0, F > 0 ? F : 0, p);
   if (T <= 0 || F <= 0 || N <= 0 || gr.NT == 0 || gr.NF == 0) {
     // nothing to search: validate the ranges, report zero decodes
     if (p->t_lo < 0 || p->t_hi > g.frames || p->f_lo < 0 || p->f_hi > g.nfft)
@@ -2003,6 +2069,95 @@ int ft8_synthesize(ft8_ctx* c, const uint8_t* d_tones, const ft8_tx_signal* d_si
   return e == hipSuccess ? FT8_OK : hipfail(c, e, "synthesize launch");
 }
 
+// ---- FT4 stage calls (ft4.hip) -----------------------------------------------------------------------
+int ft8_geometry_proto(int32_t protocol, double fs, int32_t bpt, int32_t sps, int64_t n, int32_t* nperseg,
+                       int32_t* hop, int32_t* nfft, int32_t* frames) {
+  Geo g;
+  std::string why;
+  int rc = geometry(protocol, fs, bpt, sps, n, &g, &why);
+  if (rc) return rc;
+  if (nperseg) *nperseg = g.nperseg;
+  if (hop) *hop = g.hop;
+  if (nfft) *nfft = g.nfft;
+  if (frames) *frames = g.frames;
+  return FT8_OK;
+}
+
+int ft8_ft4_llr(ft8_ctx* c, const void* d_wf, int wf_f64, int32_t T, int32_t F, int32_t sps, int32_t bpt,
+                const int32_t* d_cand, int32_t n, int normalize, double* d_llr, void* stream) {
+  if (c) c->replay_ok = c->snr_ok = false;
+  if (!c || !d_llr || (!d_cand && n > 0) || (!d_wf && n > 0) || sps <= 0 || bpt <= 0 || T < 0 || F < 0)
+    return fail(c, FT8_E_ARG, "bad argument");
+  if (n <= 0) return FT8_OK;
+  DeviceGuard dg(c->device);
+  BpLaunch L{};
+  L.wf = d_wf;
+  L.wf_f64 = wf_f64;
+  L.T = T;
+  L.F = F;
+  L.sps = sps;
+  L.bpt = bpt;
+  L.cand = d_cand;
+  L.n_items = n;
+  L.mode = 1;
+  L.normalize = normalize;
+  L.llr_out = d_llr;
+  hipStream_t s = (hipStream_t)stream;
+  return timed_launch(c, kLlr, s, "llr launch", [&] { return launch_llr4(L, s); });
+}
+
+int ft8_ft4_unscramble(ft8_ctx* c, ft8_result* d_res, int32_t n, void* stream) {
+  if (c) c->replay_ok = c->snr_ok = false;
+  if (!c || n < 0 || (n > 0 && !d_res)) return fail(c, FT8_E_ARG, "bad argument");
+  if (n == 0) return FT8_OK;
+  DeviceGuard dg(c->device);
+  hipError_t e = launch_ft4_unscramble(d_res, n, nullptr, 0, (hipStream_t)stream);
+  return e == hipSuccess ? FT8_OK : hipfail(c, e, "unscramble launch");
+}
+
+int ft8_ft4_encode(ft8_ctx* c, const uint8_t* d_msg, int32_t n, uint8_t* d_a91, uint8_t* d_codeword, uint8_t* d_tones,
+                   void* stream) {
+  if (c) c->replay_ok = c->snr_ok = false;
+  if (!c || n < 0 || (n > 0 && !d_msg)) return fail(c, FT8_E_ARG, "bad argument");
+  if (n == 0) return FT8_OK;
+  DeviceGuard dg(c->device);
+  hipError_t e = launch_ft4_encode(d_msg, n, d_a91, d_codeword, d_tones, (hipStream_t)stream);
+  return e == hipSuccess ? FT8_OK : hipfail(c, e, "encode launch");
+}
+
+int ft8_ft4_synthesize(ft8_ctx* c, const uint8_t* d_tones, const ft8_tx_signal* d_signals, int32_t n_signals,
+                       int32_t sample_rate, void* d_out, int out_dtype, int64_t n_samples, int32_t n_slots,
+                       int64_t slot_stride, void* stream) {
+  StreamOrder order_(c, (hipStream_t)stream);
+  if (c) c->replay_ok = c->snr_ok = false;
+  if (!c || n_signals < 0 || n_slots < 0 || n_samples < 0 || sample_rate <= 0) return fail(c, FT8_E_ARG, "bad argument");
+  if (out_dtype != FT8_F32 && out_dtype != FT8_F64 && out_dtype != FT8_C64 && out_dtype != FT8_C128)
+    return fail(c, FT8_E_ARG, "out_dtype must be FT8_F32, FT8_F64, FT8_C64 or FT8_C128");
+  const int nsps = ft4_nsps((double)sample_rate);
+  if (nsps == 0 || (int64_t)nsps * 105 > INT32_MAX)
+    return fail(c, FT8_E_UNSUPPORTED, "FT4 needs a sample rate whose 0.048-s symbol is a whole number of samples (>= 8)");
+  if (n_signals == 0 || n_slots == 0 || n_samples == 0) return FT8_OK;
+  if (!d_tones || !d_signals || !d_out) return fail(c, FT8_E_ARG, "null argument");
+  if (slot_stride < n_samples && n_slots > 1) return fail(c, FT8_E_ARG, "slot_stride < n_samples");
+  DeviceGuard dg(c->device);
+  int rc = gfsk_tables(c, nsps, 1.0);
+  if (rc) return rc;
+  SynthLaunch L{};
+  L.tones = d_tones;
+  L.sig = d_signals;
+  L.n_sig = n_signals;
+  L.nsps = nsps;
+  L.fs = (double)sample_rate;
+  L.P = c->gfsk_P.as<const double>();
+  L.out = d_out;
+  L.dtype = out_dtype;
+  L.n_samples = n_samples;
+  L.slot_stride = slot_stride;
+  L.n_slots = n_slots;
+  hipError_t e = launch_ft4_synth(L, (hipStream_t)stream);
+  return e == hipSuccess ? FT8_OK : hipfail(c, e, "synthesize launch");
+}
+
 int ft8_subtract(ft8_ctx* c, const void* d_samples, int dtype, float* d_residual, int64_t n_samples, int32_t n_slots,
                  int64_t slot_stride, const ft8_params* p, const ft8_result* d_res, const int32_t* d_counts, int32_t cap,
                  void* stream) {
@@ -2067,6 +2222,7 @@ int ft8_stft_argmax(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samp
   if (!c || !p || (n_slots > 0 && (!d_samples || !d_idx))) return fail(c, FT8_E_ARG, "null argument");
   if (n_slots < 0 || n_samples < 0) return fail(c, FT8_E_ARG, "negative size");
   if (n_slots > 1 && slot_stride < n_samples) return fail(c, FT8_E_ARG, "slot_stride < n_samples");
+  if (int rc = ft8_only(c, p, "ft8_stft_argmax")) return rc;
   DeviceGuard dg(c->device);
   return stft_argmax_core(c, d_samples, dtype, n_samples, n_slots, slot_stride, p, d_idx, (hipStream_t)stream);
 }
@@ -2227,7 +2383,9 @@ int ft8_snr(ft8_ctx* c, const void* d_wf, int wf_f64, int32_t n_slots, int32_t T
   if (radius < 0 || radius > 1) return fail(c, FT8_E_ARG, "radius must be 0 or 1");
   Geo g;
   std::string why;
-  int rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
+  int rc = ft8_only(c, p, "ft8_snr");
+  if (rc) return rc;
+  rc = geometry(rate_of(p), p->bins_per_tone, p->steps_per_symbol, n_samples, &g, &why);
   if (rc) return fail(c, rc, why);
   if (n_slots == 0 || cap == 0) return FT8_OK;
   if (T <= 0 || F <= 0) return fail(c, FT8_E_ARG, "empty waterfall");
@@ -2250,6 +2408,7 @@ int ft8_snr_last(ft8_ctx* c, const ft8_result* d_records, const int32_t* d_count
   if (n_slots != b.n_slots || cap != b.cap)
     return fail(c, FT8_E_ARG, "n_slots / cap differ from the last ft8_decode_batch's (" + std::to_string(b.n_slots) +
                                   " / " + std::to_string(b.cap) + ")");
+  if (b.ft4) return fail(c, FT8_E_UNSUPPORTED, "the last batch was FT4: ft8_snr_last does not take FT4");
   if (b.subtract)
     return fail(c, FT8_E_UNSUPPORTED,
                 "the last batch ran FT8_FLAG_SUBTRACT: the context holds the residual's waterfall, without the pass-1 "

@@ -177,7 +177,17 @@ __host__ __device__ inline double key_value(unsigned long long k) {
   return x.d;
 }
 
+// ft8_find_candidates' admission test (ft8_decode.py:127): not -inf and not below min_score, the
+// comparison done in the score's dtype unless min_score is a float64 scalar
+template <typename T>
+__device__ __forceinline__ bool passes(T s, double ms, int cmp_f64) {
+  if (s == (T)-INFINITY) return false;
+  if (cmp_f64) return !((double)s < ms);
+  return !(s < (T)ms);
+}
+
 struct SyncLaunch {
+  int protocol = FT8_PROTO_FT8;  // FT8_PROTO_FT4: the FT4 score kernels (ft4.hip) on the FT4 grid
   const void* wf;          // [n_slots][T][F]
   int wf_f64;
   int n_slots, T, F;
@@ -224,6 +234,11 @@ inline __host__ __device__ int n_segments(int NF) { return (NF + kSegCols - 1) /
 // whether launch_score writes the compact layout for this launch (else the full grid)
 bool score_compact(const SyncLaunch& a);
 hipError_t launch_select(const SyncLaunch& a, hipStream_t s);
+// FT4 (ft4.hip): launch_score's work for protocol FT8_PROTO_FT4 -- the same promises to launch_select (the
+// full grid or the compact segments, the masks, the summaries); score4_path: whether the tiled kernel
+// k_score4 takes the launch (the only one that writes the compact layout), else k_score4g
+bool score4_path(const SyncLaunch& a);
+hipError_t launch_score4(const SyncLaunch& a, hipStream_t s);
 // ft8_sync_score for arbitrary candidates [n][2] = (abs_time, abs_freq); err[i] = 1: IndexError
 hipError_t launch_score_list(const void* wf, int wf_f64, int T, int F, int sps, int bpt, const int32_t* cand,
                              int n, void* out, int32_t* err, hipStream_t s);
@@ -269,6 +284,13 @@ struct BpLaunch {
 };
 hipError_t launch_llr(const BpLaunch& a, hipStream_t s);  // k_llr: waterfall -> LLRs
 hipError_t launch_bp(const BpLaunch& a, hipStream_t s);   // k_bp: LLRs -> BP + CRC
+// FT4 (ft4.hip): k_llr4, launch_llr's modes 0 and 1 with the FT4 symbol layout.  It does not run the
+// deferred tie order of mode 0 beside its workgroups: launch_tie_order (bp.hip, one wave per slot) does.
+hipError_t launch_llr4(const BpLaunch& a, hipStream_t s);
+hipError_t launch_tie_order(const TieArgs& a, hipStream_t s);
+// FT4: rvec XORed onto the 77 payload bits of n records in place; with counts, res is [n / cap][cap] and
+// only the rows below min(counts[slot], cap) are touched
+hipError_t launch_ft4_unscramble(ft8_result* res, int n, const int32_t* counts, int cap, hipStream_t s);
 
 struct CompactLaunch {
   const ft8_result* res;   // [n_slots][N]
@@ -482,6 +504,10 @@ struct SynthLaunch {
 hipError_t launch_encode(const uint8_t* msg, int msg_bytes, int n, uint8_t* a91, uint8_t* cw, uint8_t* tones,
                          hipStream_t s);
 hipError_t launch_synth(const SynthLaunch& a, hipStream_t s);
+// FT4 (ft4.hip, ft4_device.h): payloads [n][10] -> a91 / codeword / tones [n][103]; the waveforms of
+// SynthLaunch with tones [n_sig][103], P the BT = 1.0 pulse table and style unused
+hipError_t launch_ft4_encode(const uint8_t* msg, int n, uint8_t* a91, uint8_t* cw, uint8_t* tones, hipStream_t s);
+hipError_t launch_ft4_synth(const SynthLaunch& a, hipStream_t s);
 
 struct SubLaunch {
   Baseband b;

@@ -36,6 +36,7 @@
 
 #include "ft8_internal.h"
 #include "heap_replay.h"
+#include "score_shared.h"
 
 namespace ft8 {
 namespace {
@@ -59,15 +60,6 @@ struct ScoreArgs {
   int cmp_f64;
   int n_slots, n_bands, n_ctiles;  // k_score2 grid
 };
-
-// ft8_find_candidates' admission test (ft8_decode.py:127): not -inf and not below min_score, the
-// comparison done in the score's dtype unless min_score is a float64 scalar
-template <typename T>
-__device__ __forceinline__ bool passes(T s, double ms, int cmp_f64) {
-  if (s == (T)-INFINITY) return false;
-  if (cmp_f64) return !((double)s < ms);
-  return !(s < (T)ms);
-}
 
 template <typename T, bool LDS, int TW>
 __global__ __launch_bounds__(kScoreThreads) void k_score(ScoreArgs a) {
@@ -183,7 +175,6 @@ constexpr int kS2R = 22;                   // grid rows per workgroup (88 = 4 x 
 constexpr int kS2Waves = 8;                // row j of the workgroup on wave j % 8
 constexpr int kS2Rows = (kS2R + kS2Waves - 1) / kS2Waves;  // rows per wave (3, the last two waves 2)
 constexpr int kS2Threads = kS2Waves * kWave;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // A workgroup's 22 grid rows are one residue class mod sps, consecutive in it: abs_time a0 +
 // sps j, j < 22.  Every waterfall row those candidates read for Costas band m is a0 + 36 m sps +
@@ -198,37 +189,6 @@ struct S2Geom {
   static constexpr int Q = P / 4;                        // float4 per staged row
   static constexpr int kIter = (H * Q + kS2Threads - 1) / kS2Threads;  // float4 staged per thread
 };
-
-// maximum over the wave (no NaN), on order-preserving integer keys (a float max would re-quiet
-// every DPP operand): rotations inside each 16-lane row (DPP row_ror 8, 4, 2, 1), then the four
-// row maxima in scalar registers -- instead of six ds_bpermute rounds
-__device__ __forceinline__ int fkey(float v) {
-  const int i = __float_as_int(v);
-  return i ^ ((i >> 31) & 0x7fffffff);
-}
-template <int CTRL>
-__device__ __forceinline__ int dpp_max(int k) {
-  return max(k, __builtin_amdgcn_mov_dpp(k, CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float wave_max(float v) {
-  int k = fkey(v);
-  k = dpp_max<0x128>(k);  // row_ror:8
-  k = dpp_max<0x124>(k);  // row_ror:4
-  k = dpp_max<0x122>(k);  // row_ror:2
-  k = dpp_max<0x121>(k);  // row_ror:1
-  const int m = max(max(__builtin_amdgcn_readlane(k, 0), __builtin_amdgcn_readlane(k, 16)),
-                    max(__builtin_amdgcn_readlane(k, 32), __builtin_amdgcn_readlane(k, 48)));
-  return __int_as_float(m ^ ((m >> 31) & 0x7fffffff));
-}
-
-// volatile LDS load: one ds_read_b64 per pair.  The compiler would otherwise merge neighbouring
-// pairs into ds_read2_b64, which moves half as many bytes per LDS cycle (measured: k_score2 0.27
-// vs 0.30 ms per 256-slot step).
-template <int BPT>
-__device__ __forceinline__ f32x2 ld2(const float* p) {
-  if constexpr (BPT % 2 == 0) return *(const volatile __attribute__((address_space(3))) f32x2*)p;
-  else return f32x2{p[0], p[1]};
-}
 
 // Costas band m of the tile (staged rows a0 - SPS + 36 m SPS + SPS u, u < H; columns [c0, c0 + P))
 // as float4 loads into registers; rows outside the waterfall / columns past F are zero and never
@@ -1387,11 +1347,13 @@ __global__ __launch_bounds__(kSelThreads) void k_topkc(SelectArgs a, int M, int 
 // the compact layout needs k_score2 (whole-segment writes); top-k selection reads it through
 // k_topkc when the slot's segment offsets fit its LDS (else k_topk on the full grid)
 bool score_compact(const SyncLaunch& L) {
-  return L.compact && score2_path(L) && (!L.topk || (int64_t)L.NT * n_segments(L.NF) <= kTkcMaxSeg);
+  const bool path = L.protocol == FT8_PROTO_FT4 ? score4_path(L) : score2_path(L);
+  return L.compact && path && (!L.topk || (int64_t)L.NT * n_segments(L.NF) <= kTkcMaxSeg);
 }
 
 hipError_t launch_score(const SyncLaunch& L, hipStream_t s) {
   if (L.NT <= 0 || L.NF <= 0 || L.n_slots <= 0) return hipSuccess;
+  if (L.protocol == FT8_PROTO_FT4) return launch_score4(L, s);
   if (L.wf_f64) return launch_score_t<double, 32>(L, s);
   return launch_score_t<float, 64>(L, s);
 }

@@ -305,6 +305,10 @@ def main(argv=None):
                         help="most hard decisions of an OSD decode that may contradict the received bits (default 36)")
     parser.add_argument("--selection", choices=("reference", "topk"), default="reference",
                         help="candidate selection: the reference's, or the max-candidates highest scores")
+    parser.add_argument("--ft4", action="store_true",
+                        help="decode FT4 instead of FT8 (build-defined, interoperability with WSJT-X unverified; "
+                             "not with --snr, --coherent, --subtract or --correction; FT4 scores are lower: "
+                             "try --min-score 4 or --selection topk --min-score 0)")
     parser.add_argument("--subtract", nargs="?", type=int, const=2, default=None, metavar="PASSES",
                         help="subtract what each pass decodes and decode the residual again, PASSES passes in all "
                              "(2 to 4, default 2), with --ap / --coherent in every pass; a decode a later pass "
@@ -319,6 +323,8 @@ def main(argv=None):
         if args.snr:
             parser.error("--subtract cannot report --snr (the waterfall left is the residual's)")
     coherent = None if args.coherent is None else (True if args.coherent < 0 else args.coherent)
+    if args.ft4 and (args.snr or args.coherent is not None or args.subtract is not None or args.correction):
+        parser.error("--ft4 takes none of --snr, --coherent, --subtract, --correction")
     if args.coherent_drift is not None and coherent is None:
         parser.error("--coherent-drift needs --coherent")
     if args.coherent_nsym is not None and coherent is None:
@@ -345,7 +351,7 @@ def main(argv=None):
               max_candidates=args.max_candidates, min_score=args.min_score, max_iterations=args.max_iterations)
     many = len(paths) > 1
     if (args.ap or args.snr or coherent is not None or args.subtract is not None or args.osd is not None
-            or args.selection != "reference"):
+            or args.selection != "reference" or args.ft4):
         # the report comes from the decode's own waterfall, an AP decode's mark from its own record:
         # one file at a time, each decoded once (lazily: a file is printed before the next is decoded)
         if args.correction:
@@ -360,6 +366,8 @@ def main(argv=None):
             kw = dict(kw, coherent_ap=True)
         if args.selection != "reference":
             kw = dict(kw, selection=args.selection)
+        if args.ft4:
+            kw = dict(kw, protocol="ft4")
         if args.subtract is not None:
             kw = dict(kw, subtract=args.subtract)
         if args.osd is not None:

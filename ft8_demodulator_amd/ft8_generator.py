@@ -51,6 +51,30 @@ def encode_batch(msgs, msg_bytes: int = 10, device=None):
     return a91, cw, tones
 
 
+def ft4_encode_batch(payloads, device=None):
+    """[n, 10] payloads, NumPy or torch -> (a91 [n, 12], codeword [n, 22], tones [n, 103]) uint8 torch tensors on
+    the GPU (ft8_ft4_encode: the payload is scrambled before CRC-14 and LDPC; ft4.py)."""
+    torch = _lib.require_gpu()
+    ctx = _lib.context(device)
+    dev = torch.device("cuda", ctx.device)
+    m = payloads if isinstance(payloads, torch.Tensor) else torch.from_numpy(np.array(payloads, dtype=np.uint8, copy=True))
+    m = m.to(device=dev, dtype=torch.uint8).reshape(-1, 10).contiguous()
+    n = m.shape[0]
+    a91 = torch.empty((n, 12), dtype=torch.uint8, device=dev)
+    cw = torch.empty((n, 22), dtype=torch.uint8, device=dev)
+    tones = torch.empty((n, _lib.FT8_FT4_SYMBOLS), dtype=torch.uint8, device=dev)
+    if n:
+        ctx.check(_lib.lib().ft8_ft4_encode(ctx.handle, _lib.ptr(m), n, _lib.ptr(a91), _lib.ptr(cw), _lib.ptr(tones),
+                                            _lib.stream_handle(dev)), "ft8_ft4_encode")
+    return a91, cw, tones
+
+
+def ft4_encode(payload) -> np.ndarray:
+    """payload -> 103 FT4 channel tones (uint8)."""
+    _, _, tones = ft4_encode_batch(_u8(payload, 10)[None, :])
+    return tones[0].cpu().numpy()
+
+
 def crc_generator(payload_10bytes) -> np.ndarray:
     """crc.py:25-47: payload (77 bits) -> a91 (12 bytes) = payload | 5 zero bits dropped | CRC-14."""
     a91, _, _ = encode_batch(_u8(payload_10bytes, 10)[None, :], 10)
@@ -76,8 +100,9 @@ def ft8_encode(payload) -> np.ndarray:
 
 
 def synthesize(tones, signals, n_slots: int, n_samples: int, sample_rate: int, style: int = _lib.FT8_TX_PROTOCOL,
-               out=None, dtype=None, device=None):
-    """Add GFSK waveforms to slots on the GPU (ft8_synthesize).
+               out=None, dtype=None, device=None, protocol="ft8"):
+    """Add GFSK waveforms to slots on the GPU (ft8_synthesize; protocol "ft4": ft8_ft4_synthesize, tones
+    [n, 103], `start` the first sample of symbol 0, style ignored).
 
     tones    [n, 79] uint8 (torch on the GPU or NumPy), signal i uses row i
     signals  NumPy array of _lib.TX_SIGNAL_DTYPE (f0, amplitude, phase, start, slot); sorted here
@@ -90,7 +115,9 @@ def synthesize(tones, signals, n_slots: int, n_samples: int, sample_rate: int, s
     dev = torch.device("cuda", ctx.device)
     sig = np.ascontiguousarray(signals, dtype=_lib.TX_SIGNAL_DTYPE).reshape(-1)
     t = tones if isinstance(tones, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tones, dtype=np.uint8))
-    t = t.to(device=dev, dtype=torch.uint8).reshape(-1, FT8_SYMBOL_NUM)
+    from .ft4 import protocol_code
+    ft4 = protocol_code(protocol) == _lib.FT8_PROTO_FT4
+    t = t.to(device=dev, dtype=torch.uint8).reshape(-1, _lib.FT8_FT4_SYMBOLS if ft4 else FT8_SYMBOL_NUM)
     if t.shape[0] != sig.shape[0]:
         raise ValueError("tones and signals differ in length")
     order = np.argsort(sig["slot"], kind="stable")
@@ -106,7 +133,13 @@ def synthesize(tones, signals, n_slots: int, n_samples: int, sample_rate: int, s
              torch.complex128: _lib.FT8_C128}
     if out.dtype not in codes or out.dim() != 2 or out.stride(1) != 1:
         raise ValueError("out must be a 2-D row-contiguous float32/float64/complex64/complex128 tensor")
-    if sig.size:
+    if sig.size and ft4:
+        d_sig = torch.from_numpy(sig.view(np.uint8).copy()).to(dev)
+        ctx.check(_lib.lib().ft8_ft4_synthesize(ctx.handle, _lib.ptr(t), _lib.ptr(d_sig), int(sig.shape[0]),
+                                                int(sample_rate), _lib.ptr(out), codes[out.dtype], int(out.shape[1]),
+                                                int(out.shape[0]), int(out.stride(0)), _lib.stream_handle(dev)),
+                  "ft8_ft4_synthesize")
+    elif sig.size:
         d_sig = torch.from_numpy(sig.view(np.uint8).copy()).to(dev)
         ctx.check(_lib.lib().ft8_synthesize(ctx.handle, _lib.ptr(t), _lib.ptr(d_sig), int(sig.shape[0]),
                                             int(sample_rate), int(style), _lib.ptr(out), codes[out.dtype],

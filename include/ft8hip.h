@@ -63,7 +63,10 @@ typedef struct ft8_params {
   int32_t f_lo, f_hi;       /* kept STFT bins [f_lo, f_hi) after f >= 0 and the band mask */
   int32_t t_lo, t_hi;       /* kept frames [t_lo, t_hi) after the time mask */
   int32_t flags;            /* FT8_FLAG_* (0: the reference's behaviour exactly) */
-  int32_t reserved;
+  int32_t protocol;         /* FT8_PROTO_FT8 (0: everything as before the field had a meaning) or FT8_PROTO_FT4
+                               ("FT4" below); anything else: FT8_E_ARG.  Honoured by ft8_stft (geometry),
+                               ft8_sync_select and ft8_decode_batch; every other entry point that takes an
+                               ft8_params refuses FT4 with FT8_E_UNSUPPORTED */
   double sample_rate_hz;    /* ABI 2: when > 0, the exact sample rate in Hz, integral or not (the
                                reference takes a float fs: spectrogram_analyse.py:32-34 computes
                                int(0.16 fs) and int(fs / 6.25 bpt) on it, so fs = 12006.3 gives
@@ -792,6 +795,74 @@ int ft8_drift_fit(ft8_ctx* ctx, int32_t stage, const int32_t* d_idx, int32_t n_s
 int ft8_drift_correct(ft8_ctx* ctx, const void* d_samples, int dtype, int64_t n_samples, int32_t n_slots,
                       int64_t slot_stride, const ft8_drift_params* p, void* d_out, ft8_drift_result* d_res,
                       void* stream);
+
+/* ---- FT4 -------------------------------------------------------------------------------------------
+ * Build-defined, outside reference parity: the reference decodes FT8 only, and no vector of another FT4
+ * implementation was available to the build.  The constants are the published protocol's as the build
+ * states them below; INTEROPERABILITY WITH WSJT-X IS NOT VERIFIED.  ft8_demodulator_amd/ft4.py restates
+ * every stage in NumPy and the tests pin the device to it bit for bit.
+ *   symbol      T = 0.048 s: nsps = fs * 6 / 125 samples, which must be an integer (12 000 Hz: 576; 44 100 Hz:
+ *               FT8_E_UNSUPPORTED).  Tone spacing fs / nsps (20.8333 Hz), 4-FSK, modulation index 1.
+ *   STFT        nperseg = nsps, hop = nsps / steps_per_symbol (the reference's noverlap rule), nfft =
+ *               nsps * bins_per_tone, periodic Hann, the same dB formula.
+ *   frame       103 symbols S4 D29 S4 D29 S4 D29 S4.  Sync group m = 0 .. 3 starts at symbol 33 m with the
+ *               tones {0,1,3,2}, {1,0,2,3}, {2,3,1,0}, {3,2,0,1}.  Data symbol k (0 .. 86) sits at k + 4
+ *               (k < 29), k + 8 (k < 58), else k + 12; Gray map {0,1,3,2}, two bits per symbol, MSB first.
+ *   scrambling  the 77 message bits are XORed with rvec = 4a 5e 89 b4 b0 8a 79 55 be 28 (MSB first, 77 bits)
+ *               before CRC-14 and LDPC(174,91); the receiver XORs the decoded 77 bits again.  CRC and parity
+ *               are over the scrambled bits.
+ *   waveform    105 symbols: a ramp-up symbol, the 103, a ramp-down symbol.  GFSK with the frequency pulse
+ *               of ft8_synthesize at BT = 1.0 (length 3 nsps): symbol j's pulse covers the samples
+ *               [(j - 1) nsps, (j + 2) nsps) relative to the start of symbol 0.  No extension pulses: the
+ *               ramp symbols carry tone 0 plus their neighbours' tails.  Envelope (1 - cos(pi i / nsps)) / 2
+ *               over the first symbol, its mirror over the last, 1 between.  The phase is 0 at the
+ *               waveform's first sample and the real part is sin.
+ *   sync score  ft8_sync_score with the layout swapped: m = 0 .. 3 outer, k = 0 .. 3 inner, block = 33 m + k,
+ *               tone = Costas[m][k]; the block test is on floor(abs_time / sps) + block against
+ *               num_blocks = T / sps; the terms are tone - 1 (tone > 0), tone + 1 (tone < 3), time - 1 (k > 0
+ *               and block_abs > 0), time + 1 (k < 3 and block_abs + 1 < num_blocks), each added one after
+ *               another in the waterfall dtype, the sum divided by the term count; -inf for no terms or a
+ *               NaN or infinite sum.  Grid: abs_time in [-10 sps, (num_blocks - 83) sps), abs_freq in
+ *               [0, F - 3 bpt).
+ *   selection   unchanged (the heap rule, or FT8_FLAG_TOPK).
+ *   LLRs        per data symbol s[j] = wf[row][abs_freq + Gray[j] bpt] in double, L[2k] = max(s2, s3) -
+ *               max(s0, s1), L[2k+1] = max(s1, s3) - max(s0, s2); both 0 where the symbol's block lies
+ *               outside [0, num_blocks); then ftx_normalize_logl unchanged.
+ *   back end    unchanged (ft8_bp, the a-priori and OSD passes).  ft8_result.payload of a decode of
+ *               ft8_decode_batch holds the DESCRAMBLED message bits; crc_* are the transmitted (scrambled)
+ *               frame's.  ft8_bp's own records carry scrambled bits (ft8_ft4_unscramble).
+ * ft8_params.protocol = FT8_PROTO_FT4 is honoured by ft8_stft (geometry only), ft8_sync_select and
+ * ft8_decode_batch.  In an FT4 batch FT8_FLAG_TOPK and FT8_FLAG_OSD work unchanged; FT8_FLAG_AP works with the
+ * context's hypotheses in MESSAGE bits (every AP launch takes a copy whose value is XORed with rvec, so the
+ * clamp and the acceptance both work on scrambled bits); FT8_FLAG_COHERENT and FT8_FLAG_SUBTRACT are
+ * FT8_E_UNSUPPORTED, as are ft8_stft_argmax, ft8_subtract, ft8_snr, ft8_coherent_*llr with an FT4 block and
+ * ft8_snr_last after an FT4 batch (follow-ups: DESIGN.md section 15).  ft8_replay_stage after an FT4 batch is
+ * FT8_E_ARG: the descramble step is an involution, not idempotent. */
+#define FT8_PROTO_FT8 0
+#define FT8_PROTO_FT4 1
+#define FT8_FT4_SYMBOLS 103
+/* ft8_geometry_hz for a protocol (host only).  FT8_E_ARG for an unknown protocol, FT8_E_UNSUPPORTED for an FT4
+ * sample rate whose symbol is no whole number of samples. */
+int ft8_geometry_proto(int32_t protocol, double sample_rate_hz, int32_t bins_per_tone, int32_t steps_per_symbol,
+                       int64_t n_samples, int32_t* nperseg, int32_t* hop, int32_t* nfft, int32_t* n_frames);
+/* ft8_llr for FT4: d_cand[n][3] = (slot, abs_time, abs_freq) -> d_llr[n][174] (double). */
+int ft8_ft4_llr(ft8_ctx* ctx, const void* d_wf, int wf_f64, int32_t T, int32_t F, int32_t steps_per_symbol,
+                int32_t bins_per_tone, const int32_t* d_cand, int32_t n, int normalize, double* d_llr,
+                void* stream);
+/* XORs rvec onto the 77 payload bits of d_res[0 .. n) in place; nothing else of a record changes and the low
+ * 3 bits of payload[9] stay.  ft8_decode_batch runs it on its output; it is a stage call because ft8_bp's
+ * records carry scrambled bits.  Its own inverse. */
+int ft8_ft4_unscramble(ft8_ctx* ctx, ft8_result* d_res, int32_t n, void* stream);
+/* ft8_encode for FT4: d_msg[n][10] payloads (77 bits; [9] & 0xF8 is applied) -> d_a91[n][12] (scrambled
+ * payload | CRC-14), d_codeword[n][22], d_tones[n][103]; each output nullable. */
+int ft8_ft4_encode(ft8_ctx* ctx, const uint8_t* d_msg, int32_t n, uint8_t* d_a91, uint8_t* d_codeword,
+                   uint8_t* d_tones, void* stream);
+/* ft8_synthesize for FT4 (its contract: ADDS into d_out in array order, the same dtypes, d_signals sorted by
+ * slot): d_tones[n][103]; ft8_tx_signal.start is the first sample of symbol 0, so a signal covers
+ * [start - nsps, start + 104 nsps).  FT8_E_UNSUPPORTED for a sample rate FT4 does not take. */
+int ft8_ft4_synthesize(ft8_ctx* ctx, const uint8_t* d_tones, const ft8_tx_signal* d_signals, int32_t n_signals,
+                       int32_t sample_rate, void* d_out, int out_dtype, int64_t n_samples, int32_t n_slots,
+                       int64_t slot_stride, void* stream);
 
 /* ---- build provenance --------------------------------------------------------------------- */
 /* SHA-256 prefix of the sources, headers and Makefile the library was compiled from (the Python
