@@ -132,16 +132,18 @@ def normalize(x):
     return out.cpu().numpy()
 
 
-def bp(llrs, max_iterations):
-    """LLRs [n, 174] -> (plain uint8 [n, 174], records structured [n])."""
+def bp(llrs, max_iterations, f32=False):
+    """LLRs [n, 174] -> (plain uint8 [n, 174], records structured [n]).  f32: the float32 decoder
+    (ft8_bp_f32; bp32.bp32_restate is its restatement) instead of the reference's float64."""
     torch = _lib.require_gpu()
     ctx = _lib.context()
     a = _llr_rows(llrs)
     n = a.shape[0]
     plain = torch.zeros(n, 174, dtype=torch.uint8, device=a.device)
     res = torch.zeros(n * _lib.RESULT_DTYPE.itemsize, dtype=torch.uint8, device=a.device)
-    ctx.check(_lib.lib().ft8_bp(ctx.handle, _lib.ptr(a), n, int(max_iterations), _lib.ptr(plain), _lib.ptr(res),
-                                _lib.stream_handle()), "ft8_bp")
+    call, name = (_lib.lib().ft8_bp_f32, "ft8_bp_f32") if f32 else (_lib.lib().ft8_bp, "ft8_bp")
+    ctx.check(call(ctx.handle, _lib.ptr(a), n, int(max_iterations), _lib.ptr(plain), _lib.ptr(res),
+                   _lib.stream_handle()), name)
     return plain.cpu().numpy(), res.cpu().numpy().view(_lib.RESULT_DTYPE)
 
 

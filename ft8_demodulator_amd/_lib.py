@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("FT8HIP_LIB", os.path.join(_HERE, "lib", "libft8hip.so
 FT8_F32, FT8_F64, FT8_C64, FT8_C128, FT8_I16 = 0, 1, 2, 3, 4
 FT8_OK, FT8_E_ARG, FT8_E_HIP, FT8_E_UNSUPPORTED, FT8_E_NOMEM, FT8_E_RANGE = 0, -1, -2, -3, -4, -5
 FT8_FLAG_TOPK, FT8_FLAG_SUBTRACT, FT8_FLAG_AP, FT8_FLAG_COHERENT, FT8_FLAG_OSD = 1, 2, 4, 8, 16
+FT8_FLAG_BP_F32 = 32   # every BP launch of a batch in float32 (csrc/bp32.hip; bp32.py)
 FT8_AP_MAX_HYP = 8
 FT8_PROTO_FT8, FT8_PROTO_FT4 = 0, 1
 FT8_FT4_SYMBOLS = 103
@@ -148,6 +149,7 @@ def lib():
             "ft8_llr": ([vp, vp, ctypes.c_int, i32, i32, i32, i32, vp, i32, ctypes.c_int, vp, vp], ctypes.c_int),
             "ft8_normalize": ([vp, vp, i32, vp, vp], ctypes.c_int),
             "ft8_bp": ([vp, vp, i32, i32, vp, vp, vp], ctypes.c_int),
+            "ft8_bp_f32": ([vp, vp, i32, i32, vp, vp, vp], ctypes.c_int),
             "ft8_decode_batch": ([vp, vp, ctypes.c_int, i64, i32, i64, P, vp, vp, i32, vp], ctypes.c_int),
             "ft8_select_warnings": ([vp, vp, i32, vp], ctypes.c_int),
             "ft8_crc14": ([vp, vp, vp, i32, vp, vp], ctypes.c_int),
@@ -221,7 +223,7 @@ def lib():
 
 # csrc files hashed into FT8_BUILD_ID, in the Makefile's ID_FILES order
 _ID_FILES = ("capi.hip", "stft.hip", "stft3840.hip", "sync.hip", "bp.hip", "tx.hip", "subtract.hip", "drift.hip",
-             "msg.hip", "snr.hip", "ap.hip", "coherent.hip", "osd.hip", "ft4.hip", "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "baseband.h", "heap_replay.h", "msg77.h",
+             "msg.hip", "snr.hip", "ap.hip", "coherent.hip", "osd.hip", "ft4.hip", "bp32.hip", "ft8_internal.h", "ft8_ldpc_tables.h", "tx_device.h", "baseband.h", "heap_replay.h", "msg77.h",
              "div_shared.h", "ft4_device.h", "llr_shared.h", "score_shared.h",
              "../../include/ft8hip.h",
              "Makefile")
@@ -245,7 +247,7 @@ def source_hash():
 EXPORTED_SYMBOLS = (
     "ft8_create", "ft8_destroy", "ft8_last_error", "ft8_abi_version", "ft8_limits", "ft8_geometry",
     "ft8_geometry_hz",
-    "ft8_stft", "ft8_sync_select", "ft8_llr", "ft8_normalize", "ft8_bp", "ft8_decode_batch", "ft8_select_warnings",
+    "ft8_stft", "ft8_sync_select", "ft8_llr", "ft8_normalize", "ft8_bp", "ft8_bp_f32", "ft8_decode_batch", "ft8_select_warnings",
     "ft8_crc14", "ft8_ldpc_check", "ft8_set_timing", "ft8_get_timing", "ft8_get_counters", "ft8_get_bp_clock", "ft8_set_pipeline",
     "ft8_encode", "ft8_synthesize", "ft8_subtract", "ft8_stft_argmax", "ft8_drift_fit", "ft8_drift_correct",
     "ft8_build_id", "ft8_build_flags", "ft8_replay_stage", "ft8_set_timing_stages", "ft8_sync_score",

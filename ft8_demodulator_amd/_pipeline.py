@@ -246,7 +246,7 @@ class SlotDecoder:
                  min_score=10, max_iterations=20, freq_min=None, freq_max=None, time_min=None,
                  time_max=None, device=None, flags=0, max_results_per_slot=None, context=None, ap=None,
                  ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1, subtract=None,
-                 coherent_ap=False, osd=None, osd_max_hard_errors=None, protocol="ft8"):
+                 coherent_ap=False, osd=None, osd_max_hard_errors=None, protocol="ft8", bp32=False):
         """subtract: True or a pass count in [2, 4] (True: 2) -- sets FT8_FLAG_SUBTRACT: what each pass decodes is
         subtracted and the residual decoded again, that many passes in all, every pass with the ap / coherent
         retries asked for below (ft8_set_subtract(n, 1)); the default capacity holds n * max_candidates rows.
@@ -271,7 +271,10 @@ class SlotDecoder:
         max_per_slot candidates (True: order 2 of 32; 0: every one) that every retry above left failed are
         decoded by ordered-statistics decoding of their STFT LLRs (osd.py; ft8_set_osd); None / False: off.
         osd_max_hard_errors: the most hard decisions of an accepted OSD decode that may contradict the received
-        LLRs' signs (default osd.DEFAULT_MAX_HARD_ERRORS = 36; 174: no limit)."""
+        LLRs' signs (default osd.DEFAULT_MAX_HARD_ERRORS = 36; 174: no limit).
+        bp32: True -- sets FT8_FLAG_BP_F32: every belief-propagation launch of a batch (main pass, retries,
+        subtraction passes, FT4) runs in float32 (bp32.py): faster, and no longer bit-identical to the
+        reference's float64 decoder.  False: the reference's arithmetic."""
         from . import ap as _ap
         from . import coherent as _coh
         from . import osd as _osd
@@ -285,6 +288,9 @@ class SlotDecoder:
             if off or coherent_nsym != 1 or flags & (_lib.FT8_FLAG_COHERENT | _lib.FT8_FLAG_SUBTRACT):
                 raise NotImplementedError("FT4 has no coherent re-demodulation and no subtraction yet: "
                                           + ", ".join(off or ["flags"]) + " is not available with protocol='ft4'")
+        self.bp32 = bool(bp32)
+        if self.bp32:
+            flags |= _lib.FT8_FLAG_BP_F32
         self.osd = _osd.parse_option(osd)   # ValueError for what the library refuses
         self.osd_max_hard_errors = _osd.check_max_hard_errors(
             _osd.DEFAULT_MAX_HARD_ERRORS if osd_max_hard_errors is None else osd_max_hard_errors)
@@ -540,7 +546,7 @@ def decode_slots(samples, sample_rate=12000, **kwargs):
 def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_candidates=20, min_score=10,
                max_iterations=20, freq_min=None, freq_max=None, time_min=None, time_max=None, *, flags=0, snr=False,
                ap=None, ap_max_hard_errors=None, coherent=None, coherent_drift=None, coherent_nsym=1, subtract=None,
-               pass_counts=False, coherent_ap=False, osd=None, osd_max_hard_errors=None, protocol="ft8"):
+               pass_counts=False, coherent_ap=False, osd=None, osd_max_hard_errors=None, protocol="ft8", bp32=False):
     """One slot, x [N] on the GPU with its ft8 dtype code, through a SlotDecoder of its own:
     -> (decode_ft8_message's 5-tuples, with snr the ft8_snr_rec records aligned with them else None,
     the ft8_result records) and, with pass_counts (a subtract decode), the slot's row of
@@ -555,7 +561,7 @@ def decode_one(x, code, sample_rate, bins_per_tone=2, steps_per_symbol=2, max_ca
                           freq_min, freq_max, time_min, time_max, device=x.device, flags=flags, ap=ap,
                           ap_max_hard_errors=ap_max_hard_errors, coherent=coherent, coherent_drift=coherent_drift,
                           coherent_nsym=coherent_nsym, subtract=subtract, coherent_ap=coherent_ap, osd=osd,
-                          osd_max_hard_errors=osd_max_hard_errors, protocol=protocol)
+                          osd_max_hard_errors=osd_max_hard_errors, protocol=protocol, bp32=bp32)
         recs, _, reps = (v if v is None else v[0] for v in dec._fetch(x.unsqueeze(0), code, snr=snr))
         if pass_counts:
             per_pass = dec.pass_counts()[0]

@@ -925,7 +925,7 @@ int check_search_params(ft8_ctx* c, const ft8_params* p, bool limit_first) {
   if (p->steps_per_symbol <= 0 || p->bins_per_tone <= 0) return fail(c, FT8_E_ARG, "bad oversampling factors");
   if (p->protocol != FT8_PROTO_FT8 && p->protocol != FT8_PROTO_FT4) return fail(c, FT8_E_ARG, "unknown ft8_params.protocol");
   const bool over = p->max_candidates > kMaxCandidates;
-  if ((p->flags & ~(FT8_FLAG_TOPK | FT8_FLAG_SUBTRACT | FT8_FLAG_AP | FT8_FLAG_COHERENT | FT8_FLAG_OSD)) && !(limit_first && over))
+  if ((p->flags & ~(FT8_FLAG_TOPK | FT8_FLAG_SUBTRACT | FT8_FLAG_AP | FT8_FLAG_COHERENT | FT8_FLAG_OSD | FT8_FLAG_BP_F32)) && !(limit_first && over))
     return fail(c, FT8_E_ARG, "unknown bits in ft8_params.flags");
   if (over) return fail(c, FT8_E_RANGE, "max_candidates > " + std::to_string(kMaxCandidates) + " is not supported");
   return FT8_OK;
@@ -950,10 +950,10 @@ void wire_bp_counters(ft8_ctx* c, BpLaunch& B, int counter, int grid_waves) {
   B.grid_waves = grid_waves;
 }
 
-// k_bp in mode 0 over a retry pass's compacted lists: llr_in / plain_out (nullable) / res_out per
-// list position
+// k_bp (f32: k_bp32, an FT8_FLAG_BP_F32 batch) in mode 0 over a retry pass's compacted lists: llr_in /
+// plain_out (nullable) / res_out per list position
 hipError_t bp_over_lists(ft8_ctx* c, const RetryLists& l, const double* llr_in, uint8_t* plain_out,
-                         ft8_result* res_out, int max_iterations, int counter, hipStream_t s) {
+                         ft8_result* res_out, int max_iterations, int counter, hipStream_t s, bool f32) {
   BpLaunch B{};
   B.cand = l.cand;
   B.cand_score = l.score;
@@ -966,8 +966,9 @@ hipError_t bp_over_lists(ft8_ctx* c, const RetryLists& l, const double* llr_in, 
   B.llr_in = llr_in;
   B.plain_out = plain_out;
   B.res = res_out;
+  B.f32 = f32 ? 1 : 0;
   wire_bp_counters(c, B, counter, c->bp_waves);
-  return launch_bp(B, s);
+  return run_bp(B, s);
 }
 
 // score + select on the scratch `sc`; compact: the score kernel may write only the passing scores
@@ -1040,7 +1041,7 @@ int do_sync_select(ft8_ctx* c, const void* d_wf, int wf_f64, int n_slots, int T,
 // that starts at slot `slot0`; `counter` is the k_bp claim counter the pass's launches draw their
 // tickets from.
 int ap_pass(ft8_ctx* c, const RetryLists& failed, const double* llr, int slot0, int max_iterations, int16_t* hard,
-            int counter, hipStream_t s, int protocol = FT8_PROTO_FT8) {
+            int counter, hipStream_t s, int protocol = FT8_PROTO_FT8, bool f32 = false) {
   const ApRetry::View v = c->ap.at(failed, slot0);
   ApLaunch A{v.lists, llr, {}, 0, c->ap.max_hard, v.amax, v.llr, v.plain, v.res, hard};
   A.r.gate = A.amax;
@@ -1055,7 +1056,7 @@ int ap_pass(ft8_ctx* c, const RetryLists& failed, const double* llr, int slot0, 
     A.h = (int)h;
     if ((e = launch_retry_list(A.r, s)) != hipSuccess) return hipfail(c, e, "ap launch");
     if ((e = launch_ap_clamp(A, s)) != hipSuccess) return hipfail(c, e, "ap launch");
-    if ((e = bp_over_lists(c, A.r, v.llr, v.plain, v.res, max_iterations, counter, s)) != hipSuccess)
+    if ((e = bp_over_lists(c, A.r, v.llr, v.plain, v.res, max_iterations, counter, s, f32)) != hipSuccess)
       return hipfail(c, e, "ap bp launch");
     if ((e = launch_ap_merge(A, s)) != hipSuccess) return hipfail(c, e, "ap launch");
   }
@@ -1120,7 +1121,7 @@ int check_coherent_nsym(ft8_ctx* c, int max_nsym) {
 // list, k_coherent, then per set k_bp over the lists and the merge, on one claim counter as ap_pass's
 // hypotheses.  L: coherent_setup's launch for the chunk's samples.
 int coherent_pass(ft8_ctx* c, CohLaunch L, const CoherentRetry::View& v, int max_iterations, int counter,
-                  hipStream_t s) {
+                  hipStream_t s, bool f32 = false) {
   const RetryLists& l = v.lists;
   hipError_t e = launch_retry_list(l, s);
   if (e != hipSuccess) return hipfail(c, e, "coherent launch");
@@ -1137,7 +1138,7 @@ int coherent_pass(ft8_ctx* c, CohLaunch L, const CoherentRetry::View& v, int max
   for (int n = 0; n < v.nsym; ++n) {
     const double* llr_n = v.llr + (size_t)n * v.set_stride;
     ft8_result* res_n = v.res + (size_t)n * v.n_all;
-    if ((e = bp_over_lists(c, l, llr_n, nullptr, res_n, max_iterations, counter, s)) != hipSuccess)
+    if ((e = bp_over_lists(c, l, llr_n, nullptr, res_n, max_iterations, counter, s, f32)) != hipSuccess)
       return hipfail(c, e, "coherent bp launch");
     const CohPass A{l, v.fit, res_n, v.drift, v.valid, n};
     if ((e = launch_coh_merge(A, s)) != hipSuccess) return hipfail(c, e, "coherent launch");
@@ -1161,7 +1162,8 @@ CohApLaunch coherent_ap_input(const CoherentRetry::View& v) {
 // The stage over one chunk (ap.hip): A.res / n_slots / N / M / S and the coherent list, fits, validity
 // bytes, drift records and LLRs are the caller's; the hypotheses, the limit and the scratch of the chunk
 // that starts at slot `slot0` are filled in here.  Five launches.
-int coherent_ap_pass(ft8_ctx* c, CohApLaunch A, int slot0, int max_iterations, int counter, hipStream_t s) {
+int coherent_ap_pass(ft8_ctx* c, CohApLaunch A, int slot0, int max_iterations, int counter, hipStream_t s,
+                     bool f32 = false) {
   A.H = (int)c->ap.hyps.size();
   for (int h = 0; h < A.H; ++h) A.hyp[h] = c->ap.hyps[h];
   A.max_hard = c->ap.max_hard;
@@ -1176,7 +1178,7 @@ int coherent_ap_pass(ft8_ctx* c, CohApLaunch A, int slot0, int max_iterations, i
   if (e == hipSuccess) e = launch_cohap_list(A, s);
   if (e == hipSuccess) e = launch_cohap_clamp(A, s);
   if (e != hipSuccess) return hipfail(c, e, "coherent ap launch");
-  if ((e = bp_over_lists(c, A.att, v.llr, v.plain, v.res, max_iterations, counter, s)) != hipSuccess)
+  if ((e = bp_over_lists(c, A.att, v.llr, v.plain, v.res, max_iterations, counter, s, f32)) != hipSuccess)
     return hipfail(c, e, "coherent ap bp launch");
   if ((e = launch_cohap_merge(A, s)) != hipSuccess) return hipfail(c, e, "coherent ap launch");
   return FT8_OK;
@@ -1233,19 +1235,20 @@ int ensure_retry_scratch(ft8_ctx* c, int flags, size_t n_slots, int N) {
 int retry_passes(ft8_ctx* c, const RetryLists& failed, const double* llr, const void* xs, int dtype, int64_t n_samples,
                  int64_t slot_stride, const ft8_params* p, int slot0, int k, int n_chunks, hipStream_t s) {
   int rc;
+  const bool f32 = (p->flags & FT8_FLAG_BP_F32) != 0;  // every BP launch of the batch runs k_bp32
   if (p->flags & FT8_FLAG_COHERENT) {
     CohLaunch L;
     if ((rc = coherent_setup(c, xs, dtype, n_samples, failed.n_slots, slot_stride, p, c->coh.nsym > 1, &L))) return rc;
     const CoherentRetry::View v = c->coh.at(failed, slot0);
-    if ((rc = coherent_pass(c, L, v, p->max_iterations, bp_counter(kChunkCoherent, k, n_chunks), s))) return rc;
+    if ((rc = coherent_pass(c, L, v, p->max_iterations, bp_counter(kChunkCoherent, k, n_chunks), s, f32))) return rc;
     if (coherent_ap_on(c, p->flags) &&
         (rc = coherent_ap_pass(c, coherent_ap_input(v), slot0, p->max_iterations,
-                               bp_counter(kChunkCoherentAp, k, n_chunks), s)))
+                               bp_counter(kChunkCoherentAp, k, n_chunks), s, f32)))
       return rc;
   }
   if ((p->flags & FT8_FLAG_AP) &&
       (rc = ap_pass(c, failed, llr, slot0, p->max_iterations, nullptr, bp_counter(kChunkAp, k, n_chunks), s,
-                    p->protocol)))
+                    p->protocol, f32)))
     return rc;
   if ((p->flags & FT8_FLAG_OSD) && (rc = osd_pass(c, failed, llr, slot0, s))) return rc;
   return FT8_OK;
@@ -1341,13 +1344,14 @@ int decode_pass(ft8_ctx* c, const void* d_samples, int dtype, int64_t n_samples,
     B.llr_out = c->llr.as<double>() + (size_t)FT8_LDPC_N * c0 * N;
     B.llr_in = B.llr_out;
     B.res = c->res_all.as<ft8_result>() + (size_t)c0 * N;
+    B.f32 = (f & FT8_FLAG_BP_F32) ? 1 : 0;
     wire_bp_counters(c, B, bp_counter(kChunkBp, k, n_chunks), c->bp_waves);
     B.tie = sc.tie;
     B.warn = sc.warn;
     const bool ft4 = p->protocol == FT8_PROTO_FT4;
     if ((rc = timed_launch(c, kLlr, cs, "llr launch", [&] { return ft4 ? launch_llr4(B, cs) : launch_llr(B, cs); })))
       return rc;
-    if ((rc = timed_launch(c, kBp, cs, "bp launch", [&] { return launch_bp(B, cs); }))) return rc;
+    if ((rc = timed_launch(c, kBp, cs, "bp launch", [&] { return run_bp(B, cs); }))) return rc;
     // the tie order k_compact applies permutes positions, not records, so the coherent and AP passes
     // work on res_all as it is; the coherent pass leaves c->llr alone, so AP sees the STFT LLRs
     RetryLists failed{};
@@ -1749,8 +1753,9 @@ int ft8_normalize(ft8_ctx* c, const double* d_in, int32_t n, double* d_out, void
   return timed_launch(c, kLlr, s, "normalize launch", [&] { return launch_llr(L, s); });
 }
 
-int ft8_bp(ft8_ctx* c, const double* d_llr, int32_t n, int32_t max_iterations, uint8_t* d_plain, ft8_result* d_res,
-           void* stream) {
+// ft8_bp and ft8_bp_f32: one stage call, the kernel and its grid residency apart
+static int bp_stage_call(ft8_ctx* c, const double* d_llr, int32_t n, int32_t max_iterations, uint8_t* d_plain,
+                  ft8_result* d_res, void* stream, bool f32) {
   StreamOrder order_(c, (hipStream_t)stream);
   if (c) c->replay_ok = c->snr_ok = false;
   if (!c || (!d_llr && n > 0)) return fail(c, FT8_E_ARG, "bad argument");
@@ -1766,9 +1771,21 @@ int ft8_bp(ft8_ctx* c, const double* d_llr, int32_t n, int32_t max_iterations, u
   L.max_iterations = max_iterations;
   L.plain_out = d_plain;
   L.res = d_res;
-  wire_bp_counters(c, L, bp_counter(kCallerBp, 0, 0), L.grid_waves);  // BpLaunch's default residency, not the pipeline's
+  L.f32 = f32 ? 1 : 0;
+  // ft8_bp: BpLaunch's default residency, not the pipeline's; ft8_bp_f32: the pipeline's (ft8_set_pipeline)
+  wire_bp_counters(c, L, bp_counter(kCallerBp, 0, 0), f32 ? c->bp_waves : L.grid_waves);
   hipStream_t s = (hipStream_t)stream;
-  return timed_launch(c, kBp, s, "bp launch", [&] { return launch_bp(L, s); });
+  return timed_launch(c, kBp, s, "bp launch", [&] { return run_bp(L, s); });
+}
+
+int ft8_bp(ft8_ctx* c, const double* d_llr, int32_t n, int32_t max_iterations, uint8_t* d_plain, ft8_result* d_res,
+           void* stream) {
+  return bp_stage_call(c, d_llr, n, max_iterations, d_plain, d_res, stream, false);
+}
+
+int ft8_bp_f32(ft8_ctx* c, const double* d_llr, int32_t n, int32_t max_iterations, uint8_t* d_plain,
+               ft8_result* d_res, void* stream) {
+  return bp_stage_call(c, d_llr, n, max_iterations, d_plain, d_res, stream, true);
 }
 
 int ft8_set_ap(ft8_ctx* c, const ft8_ap_hyp* hyps, int32_t n, int32_t max_hard_errors) {
@@ -2311,7 +2328,7 @@ int ft8_replay_stage(ft8_ctx* c, int32_t stage, int32_t reps, void* stream) {
       case kStft: e = launch_stft(c->last_stft, s); break;
       case kScore: e = launch_score(c->last_sync, s); break;
       case kSelect: e = launch_select(c->last_sync, s); break;
-      case kBp: e = launch_bp(c->last_bp, s); break;
+      case kBp: e = run_bp(c->last_bp, s); break;  // the kernel that ran (BpLaunch.f32)
       case kCompact: e = launch_compact(c->last_compact, s); break;
       case kLlr: e = launch_llr(c->last_bp, s); break;
       default: return fail(c, FT8_E_ARG, "stage " + std::to_string(stage) + " cannot be replayed");

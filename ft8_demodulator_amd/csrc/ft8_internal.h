@@ -277,6 +277,7 @@ struct BpLaunch {
   unsigned long long* clock = nullptr;  // timed launches: [wave cycles, wave wall ticks, max wave cycles, waves]
   int slot0 = 0;           // batch index of slot 0 (records carry slot0 + local slot)
   int grid_waves = 4;      // k_bp persistent grid: resident waves per SIMD (clamped to 4)
+  int f32 = 0;             // 1: the float32 decoder k_bp32 (bp32.hip) runs this launch (run_bp)
   // mode 0, nullable: slots whose order of equal scores k_select deferred (warn bit 3) get it
   // replayed by k_llr's first workgroups
   int32_t* tie = nullptr;  // [n_slots][tie_stride(N)]
@@ -284,6 +285,12 @@ struct BpLaunch {
 };
 hipError_t launch_llr(const BpLaunch& a, hipStream_t s);  // k_llr: waterfall -> LLRs
 hipError_t launch_bp(const BpLaunch& a, hipStream_t s);   // k_bp: LLRs -> BP + CRC
+// k_bp32 (bp32.hip): launch_bp's modes 0 and 2 in IEEE binary32, two candidates per wave.  The same host
+// protocol on the same counters, but a claim takes two tickets: the launch advances *work_base by
+// 2 (ceil(n_items / 2) + waves).
+hipError_t launch_bp32(const BpLaunch& a, hipStream_t s);
+// the kernel the launch names (BpLaunch.f32)
+inline hipError_t run_bp(const BpLaunch& a, hipStream_t s) { return a.f32 ? launch_bp32(a, s) : launch_bp(a, s); }
 // FT4 (ft4.hip): k_llr4, launch_llr's modes 0 and 1 with the FT4 symbol layout.  It does not run the
 // deferred tie order of mode 0 beside its workgroups: launch_tie_order (bp.hip, one wave per slot) does.
 hipError_t launch_llr4(const BpLaunch& a, hipStream_t s);

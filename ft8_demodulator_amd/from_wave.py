@@ -303,6 +303,9 @@ def main(argv=None):
                              "with the order)")
     parser.add_argument("--osd-max-hard-errors", type=int, default=None,
                         help="most hard decisions of an OSD decode that may contradict the received bits (default 36)")
+    parser.add_argument("--bp32", action="store_true",
+                        help="run belief propagation in float32 (faster; decodes are no longer bit-identical to "
+                             "the reference's float64 decoder)")
     parser.add_argument("--selection", choices=("reference", "topk"), default="reference",
                         help="candidate selection: the reference's, or the max-candidates highest scores")
     parser.add_argument("--ft4", action="store_true",
@@ -351,7 +354,7 @@ def main(argv=None):
               max_candidates=args.max_candidates, min_score=args.min_score, max_iterations=args.max_iterations)
     many = len(paths) > 1
     if (args.ap or args.snr or coherent is not None or args.subtract is not None or args.osd is not None
-            or args.selection != "reference" or args.ft4):
+            or args.selection != "reference" or args.ft4 or args.bp32):
         # the report comes from the decode's own waterfall, an AP decode's mark from its own record:
         # one file at a time, each decoded once (lazily: a file is printed before the next is decoded)
         if args.correction:
@@ -368,6 +371,8 @@ def main(argv=None):
             kw = dict(kw, selection=args.selection)
         if args.ft4:
             kw = dict(kw, protocol="ft4")
+        if args.bp32:
+            kw = dict(kw, bp32=True)
         if args.subtract is not None:
             kw = dict(kw, subtract=args.subtract)
         if args.osd is not None:

@@ -24,9 +24,10 @@ def bp_decode(codeword: np.ndarray, max_iterations: int) -> Tuple[np.ndarray, in
     return plain[0].astype(np.uint8), int(rec[0]["ldpc_errors"])
 
 
-def bp_decode_batch(codewords: np.ndarray, max_iterations: int):
-    """Batched bp_decode: LLRs [n, 174] -> (plain [n, 174] uint8, min_errors [n])."""
-    plain, rec = _device.bp(np.asarray(codewords, dtype=np.float64).reshape(-1, FTX_LDPC_N), max_iterations)
+def bp_decode_batch(codewords: np.ndarray, max_iterations: int, f32: bool = False):
+    """Batched bp_decode: LLRs [n, 174] -> (plain [n, 174] uint8, min_errors [n]).  f32: the opt-in float32
+    decoder (k_bp32, csrc/bp32.hip), bit-identical to bp32.bp32_restate instead of the reference."""
+    plain, rec = _device.bp(np.asarray(codewords, dtype=np.float64).reshape(-1, FTX_LDPC_N), max_iterations, f32)
     return plain, rec["ldpc_errors"].astype(np.int64)
 
 

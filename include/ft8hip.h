@@ -102,12 +102,17 @@ typedef struct ft8_params {
  *                      after the passes above by ordered-statistics decoding of their STFT LLRs
  *                      ("ordered-statistics decoding" below; ft8_set_osd: order, cap per slot, hard-error
  *                      limit).  Rescued candidates come out in candidate order among the other decodes with
- *                      pass_index >> 4 = 15.  With FT8_FLAG_SUBTRACT only after ft8_set_subtract(ctx, n, 1). */
+ *                      pass_index >> 4 = 15.  With FT8_FLAG_SUBTRACT only after ft8_set_subtract(ctx, n, 1).
+ *   FT8_FLAG_BP_F32    every belief-propagation launch of the batch (the main pass, the a-priori, coherent and
+ *                      coherent-AP retries, every subtraction pass, FT4) runs in IEEE binary32 instead of
+ *                      float64 ("float32 belief propagation" below).  Decodes are then no longer bit-identical
+ *                      to the reference's, but to the restatement named there; no record mark. */
 #define FT8_FLAG_TOPK 1
 #define FT8_FLAG_SUBTRACT 2
 #define FT8_FLAG_AP 4
 #define FT8_FLAG_COHERENT 8
 #define FT8_FLAG_OSD 16
+#define FT8_FLAG_BP_F32 32
 
 /* One decoded (or attempted) candidate, 40 bytes, 8-byte aligned. */
 typedef struct ft8_result {
@@ -635,6 +640,26 @@ int ft8_osd_decode(ft8_ctx* ctx, const double* d_llr, ft8_result* d_res, int32_t
  *        to order them, bit 3 (informational): that replay ran outside the selection kernel
  *        (beside the LLRs in ft8_decode_batch). */
 int ft8_select_warnings(ft8_ctx* ctx, int32_t* d_out, int32_t n_slots, void* stream);
+
+/* ---- float32 belief propagation (build-defined, opt-in; no reference counterpart) --------------------
+ * The reference's decoder is float64 because NumPy made it so; the C library it ports is float32.  ft8_bp_f32
+ * and FT8_FLAG_BP_F32 run the same algorithm in IEEE binary32 (csrc/bp32.hip, k_bp32: two candidates per
+ * wave, packed float32 arithmetic).  With the flag clear nothing changes.  The contract, per candidate
+ * (bp32.bp32_restate is its NumPy restatement, bit for bit):
+ *   - the 174 input LLRs (double) are rounded to nearest float32 (beyond its range: +-inf; below: subnormal, 0);
+ *   - every later operation is IEEE binary32, round to nearest, no FMA contraction, subnormals kept, in the
+ *     reference's order (ldpc_decoder.py:54-113): messages = c + ((t0 + t1) + t2); Tnm = c + the other two
+ *     tov in kFTX_LDPC_Mn order; toc = fast_tanh(-Tnm / 2) with np.clip to +-4.97 rounded to float32 (NaN
+ *     passes); Tmn = the left-to-right product of the check's other toc starting from 1.0f;
+ *     tov = -2 fast_atanh(Tmn);
+ *   - the all-zero stop, the errors < min_errors rule, the unread update of the last iteration, the CRC-14
+ *     tail and every ft8_result field are ft8_bp's.
+ * NaN and +-inf LLRs behave as the restatement does.  ft8_bp_f32 has ft8_bp's signature and argument checks;
+ * its persistent grid follows ft8_set_pipeline's bp_waves_per_simd (ft8_bp's does not).  In a batch the flag
+ * is a property of the batch: OSD reads LLRs only and is unaffected, and ft8_replay_stage replays the kernel
+ * that ran. */
+int ft8_bp_f32(ft8_ctx* ctx, const double* d_llr, int32_t n, int32_t max_iterations,
+               uint8_t* d_plain, ft8_result* d_res, void* stream);
 
 /* ---- small device utilities used by the Python mirror of crc.py / ldpc_check ---------------- */
 /* CRC-14 (crc.py:11-39) of d_msg[n][12] over d_nbits[n] bits -> d_crc[n]. */
